@@ -17,13 +17,20 @@ N > 1 (one process per GPU, RCCL): weak scaling -- every rank embeds its own Q i
 is row-sharded N ways; all_gather of the packed query codes, per-shard ranking of all N*Q queries,
 all_to_all of the per-shard lists, GPU merge (wvhash/parallel.py).  value = N*Q / step time.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (dominant kernel, live HIP-event timing),
-"kernels" (every stage of the step, then rows "not in the step": the other BASELINE shapes -- c0, c3 -- and SURVEY 8(d)'s
-grid of wavelets / batch sizes / head shapes, and the deferred SharedDinoHashing pipeline with a random-init ViT-S/14
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: setup (including the placement
+probe of the sub-band buffer), clock-ramp and warm-up steps, the K timed steps.  N > 1: config.exchange carries the
+collectives counted per timed step and whether the hinted list prefix was long enough.
+
+--full adds everything else the benchmark measures or checks.  Extra objects: "roofline" (dominant kernel, live HIP-event
+timing), "kernels" (every stage of the step, then rows "not in the step": the other BASELINE shapes -- c0, c3 -- and SURVEY
+8(d)'s grid of wavelets / batch sizes / head shapes, and the deferred SharedDinoHashing pipeline with a random-init ViT-S/14
 consuming the sub-bands), "cpu_baseline" (the oracle = CPU port of the reference's op sequence, timed on this host's cores
 on a bounded sample, N = 1 only).  N = 1 also reports "value_first_allocation": the same K steps timed BEFORE the two
-setup steps that lift "value" (placement probe of the sub-band buffer, clock-ramp steps).  N > 1: config.exchange carries
-the collectives counted per timed step and per-rank kernel / collective milliseconds.
+setup steps that lift "value" (placement probe of the sub-band buffer, clock-ramp steps).  N > 1: config.exchange also
+carries the check against the unsharded kernel and per-rank kernel / collective milliseconds.
+
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (dump_outputs()); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -62,13 +69,19 @@ def parse():
                          "speeding up for ~25 steps (~35 ms) while the GPU's clocks ramp (kernel trace: head front 265 -> 212 us, "
                          "ranking 63 -> 49 us, the HBM-bound SWT unchanged); 0 = measure the ramp")
     ap.add_argument("--queries", type=int, default=Q_PER_GPU, help="query images per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-grid", action="store_true", help="skip the kernel rows that are not part of the step (c0 / c3 / SURVEY 8(d) grid)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: first-allocation steps, roofline, kernel "
+                         "table and grid, CPU baseline (N = 1); unsharded-kernel check and per-rank breakdown (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-grid", action="store_true",
+                    help="with --full: skip the kernel rows that are not part of the step (c0 / c3 / SURVEY 8(d) grid)")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("WV_BENCH_STREAMS", "0")), choices=(0, 1, 2),
                     help="2: the SWT of a batch runs on its own HIP stream, started when the head is done, beside hash tail, search "
                          "and collectives (stage pipelining); 1: everything on one stream; 0 (default): 1 on one GPU -- where the two "
                          "are equal within noise -- and 2 on several, where the exchange's latency hides behind the transform")
-    ap.add_argument("--kernel-reps", type=int, default=10, help="launches per stage for the roofline timing")
+    ap.add_argument("--kernel-reps", type=int, default=10, help="with --full: launches per stage for the roofline timing")
     return ap.parse_args()
 
 
@@ -623,10 +636,41 @@ def timed_steps(p, steps, barrier):
         barrier()
         elapsed = time.perf_counter() - t0
     trace, parallel.TRACE = parallel.TRACE, None
-    syncs = None if staged else sum(1 for w in caught if "synchroniz" in str(w.message).lower())
+    # "called a synchronizing ... operation"; not the one-time notice the first set_sync_debug_mode() of a process prints
+    # ("... does not yet detect all synchronizing operations")
+    syncs = None if staged else sum(1 for w in caught if "called a synchronizing" in str(w.message).lower())
     marks, p.marks = p.marks, None
     swt_ms = [a[1].elapsed_time(b[1]) for a, b in zip(marks[0::2], marks[1::2])]
     return elapsed, out, sum(swt_ms) / max(len(swt_ms), 1), trace, syncs
+
+
+BANDS_SAMPLE = 1 << 22      # sub-band values dumped per run (16 MB): the full [Q,3,4,224,224] output is 4.9 GB
+
+
+def dump_outputs(dirname, p, out):
+    """What the last timed step returned, as float32 / float64 .npy files (with N > 1 every rank writes its own, suffixed
+    .rank<r>):
+      bands_sample  [BANDS_SAMPLE / N] f32  sub-band values at fixed seeded positions of the [Q,3,4,H,W] view (either layout)
+      code_bits     [Q, NBITS] f32          the packed query codes, one 0 / 1 per bit (bit j of word w = code 64w + j)
+      ap            [Q] f32                 average precision per query
+      map_at_5000   [1] f64                 their mean over this rank's queries"""
+    bands, packed, _, ap = out
+    view = bands.permute(1, 2, 0, 3, 4) if p.band_major else bands          # band-major [4,Q,3,H,W] -> [Q,3,4,H,W]
+    g = torch.Generator(device="cpu").manual_seed(0)
+    flat = torch.randint(0, view.numel(), (BANDS_SAMPLE // p.world,), generator=g, dtype=torch.int64).sort().values
+    pos = []
+    for n in reversed(view.shape):
+        pos.append(flat % n)
+        flat = flat // n
+    sample = view[tuple(i.to(view.device) for i in reversed(pos))]
+    shifts = torch.arange(64, device=packed.device, dtype=torch.int64)
+    bits = ((packed.unsqueeze(-1) >> shifts) & 1).reshape(packed.shape[0], -1)[:, :NBITS]
+    arrays = {"bands_sample": sample.float(), "code_bits": bits.float(), "ap": ap.float(),
+              "map_at_5000": ap.double().mean().reshape(1)}
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f".rank{p.rank}" if p.world > 1 else ""
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), t.cpu().numpy())
 
 
 def per_rank_breakdown(p, reps=5):
@@ -705,7 +749,7 @@ def run(args, rank, world, device):
     out = p.step()                     # untimed: sizes the list exchange exactly (one host read), compiles nothing
     p.learn_send_hint()
     first = None
-    if world == 1:
+    if world == 1 and args.full:
         # ---- as allocated, clocks as they are: W warm-up steps, K timed steps -- before the two setup steps below
         for _ in range(args.warmup):
             p.step()
@@ -727,6 +771,17 @@ def run(args, rank, world, device):
                            dtype=torch.int32, device=cdev)
         dist.all_reduce(bad, op=dist.ReduceOp.MAX)             # every rank learns whether any rank fell short
         ok, lean = int(bad[0].item()) == 0, int(bad[1].item()) == 0
+        exchange = {"prefix_entries": p.send_hint, "max_possible": p.kin, "verified_exact": ok,
+                    "collectives_per_timed_step": {k: v for k, v in per_step.items()},
+                    "one_all_gather_one_all_to_all_per_step": lean,
+                    "bytes_sent_per_rank_per_timed_step": {k: v // args.steps for k, v in trace.bytes.items() if v},
+                    "host_syncs_in_timed_steps": host_syncs}
+        if not ok:
+            raise SystemExit(f"a timed step needed a longer list prefix than the hinted {p.send_hint}: the results of "
+                             "that step are not exact, refusing to report a number")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, p, out)
+    if world > 1 and args.full:
         # the sharded result of the last timed step against the unsharded kernel on THIS rank's queries and the whole
         # database (every rank holds it: 200 KB): the exchange over the real fabric must reproduce it bit for bit
         with torch.no_grad():
@@ -737,16 +792,8 @@ def run(args, rank, world, device):
         mine = per_rank_breakdown(p)
         ranks = [None] * world
         dist.all_gather_object(ranks, mine)
-        exchange = {"prefix_entries": p.send_hint, "max_possible": p.kin, "verified_exact": ok,
-                    "ap_equals_unsharded_kernel_on_every_rank": matches,
-                    "collectives_per_timed_step": {k: v for k, v in per_step.items()},
-                    "one_all_gather_one_all_to_all_per_step": lean,
-                    "bytes_sent_per_rank_per_timed_step": {k: v // args.steps for k, v in trace.bytes.items() if v},
-                    "host_syncs_in_timed_steps": host_syncs,
-                    "per_rank": ranks}
-        if not ok:
-            raise SystemExit(f"a timed step needed a longer list prefix than the hinted {p.send_hint}: the results of "
-                             "that step are not exact, refusing to report a number")
+        exchange["ap_equals_unsharded_kernel_on_every_rank"] = matches
+        exchange["per_rank"] = ranks
         if not matches:
             raise SystemExit("the sharded search's average precisions differ from the unsharded kernel's on the same queries: "
                              "refusing to report a number")
@@ -797,7 +844,7 @@ def run(args, rank, world, device):
         result["first_allocation"] = {"ms_per_step": first["ms_per_step"], "swt_ms": first["swt_ms"],
                                       "what": f"{args.warmup} warm-up + {args.steps} timed steps on the sub-band buffer as first "
                                               "allocated, no clock-ramp steps; run before the tuned measurement"}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         kt = kernel_table(p, args.kernel_reps, swt_ms_live)
         dom = max((k for k in kt if "not in the step" not in k["kernel"] and not k["kernel"].startswith("wv_hamming_dist")),
                   key=lambda k: k["ms"])

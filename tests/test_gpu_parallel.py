@@ -128,7 +128,7 @@ def test_bench_launches_its_own_ranks(tmp_path, gpus):
     CPU with kernel stand-ins, tests/test_parallel_gloo.py.)  A steady-state step issues exactly one all_gather and one
     all_to_all; the line carries every rank's kernel / collective milliseconds."""
     import json
-    out = _run_bench(["--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--queries", "256"])
+    out = _run_bench(["--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--queries", "256", "--full"])
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -163,12 +163,33 @@ def test_bench_rank_failing_in_setup_ends_the_run_with_its_reason():
 
 def test_single_gpu_bench_line_carries_the_untuned_number_and_no_host_sync():
     import json
-    out = _run_bench(["--steps", "3", "--warmup", "1", "--queries", "256", "--no-cpu-baseline", "--no-grid", "--clock-steps", "2"])
+    out = _run_bench(["--steps", "3", "--warmup", "1", "--queries", "256", "--full", "--no-cpu-baseline", "--no-grid",
+                     "--clock-steps", "2"])
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert rec["value_first_allocation"] > 0 and rec["first_allocation"]["ms_per_step"] > 0
     assert rec["config"]["host_syncs_in_timed_steps"] == 0
     assert rec["roofline"]["frac"] > 0 and rec["config"]["swt_output_placement"]["candidates"] >= 1
+
+
+def test_plain_bench_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes what the last timed step returned, as
+    float32 / float64 arrays within 64 MB, whose mean AP is the line's mAP."""
+    import json
+    import numpy as np
+    out = _run_bench(["--steps", "4", "--warmup", "1", "--queries", "256", "--clock-steps", "2", "--dump-outputs", str(tmp_path)])
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert rec["steps"] == 4 and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["higher_is_better"] is True
+    assert not {"roofline", "kernels", "cpu_baseline", "value_first_allocation"} & set(rec)
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["ap.npy", "bands_sample.npy", "code_bits.npy", "map_at_5000.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    arrs = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+    assert arrs["code_bits"].shape == (256, 64) and set(np.unique(arrs["code_bits"])) <= {0.0, 1.0}
+    assert arrs["ap"].shape == (256,) and abs(float(arrs["map_at_5000"][0]) - rec["map_at_5000"]) < 1e-6
+    assert arrs["bands_sample"].shape == (1 << 22,) and np.abs(arrs["bands_sample"]).max() > 0
 
 
 # ----------------------------------------------------------------------------------------- real-valued k-NN, row-sharded

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/<tag>_* (tools/profile_round.sh <tag>) -> profiles/<out>_bench.json, <out>_bench_kernel_stats.csv,
+"""$PROFILE_OUT/<tag>_* (default profile_out/; tools/profile_round.sh <tag>) -> profiles/<out>_bench.json, <out>_bench_kernel_stats.csv,
 <out>_pmc.csv (means per launch of the kernels of interest) and traffic_<round>.json.
 usage: python tools/summarize_profiles.py r02b r02"""
 import csv
@@ -11,7 +11,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag, out = sys.argv[1], sys.argv[2]
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.environ.get("PROFILE_OUT", os.path.join(ROOT, "profile_out")), os.path.join(ROOT, "profiles")
 KERNELS = {"swt": "k_swt_slide", "topk": "k_rank_window", "rankmap": "k_rank_window", "head": "k_head_front"}
 
 shutil.copy(os.path.join(G, f"{tag}_bench.json"), os.path.join(P, f"{out}_bench.json"))
