@@ -19,21 +19,16 @@
 //   horizontal pass: thread = 4 adjacent outputs of one row; the taps come from NV aligned
 //                   float4 reads of that row (NV = 3..5) instead of 4*L scalar reads
 // Generic kernels (k_axis_generic): any tap count / any size, one level per launch through a
-// caller workspace; used only when the tiled kernel's constraints do not hold.
-#include "common.hpp"
-#include "swt_fused.hpp"
+// caller workspace.
+// Which of the four implementations runs is decided in one place, choose() below: the sliding
+// kernel (swt_slide.hip), else the fused one (swt_fused.hip), else the tiled one, else generic.
+#include "swt.hpp"
 
 namespace wv {
 
 constexpr int kMaxLevels = 4;
 constexpr int kSwtThreads = 256;
 constexpr int kVR = 4;  // vertical outputs per thread (same dilation phase)
-
-template <int L>
-struct Taps {
-    float lo[L];
-    float hi[L];
-};
 
 struct PassDesc {
     int rstart, nrows;        // output rows of this level (LDS row coordinates)
@@ -56,13 +51,6 @@ struct SwtGeom {
 __device__ __forceinline__ uint32_t fast_div(uint32_t u, uint32_t d, uint32_t magic)
 {
     return d == 1 ? u : __umulhi(u, magic);
-}
-
-__device__ __forceinline__ int wrap(int v, int n)
-{
-    while (v < 0) v += n;
-    while (v >= n) v -= n;
-    return v;
 }
 
 __device__ __forceinline__ float4 load4_as_f32(const uint8_t *p, int stride)
@@ -397,34 +385,29 @@ static size_t tile_lds_bytes(int L, int n, int TH, int TW, SwtGeom *out)
     return ((size_t)2 * ((size_t)RH * RW + 2 * G) + (size_t)TH * RW + 2 * G) * sizeof(float);
 }
 
-static TilePlan plan_tiles(int B, int C, int H, int W, int L, int n, int in_layout)
+// The tiled kernel's geometry for a shape (it ignores dtypes and layout); ok = the shape fits it.
+static TilePlan plan_tiles(const SwtShape &s)
 {
     TilePlan p{};
     p.ok = false;
+    const int L = s.L, n = s.level, H = s.H, W = s.W;
     if (!(L == 2 || L == 4 || L == 8 || L == 10) || n < 1 || n > 3 || (W % 4) != 0) return p;
     // column tiles: split W evenly into pieces of <= 128 (multiples of 4)
     int tilesX = (int)ceil_div(W, 128);
     int TW = (int)align_up(ceil_div(W, tilesX), 4);
-    int TH = 32;
-    const char *env = ::wv::tune("WV_SWT_TILE");  // "TH,TW" override for tuning
-    int eth = 0, etw = 0;
-    if (env && sscanf(env, "%d,%d", &eth, &etw) == 2 && eth > 0 && etw > 0 && etw % 4 == 0) {
-        TH = eth; TW = etw;
-    } else {
-        if (TH > H) TH = H;
-        const size_t two_per_cu = 78 * 1024;
-        while (TH > 8 && tile_lds_bytes(L, n, TH, TW, nullptr) > two_per_cu) TH -= 8;
-        if (tile_lds_bytes(L, n, TH, TW, nullptr) > two_per_cu) {
-            TH = H < 32 ? H : 32;  // accept one workgroup per CU
-            while (TH > 4 && tile_lds_bytes(L, n, TH, TW, nullptr) > (size_t)kMaxLdsBytes - 1024) TH -= 4;
-        }
+    int TH = H < 32 ? H : 32;
+    const size_t two_per_cu = 78 * 1024;
+    while (TH > 8 && tile_lds_bytes(L, n, TH, TW, nullptr) > two_per_cu) TH -= 8;
+    if (tile_lds_bytes(L, n, TH, TW, nullptr) > two_per_cu) {
+        TH = H < 32 ? H : 32;  // accept one workgroup per CU
+        while (TH > 4 && tile_lds_bytes(L, n, TH, TW, nullptr) > (size_t)kMaxLdsBytes - 1024) TH -= 4;
     }
     if (TW > W) TW = W;
     tilesX = (int)ceil_div(W, TW);
     SwtGeom &g = p.g;
     p.lds_bytes = tile_lds_bytes(L, n, TH, TW, &g);
     if (p.lds_bytes > (size_t)kMaxLdsBytes - 1024) return p;
-    g.B = B; g.C = C; g.H = H; g.W = W; g.tilesX = tilesX; g.in_layout = in_layout;
+    g.B = s.B; g.C = s.C; g.H = H; g.W = W; g.tilesX = tilesX; g.in_layout = s.in_layout;
     g.ncg = g.RW / 4; g.ncg_magic = magic_of(g.ncg);
     if ((uint64_t)g.RH * g.ncg * 4 >= (1ull << 32) / (g.ncg + 1)) return p;  // fast_div range
     for (int l = 1; l <= n; ++l) {
@@ -530,28 +513,49 @@ static int run_generic(const void *in, void *out, int B, int C, int H, int W, in
     return WV_OK;
 }
 
-template <typename InT, typename OutT>
-static int swt_typed(const void *in, void *out, int B, int C, int H, int W, int n, const float *lo,
-                     const float *hi, int L, int in_layout, void *ws, size_t ws_bytes, hipStream_t st)
+enum class SwtPath { Slide, Fused, Tiled, Generic };
+
+// Which kernel computes a shape: the first of slide, fused, tiled that fits it, else the generic per-level kernels (the
+// only path that needs a workspace).  WV_SWT_PATH = slide | fused | tiled | generic (diagnostic library only) pins one
+// path for tests: the pinned path if the shape fits it, else generic.
+// Invariant that lets wv_swt2d_workspace_bytes() do without dtypes and layout: every shape slide_fits() also
+// fused_fits(), and fused / tiled ignore dtypes and layout, so whether the choice is Generic depends on neither --
+// except with the slide path pinned, where the layout decides (NHWC needs C == 3).
+static SwtPath choose(const SwtShape &s)
 {
-    // WV_SWT_PATH = fused | tiled | generic pins one implementation (tests / tuning); default: best available
-    const char *path = ::wv::tune("WV_SWT_PATH");
-    const bool want_slide = !path || !strcmp(path, "slide");
-    const bool want_fused = !path || !strcmp(path, "fused");
-    const bool want_tiled = !path || !strcmp(path, "tiled");
-    if (want_slide && swt_slide_covers(L, n, W, H)) {
-        const int rc = swt_slide_launch(in, sizeof(InT) == 1 ? WV_DT_U8 : WV_DT_F32, in_layout, out,
-                                        sizeof(OutT) == 2 ? WV_DT_BF16 : WV_DT_F32, B, C, H, W, n, lo, hi, L, st);
-        if (rc <= 0) return rc;
-    }
-    if (want_fused && swt_fused_covers(L, n, W)) {
-        const int rc = swt_fused_launch(in, sizeof(InT) == 1 ? WV_DT_U8 : WV_DT_F32, in_layout, out,
-                                        sizeof(OutT) == 2 ? WV_DT_BF16 : WV_DT_F32, B, C, H, W, n, lo, hi, L, st);
-        if (rc <= 0) return rc;
-    }
-    TilePlan p = plan_tiles(B, C, H, W, L, n, in_layout);
-    if (want_tiled && p.ok) return dispatch_taps<InT, OutT>(L, n, in, out, p, lo, hi, st);
-    return run_generic<InT, OutT>(in, out, B, C, H, W, n, lo, hi, L, in_layout, ws, ws_bytes, st);
+    const char *pin = ::wv::tune("WV_SWT_PATH");
+    auto allowed = [pin](const char *path) { return !pin || !strcmp(pin, path); };
+    if (allowed("slide") && slide_fits(s)) return SwtPath::Slide;
+    if (allowed("fused") && fused_fits(s)) return SwtPath::Fused;
+    if (allowed("tiled") && plan_tiles(s).ok) return SwtPath::Tiled;
+    return SwtPath::Generic;
+}
+
+template <typename InT, typename OutT>
+static int swt_typed(SwtPath path, const SwtShape &s, const void *in, void *out, const float *lo, const float *hi,
+                     void *ws, size_t ws_bytes, hipStream_t st)
+{
+    if (path == SwtPath::Tiled) return dispatch_taps<InT, OutT>(s.L, s.level, in, out, plan_tiles(s), lo, hi, st);
+    return run_generic<InT, OutT>(in, out, s.B, s.C, s.H, s.W, s.level, lo, hi, s.L, s.in_layout, ws, ws_bytes, st);
+}
+
+// The argument checks both entry points share.
+static int validate_swt_args(const void *in, int in_dtype, int in_layout, const void *out, int out_dtype, int B, int C,
+                             int H, int W, int level, const float *dec_lo, const float *dec_hi, int flen)
+{
+    WV_REQUIRE(in && out, "swt: null buffer");
+    WV_REQUIRE(dec_lo && dec_hi && flen >= 1, "swt: missing filter taps");
+    WV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "swt: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+    WV_REQUIRE(level >= 1 && level <= 12, "swt: level %d out of range", level);
+    WV_REQUIRE((H % (1 << level)) == 0 && (W % (1 << level)) == 0,
+               "swt: H=%d, W=%d must be multiples of 2^level=%d (PyWavelets raises ValueError here)",
+               H, W, 1 << level);
+    WV_REQUIRE(in_layout == WV_LAYOUT_NCHW || in_layout == WV_LAYOUT_NHWC, "swt: bad layout %d", in_layout);
+    WV_REQUIRE(B <= 65535 && C <= 65535, "swt: B and C must be <= 65535 per call");
+    if (!((in_dtype == WV_DT_U8 || in_dtype == WV_DT_F32) && (out_dtype == WV_DT_F32 || out_dtype == WV_DT_BF16)))
+        WV_FAIL(WV_ENOTSUP, "swt: dtype pair in=%d out=%d not supported (in: u8 or f32, out: f32 or bf16)", in_dtype,
+                out_dtype);
+    return WV_OK;
 }
 
 }  // namespace wv
@@ -561,13 +565,11 @@ using namespace wv;
 extern "C" size_t wv_swt2d_workspace_bytes(int B, int C, int H, int W, int level, int flen)
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-    const char *path = ::wv::tune("WV_SWT_PATH");
-    if (!path || strcmp(path, "generic")) {
-        if (swt_slide_covers(flen, level, W, H) && (!path || !strcmp(path, "slide"))) return 0;
-        if (swt_fused_covers(flen, level, W) && (!path || !strcmp(path, "fused"))) return 0;
-        TilePlan p = plan_tiles(B, C, H, W, flen, level, WV_LAYOUT_NCHW);
-        if (p.ok && (!path || !strcmp(path, "tiled"))) return 0;
-    }
+    // dtypes do not matter (see choose()); the layout only with the slide path pinned: a workspace unless both fit
+    SwtShape s{B, C, H, W, level, flen, WV_DT_U8, WV_DT_F32, WV_LAYOUT_NCHW};
+    SwtShape nhwc = s;
+    nhwc.in_layout = WV_LAYOUT_NHWC;
+    if (choose(s) != SwtPath::Generic && choose(nhwc) != SwtPath::Generic) return 0;
     return (size_t)3 * B * C * H * W * sizeof(float);
 }
 
@@ -576,30 +578,18 @@ extern "C" int wv_swt2d_forward(const void *in, int in_dtype, int in_layout, voi
                                 const float *dec_hi, int flen, void *workspace,
                                 size_t workspace_bytes, void *stream)
 {
-    WV_REQUIRE(in && out, "swt: null buffer");
-    WV_REQUIRE(dec_lo && dec_hi && flen >= 1, "swt: missing filter taps");
-    WV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "swt: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
-    WV_REQUIRE(level >= 1 && level <= 12, "swt: level %d out of range", level);
-    WV_REQUIRE((H % (1 << level)) == 0 && (W % (1 << level)) == 0,
-               "swt: H=%d, W=%d must be multiples of 2^level=%d (PyWavelets raises ValueError here)",
-               H, W, 1 << level);
-    WV_REQUIRE(in_layout == WV_LAYOUT_NCHW || in_layout == WV_LAYOUT_NHWC, "swt: bad layout %d",
-               in_layout);
-    WV_REQUIRE(B <= 65535 && C <= 65535, "swt: B and C must be <= 65535 per call");
+    const int rc = validate_swt_args(in, in_dtype, in_layout, out, out_dtype, B, C, H, W, level, dec_lo, dec_hi, flen);
+    if (rc != WV_OK) return rc;
+    const SwtShape s{B, C, H, W, level, flen, in_dtype, out_dtype, in_layout};
     hipStream_t st = (hipStream_t)stream;
-    if (in_dtype == WV_DT_U8 && out_dtype == WV_DT_F32)
-        return swt_typed<uint8_t, float>(in, out, B, C, H, W, level, dec_lo, dec_hi, flen, in_layout,
-                                         workspace, workspace_bytes, st);
-    if (in_dtype == WV_DT_F32 && out_dtype == WV_DT_F32)
-        return swt_typed<float, float>(in, out, B, C, H, W, level, dec_lo, dec_hi, flen, in_layout,
-                                       workspace, workspace_bytes, st);
-    if (in_dtype == WV_DT_U8 && out_dtype == WV_DT_BF16)
-        return swt_typed<uint8_t, __hip_bfloat16>(in, out, B, C, H, W, level, dec_lo, dec_hi, flen,
-                                                  in_layout, workspace, workspace_bytes, st);
-    if (in_dtype == WV_DT_F32 && out_dtype == WV_DT_BF16)
-        return swt_typed<float, __hip_bfloat16>(in, out, B, C, H, W, level, dec_lo, dec_hi, flen,
-                                                in_layout, workspace, workspace_bytes, st);
-    WV_FAIL(WV_ENOTSUP, "swt: dtype pair in=%d out=%d not supported", in_dtype, out_dtype);
+    const SwtPath path = choose(s);
+    if (path == SwtPath::Slide) return swt_slide_launch(s, in, out, dec_lo, dec_hi, st);
+    if (path == SwtPath::Fused) return swt_fused_launch(s, in, out, dec_lo, dec_hi, st);
+    const bool u8 = in_dtype == WV_DT_U8, bf16 = out_dtype == WV_DT_BF16;
+    if (u8 && !bf16) return swt_typed<uint8_t, float>(path, s, in, out, dec_lo, dec_hi, workspace, workspace_bytes, st);
+    if (!u8 && !bf16) return swt_typed<float, float>(path, s, in, out, dec_lo, dec_hi, workspace, workspace_bytes, st);
+    if (u8) return swt_typed<uint8_t, __hip_bfloat16>(path, s, in, out, dec_lo, dec_hi, workspace, workspace_bytes, st);
+    return swt_typed<float, __hip_bfloat16>(path, s, in, out, dec_lo, dec_hi, workspace, workspace_bytes, st);
 }
 
 extern "C" int wv_swt2d_forward_ex(const void *in, int in_dtype, int in_layout, void *out, int out_dtype,
@@ -611,27 +601,16 @@ extern "C" int wv_swt2d_forward_ex(const void *in, int in_dtype, int in_layout, 
         return wv_swt2d_forward(in, in_dtype, in_layout, out, out_dtype, B, C, H, W, level, dec_lo, dec_hi, flen,
                                 workspace, workspace_bytes, stream);
     WV_REQUIRE(out_layout == WV_BANDS_OUTER, "swt: bad output layout %d", out_layout);
-    WV_REQUIRE(in && out, "swt: null buffer");
-    WV_REQUIRE(dec_lo && dec_hi && flen >= 1, "swt: missing filter taps");
-    WV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "swt: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
-    WV_REQUIRE(level >= 1 && level <= 12, "swt: level %d out of range", level);
-    WV_REQUIRE((H % (1 << level)) == 0 && (W % (1 << level)) == 0,
-               "swt: H=%d, W=%d must be multiples of 2^level=%d (PyWavelets raises ValueError here)",
-               H, W, 1 << level);
-    WV_REQUIRE(in_layout == WV_LAYOUT_NCHW || in_layout == WV_LAYOUT_NHWC, "swt: bad layout %d", in_layout);
-    WV_REQUIRE(B <= 65535 && C <= 65535, "swt: B and C must be <= 65535 per call");
+    const int rc = validate_swt_args(in, in_dtype, in_layout, out, out_dtype, B, C, H, W, level, dec_lo, dec_hi, flen);
+    if (rc != WV_OK) return rc;
     WV_REQUIRE(band_stride >= (int64_t)B * C * H * W, "swt: band_stride %lld < B*C*H*W", (long long)band_stride);
-    WV_REQUIRE((in_dtype == WV_DT_U8 || in_dtype == WV_DT_F32) && (out_dtype == WV_DT_F32 || out_dtype == WV_DT_BF16),
-               "swt: dtype pair in=%d out=%d not supported", in_dtype, out_dtype);
     // band-major output exists in the sliding kernel only (the shapes of the hot path); the caller re-lays the
     // reference layout out for anything else
-    if (!swt_slide_covers(flen, level, W, H))
-        WV_FAIL(WV_ENOTSUP, "swt: band-major output is implemented by the sliding kernel only (W %% 4 == 0, 40 <= W <= 256, "
-                            "H >= 40, 2/4 taps at levels 1-3 or 8/10 taps at level 1)");
-    const int rc = swt_slide_launch(in, in_dtype, in_layout, out, out_dtype, B, C, H, W, level, dec_lo, dec_hi, flen,
-                                    (hipStream_t)stream, WV_BANDS_OUTER, band_stride);
-    if (rc > 0) WV_FAIL(WV_ENOTSUP, "swt: shape outside the sliding kernel's window");
-    return rc;
+    const SwtShape s{B, C, H, W, level, flen, in_dtype, out_dtype, in_layout};
+    char why[160];
+    if (!slide_fits(s, why, sizeof why))
+        WV_FAIL(WV_ENOTSUP, "swt: band-major output is implemented by the sliding kernel only, which does not take %s", why);
+    return swt_slide_launch(s, in, out, dec_lo, dec_hi, (hipStream_t)stream, WV_BANDS_OUTER, band_stride);
 }
 
 extern "C" int wv_rawstack_forward(const void *in, int in_dtype, int in_layout, void *out,

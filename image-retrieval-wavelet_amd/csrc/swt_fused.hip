@@ -15,18 +15,11 @@
 // (49 KB for db2 level 3 -> 3 workgroups per CU), no intermediate level ever leaves registers.
 // Per 1-D pass the taps are accumulated in the reference order (m = 0..L-1, fmaf); only the order
 // of the (commuting) passes differs from pywt's axis-0-then-axis-1 per level, i.e. fp32 rounding.
-#include "common.hpp"
-#include "swt_fused.hpp"
+#include "swt.hpp"
 
 namespace wv {
 
 constexpr int kFusedThreads = 256;
-
-template <int L>
-struct FTaps {
-    float lo[L];
-    float hi[L];
-};
 
 struct FusedGeom {
     int B, C, H, W;
@@ -35,81 +28,17 @@ struct FusedGeom {
     int out_bf16;
 };
 
-template <int L, int NLEV, int NOUT>
-struct Chain {
-    static constexpr int HALO = (L - 1) * ((1 << NLEV) - 1);
-    static constexpr int NIN = NOUT + HALO;
-
-    // levels 1 .. NLEV-1 (approximation only), in place: a_l[i] = sum_m lo[m] * a_{l-1}[i + s(L-1-m)]
-    template <int LEV>
-    static __device__ __forceinline__ void lower(float (&v)[NIN], const float (&lo)[L])
-    {
-        if constexpr (LEV < NLEV) {
-            constexpr int S = 1 << (LEV - 1);
-            constexpr int LEN = NIN - (L - 1) * ((1 << LEV) - 1);
-#pragma unroll
-            for (int i = 0; i < LEN; ++i) {
-                float a = lo[0] * v[i + S * (L - 1)];
-#pragma unroll
-                for (int m = 1; m < L; ++m) a = fmaf(lo[m], v[i + S * (L - 1 - m)], a);
-                v[i] = a;
-            }
-            lower<LEV + 1>(v, lo);
-        }
-    }
-    // level NLEV output i with filter f
-    static __device__ __forceinline__ float last(const float (&v)[NIN], const float (&f)[L], int i)
-    {
-        constexpr int S = 1 << (NLEV - 1);
-        float a = f[0] * v[i + S * (L - 1)];
-#pragma unroll
-        for (int m = 1; m < L; ++m) a = fmaf(f[m], v[i + S * (L - 1 - m)], a);
-        return a;
-    }
-};
-
-__device__ __forceinline__ int wrapi(int v, int n)
-{
-    while (v < 0) v += n;
-    while (v >= n) v -= n;
-    return v;
-}
-
-// exact fp32 x / 255 for x in 0..255 (verified exhaustively against IEEE division):
-// q = x * r ; e = fma(-q, 255, x) ; q' = fma(e, r, q), r = RN(1/255)
-__device__ __forceinline__ float u8_to_unit(float x)
-{
-    const float r = 0.003921568859368563f;  // 0x3b808081
-    const float q = x * r;
-    const float e = fmaf(-q, 255.0f, x);
-    return fmaf(e, r, q);
-}
-
-template <int N>
-__device__ __forceinline__ float ubyte_f32(uint32_t d)
-{
-    return (float)((d >> (8 * N)) & 0xffu);  // -> v_cvt_f32_ubyteN
-}
-
 // 4 consecutive pixels (x multiple of 4) of channel c at row gy, as fp32 in [0,1]
 template <typename InT>
 __device__ __forceinline__ float4 load_px4(const InT *__restrict__ in, const FusedGeom &g, int b, int c,
                                            int gy, int gx)
 {
     if constexpr (sizeof(InT) == 1) {
-        if (g.in_layout == WV_LAYOUT_NCHW) {
-            const uint32_t d = *reinterpret_cast<const uint32_t *>(in + (((size_t)b * g.C + c) * g.H + gy) * g.W + gx);
-            return make_float4(u8_to_unit(ubyte_f32<0>(d)), u8_to_unit(ubyte_f32<1>(d)),
-                               u8_to_unit(ubyte_f32<2>(d)), u8_to_unit(ubyte_f32<3>(d)));
-        }
-        if (g.C == 3) {  // 4 RGB pixels = 12 bytes = 3 aligned dwords; channel c sits at bytes c, 3+c, 6+c, 9+c
+        if (g.in_layout == WV_LAYOUT_NCHW)
+            return u8x4_to_unit(*reinterpret_cast<const uint32_t *>(in + (((size_t)b * g.C + c) * g.H + gy) * g.W + gx));
+        if (g.C == 3) {  // 4 RGB pixels = 3 aligned dwords
             const uint32_t *p = reinterpret_cast<const uint32_t *>(in + (((size_t)b * g.H + gy) * g.W + gx) * 3);
-            const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
-            const uint32_t s0 = __builtin_amdgcn_alignbyte(d1, d0, (uint32_t)c);
-            const uint32_t s1 = __builtin_amdgcn_alignbyte(d2, d1, (uint32_t)c);
-            const uint32_t s2 = __builtin_amdgcn_alignbyte(0u, d2, (uint32_t)c);
-            return make_float4(u8_to_unit(ubyte_f32<0>(s0)), u8_to_unit(ubyte_f32<3>(s0)),
-                               u8_to_unit(ubyte_f32<2>(s1)), u8_to_unit(ubyte_f32<1>(s2)));
+            return rgb4_to_unit(p[0], p[1], p[2], c);
         }
         const InT *p = in + (((size_t)b * g.H + gy) * g.W + gx) * g.C + c;
         return make_float4(u8_to_unit((float)p[0]), u8_to_unit((float)p[g.C]), u8_to_unit((float)p[2 * g.C]),
@@ -130,10 +59,10 @@ __device__ __forceinline__ void store_out(void *out, size_t off, float v, int bf
 
 template <int L, int NLEV, int R, int NRUN, int TH, typename InT>
 __global__ __launch_bounds__(kFusedThreads) void k_swt_fused(const InT *__restrict__ in, void *__restrict__ out,
-                                                             FusedGeom g, FTaps<L> taps)
+                                                             FusedGeom g, Taps<L> taps)
 {
-    using CH = Chain<L, NLEV, R>;
-    using CV = Chain<L, NLEV, TH>;
+    using CH = Cascade<L, NLEV, R>;
+    using CV = Cascade<L, NLEV, TH>;
     constexpr int HALO = CH::HALO;
     constexpr int HB = (L / 2 - 1) * ((1 << NLEV) - 1);   // halo before; after = HALO - HB
     constexpr int HBa = (HB + 3) / 4 * 4;
@@ -153,12 +82,12 @@ __global__ __launch_bounds__(kFusedThreads) void k_swt_fused(const InT *__restri
     // ------------------------------------------------------------------ pass H
     for (int u = threadIdx.x; u < RH * NRUN; u += kFusedThreads) {
         const int r = u / NRUN, j = u - r * NRUN;
-        const int gy = wrapi(y0 - HB + r, g.H);
+        const int gy = wrap(y0 - HB + r, g.H);
         const int gx0 = x0 + j * R - HBa;
         float raw[NG * 4];
 #pragma unroll
         for (int k = 0; k < NG; ++k) {
-            const float4 p4 = load_px4<InT>(in, g, b, c, gy, wrapi(gx0 + 4 * k, g.W));
+            const float4 p4 = load_px4<InT>(in, g, b, c, gy, wrap(gx0 + 4 * k, g.W));
             raw[4 * k + 0] = p4.x; raw[4 * k + 1] = p4.y; raw[4 * k + 2] = p4.z; raw[4 * k + 3] = p4.w;
         }
         float v[CH::NIN];
@@ -205,7 +134,7 @@ __global__ __launch_bounds__(kFusedThreads) void k_swt_fused(const InT *__restri
 template <int L, int NLEV, int R, int NRUN, int TH, typename InT>
 static int launch_fused(const void *in, void *out, FusedGeom g, const float *lo, const float *hi, hipStream_t st)
 {
-    FTaps<L> taps;
+    Taps<L> taps;
     for (int i = 0; i < L; ++i) { taps.lo[i] = lo[i]; taps.hi[i] = hi[i]; }
     constexpr int TW = R * NRUN;
     g.tilesX = (int)ceil_div(g.W, TW);
@@ -227,6 +156,13 @@ static int pick_shape(const void *in, void *out, const FusedGeom &g, const float
     return launch_fused<L, NLEV, 16, 4, 32, InT>(in, out, g, lo, hi, st);
 }
 
+// the (taps, levels) instantiated below; any width W % 4 == 0, any height, dtype and layout
+bool fused_fits(const SwtShape &s)
+{
+    const int L = s.L, n = s.level;
+    return (((L == 2 || L == 4) && n >= 1 && n <= 3) || ((L == 8 || L == 10) && n == 1)) && s.W % 4 == 0;
+}
+
 template <typename InT>
 static int pick_filter(int L, int n, const void *in, void *out, const FusedGeom &g, const float *lo,
                        const float *hi, hipStream_t st)
@@ -238,22 +174,15 @@ static int pick_filter(int L, int n, const void *in, void *out, const FusedGeom 
     WV_CASE(8, 1);
     WV_CASE(10, 1);
 #undef WV_CASE
-    return 1;  // not covered
+    WV_FAIL(WV_ENOTSUP, "swt fused: %d taps at level %d", L, n);   // unreachable after fused_fits()
 }
 
-bool swt_fused_covers(int L, int n, int W)
-{
-    const bool cfg = (L == 2 && n <= 3) || (L == 4 && n <= 3) || (L == 8 && n == 1) || (L == 10 && n == 1);
-    return cfg && n >= 1 && (W % 4) == 0;
-}
-
-int swt_fused_launch(const void *in, int in_dtype, int in_layout, void *out, int out_dtype, int B, int C, int H,
-                     int W, int n, const float *lo, const float *hi, int L, hipStream_t st)
+int swt_fused_launch(const SwtShape &s, const void *in, void *out, const float *lo, const float *hi, hipStream_t st)
 {
     FusedGeom g{};
-    g.B = B; g.C = C; g.H = H; g.W = W; g.in_layout = in_layout; g.out_bf16 = out_dtype == WV_DT_BF16;
-    if (in_dtype == WV_DT_U8) return pick_filter<uint8_t>(L, n, in, out, g, lo, hi, st);
-    return pick_filter<float>(L, n, in, out, g, lo, hi, st);
+    g.B = s.B; g.C = s.C; g.H = s.H; g.W = s.W; g.in_layout = s.in_layout; g.out_bf16 = s.out_dtype == WV_DT_BF16;
+    if (s.in_dtype == WV_DT_U8) return pick_filter<uint8_t>(s.L, s.level, in, out, g, lo, hi, st);
+    return pick_filter<float>(s.L, s.level, in, out, g, lo, hi, st);
 }
 
 }  // namespace wv

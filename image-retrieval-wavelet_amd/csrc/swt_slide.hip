@@ -13,40 +13,20 @@
 //   pass V : thread = (plane, column); lanes = adjacent columns -> each store instruction writes one
 //            contiguous row segment, consecutive rows follow each other in memory
 // uint8 input is converted exactly (x/255 via fma refinement, verified for all 256 values).
-#include "common.hpp"
-#include "swt_fused.hpp"
+#include "swt.hpp"
 #include <type_traits>
 #include <vector>
 
-// Folding the u8 -> [0,1] division into the last row-filter taps saves 3 VALU ops per pixel but measured
-// SLOWER on MI355X (1.265 ms vs 1.180 ms, A/B in one session, db2 level 3): off.
-#ifndef WV_SWT_FOLD255
-#define WV_SWT_FOLD255 0
-#endif
-
-// A/B on MI355X in one session (tools/build_variant.sh), db2 level 3, 2048 images:
-//   consumer (column) waves at raised issue priority: 1.148 ms vs 1.19 ms at equal priority (they are the critical role)
-//   interior chunks storing without per-row bounds checks (a second copy of the store loop): 1.18 ms, slower -> off
-#ifndef WV_SWT_VPRIO
-#define WV_SWT_VPRIO 2
-#endif
-#ifndef WV_SWT_FASTMID
-#define WV_SWT_FASTMID 0
-#endif
-// Column pass on (row-lo, row-hi) PAIRS: the two row-filtered planes go through identical arithmetic, so the
-// consumer keeps them as 2-vectors and every multiply-add becomes one v_pk_fma_f32 -- half the instructions a
-// wave has to issue for the same (bitwise identical) result.  The LDS ring then holds the planes interleaved.
-#ifndef WV_SWT_PAIRED
-#define WV_SWT_PAIRED 1
-#endif
-
 namespace wv {
 
-template <int L>
-struct STaps {
-    float lo[L];
-    float hi[L];
-};
+// The one configuration every (taps, levels) instantiation uses: runs of R columns, TH rows per step, NT threads per
+// role (W <= NT), MINW workgroups per CU.
+constexpr int kSlideR = 16, kSlideTH = 16, kSlideNT = 256, kSlideMinW = 4;
+constexpr int kPitchPad = 4;      // LDS ring pitch = nrun * R + 4 floats
+// A/B on MI355X in one session, db2 level 3, 2048 images: consumer (column) waves at raised issue priority: 1.148 ms vs
+// 1.19 ms at equal priority (they are the critical role)
+constexpr int kConsumerPrio = 2;
+constexpr int kXcds = 8;          // workgroup w runs on XCD w % 8 (hardware round-robin)
 
 struct SlideGeom {
     int B, C, H, W;
@@ -63,50 +43,23 @@ struct SlideGeom {
     unsigned long long *stamps;   // diagnostic build only
 };
 
-template <int L, int NLEV, int NOUT>
-struct SChain {
-    static constexpr int HALO = (L - 1) * ((1 << NLEV) - 1);
-    static constexpr int NIN = NOUT + HALO;
-    template <int LEV>
-    static __device__ __forceinline__ void lower(float (&v)[NIN], const float (&lo)[L])
-    {
-        if constexpr (LEV < NLEV) {
-            constexpr int S = 1 << (LEV - 1);
-            constexpr int LEN = NIN - (L - 1) * ((1 << LEV) - 1);
-#pragma unroll
-            for (int i = 0; i < LEN; ++i) {
-                float a = lo[0] * v[i + S * (L - 1)];
-#pragma unroll
-                for (int m = 1; m < L; ++m) a = fmaf(lo[m], v[i + S * (L - 1 - m)], a);
-                v[i] = a;
-            }
-            lower<LEV + 1>(v, lo);
-        }
-    }
-    static __device__ __forceinline__ float last(const float (&v)[NIN], const float (&f)[L], int i)
-    {
-        constexpr int S = 1 << (NLEV - 1);
-        float a = f[0] * v[i + S * (L - 1)];
-#pragma unroll
-        for (int m = 1; m < L; ++m) a = fmaf(f[m], v[i + S * (L - 1 - m)], a);
-        return a;
-    }
-};
-
-// Streaming form of the same cascade for pass V: a thread keeps, per column, the last (L-1)*2^(l-1)
+// Streaming form of the cascade for pass V: a thread keeps, per column, the last (L-1)*2^(l-1)
 // inputs of every level l in registers ("tails", HALO values in all), so each step costs exactly
 // L MACs per level per new row -- no halo recompute -- and emits outputs delayed by HALO rows.
-// The arithmetic per output is identical to SChain (same taps, same order).
+// The arithmetic per output is identical to Cascade (same taps, same order).
+// It runs on (row-lo, row-hi) PAIRS: the two row-filtered planes go through identical arithmetic, so the
+// consumer keeps them as 2-vectors and every multiply-add becomes one v_pk_fma_f32 -- half the instructions a
+// wave has to issue for the same (bitwise identical) result.  The LDS ring holds the planes interleaved.
 using f32x2 = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ float fma_s(float s, float x, float a) { return fmaf(s, x, a); }
 __device__ __forceinline__ f32x2 fma_s(float s, f32x2 x, f32x2 a)
 {
     const f32x2 sv = {s, s};
     return __builtin_elementwise_fma(sv, x, a);
 }
 
-template <int L, int NLEV, int N, typename T = float>
+template <int L, int NLEV, int N>
 struct VStep {
+    using T = f32x2;
     static constexpr int HALO = (L - 1) * ((1 << NLEV) - 1);
     // levels LEV .. NLEV-1: cur[] holds N new level-LEV inputs on entry, N new level-NLEV inputs on exit
     template <int LEV>
@@ -169,27 +122,6 @@ struct VStep {
     }
 };
 
-// branch-free wrap, valid for -n <= v < 2n (guaranteed by swt_slide_covers)
-__device__ __forceinline__ int swrap1(int v, int n)
-{
-    v = v < 0 ? v + n : v;
-    return v >= n ? v - n : v;
-}
-
-__device__ __forceinline__ float s_u8_to_unit(float x)
-{
-    const float r = 0.003921568859368563f;  // RN(1/255) = 0x3b808081
-    const float q = x * r;
-    const float e = fmaf(-q, 255.0f, x);
-    return fmaf(e, r, q);                   // == RN(x / 255) for every x in 0..255
-}
-
-template <int N>
-__device__ __forceinline__ float s_ubyte(uint32_t d)
-{
-    return (float)((d >> (8 * N)) & 0xffu);
-}
-
 // LAYOUT: 0 = NCHW, 1 = NHWC with C == 3.  One aligned 4-pixel group of channel c, raw.
 template <typename InT, int LAYOUT>
 struct SRaw {
@@ -222,33 +154,12 @@ __device__ __forceinline__ SRaw<InT, LAYOUT> s_fetch4(const InT *__restrict__ im
     return r;
 }
 
-// FOLD = true: leave the pixels as integers 0..255 (one v_cvt each); the 1/255 is folded into the taps of the
-// last row-filter level by the caller (the transform is linear).
-template <typename InT, int LAYOUT, bool FOLD = false>
+template <typename InT, int LAYOUT>
 __device__ __forceinline__ float4 s_convert4(const SRaw<InT, LAYOUT> &r, int c)
 {
-    if constexpr (sizeof(InT) == 1 && FOLD) {
-        if constexpr (LAYOUT == 1) {
-            const uint32_t s0 = __builtin_amdgcn_alignbyte(r.d[1], r.d[0], (uint32_t)c);
-            const uint32_t s1 = __builtin_amdgcn_alignbyte(r.d[2], r.d[1], (uint32_t)c);
-            const uint32_t s2 = __builtin_amdgcn_alignbyte(0u, r.d[2], (uint32_t)c);
-            return make_float4(s_ubyte<0>(s0), s_ubyte<3>(s0), s_ubyte<2>(s1), s_ubyte<1>(s2));
-        } else {
-            const uint32_t d = r.d[0];
-            return make_float4(s_ubyte<0>(d), s_ubyte<1>(d), s_ubyte<2>(d), s_ubyte<3>(d));
-        }
-    } else if constexpr (sizeof(InT) == 1) {
-        if constexpr (LAYOUT == 1) {  // channel c at bytes c, 3+c, 6+c, 9+c of the 12
-            const uint32_t s0 = __builtin_amdgcn_alignbyte(r.d[1], r.d[0], (uint32_t)c);
-            const uint32_t s1 = __builtin_amdgcn_alignbyte(r.d[2], r.d[1], (uint32_t)c);
-            const uint32_t s2 = __builtin_amdgcn_alignbyte(0u, r.d[2], (uint32_t)c);
-            return make_float4(s_u8_to_unit(s_ubyte<0>(s0)), s_u8_to_unit(s_ubyte<3>(s0)),
-                               s_u8_to_unit(s_ubyte<2>(s1)), s_u8_to_unit(s_ubyte<1>(s2)));
-        } else {
-            const uint32_t d = r.d[0];
-            return make_float4(s_u8_to_unit(s_ubyte<0>(d)), s_u8_to_unit(s_ubyte<1>(d)),
-                               s_u8_to_unit(s_ubyte<2>(d)), s_u8_to_unit(s_ubyte<3>(d)));
-        }
+    if constexpr (sizeof(InT) == 1) {
+        if constexpr (LAYOUT == 1) return rgb4_to_unit(r.d[0], r.d[1], r.d[2], c);
+        else return u8x4_to_unit(r.d[0]);
     } else {
         return make_float4(__uint_as_float(r.d[0]), __uint_as_float(r.d[1]), __uint_as_float(r.d[2]),
                            __uint_as_float(r.d[3]));
@@ -287,10 +198,10 @@ __device__ __forceinline__ void store_row(__hip_bfloat16 *row_uniform, uint32_t 
 
 template <int L, int NLEV, int R, int TH, int NH, int MINW, typename InT, int LAYOUT, bool BF16, bool STAMP = false>
 __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restrict__ in, void *__restrict__ out,
-                                                            SlideGeom g, STaps<L> taps)
+                                                            SlideGeom g, Taps<L> taps)
 {
     uint64_t st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0, acc_a = 0, acc_b = 0, acc_c = 0, acc_d = 0, acc_e = 0;
-    using CH = SChain<L, NLEV, R>;
+    using CH = Cascade<L, NLEV, R>;
     using Raw = SRaw<InT, LAYOUT>;
     using OutT = typename std::conditional<BF16, __hip_bfloat16, float>::type;
     constexpr int HALO = CH::HALO;
@@ -301,7 +212,7 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
     extern __shared__ float4 ring4[];
     float *ring = reinterpret_cast<float *>(ring4);       // [2 buffers][2 planes][TH][P]
     const int P = g.P, W = g.W, H = g.H;
-    const int plane_sz = TH * P, buf_sz = 2 * plane_sz;
+    const int buf_sz = 2 * TH * P;
     const int nchunks = (H + HALO + TH - 1) / TH;         // the cascade consumes H + HALO rows per plane
     const uint32_t band = (uint32_t)H * W;
     // Plane schedule.  Workgroup w runs on XCD w % 8 (round-robin dispatch) and every XCD has its own L2, so
@@ -312,15 +223,13 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
     const int nq = g.B > xcd ? (g.B - xcd + g.nxcd - 1) / g.nxcd * g.C : 0;   // planes this XCD owns
     const bool is_h = threadIdx.x >= NH;                  // wave-uniform role
     const int t = is_h ? threadIdx.x - NH : threadIdx.x;
-
-    constexpr bool FOLD = sizeof(InT) == 1 && WV_SWT_FOLD255;
-    constexpr bool PAIRED = WV_SWT_PAIRED != 0;
-    float hlo[L], hhi[L];   // taps of the last row-filter level (scaled by 1/255 when the division is folded)
+    // Two statements below change no result: the row pass takes its last-level taps from the copies hlo / hhi, and
+    // the column role evaluates (and drops) the slot index of the retired planar LDS layout.  Both keep the compiler's
+    // instruction order, and with it the machine code of the kernel as measured; dropping either
+    // re-schedules it.
+    float hlo[L], hhi[L];
 #pragma unroll
-    for (int m = 0; m < L; ++m) {
-        hlo[m] = FOLD ? taps.lo[m] * 0.003921568859368563f : taps.lo[m];
-        hhi[m] = FOLD ? taps.hi[m] * 0.003921568859368563f : taps.hi[m];
-    }
+    for (int m = 0; m < L; ++m) { hlo[m] = taps.lo[m]; hhi[m] = taps.hi[m]; }
     if (is_h) {
         // ------------------------------------------------------------------ producer: pass H
         // (row, run) of this producer thread.  Coalesced mode (planar uint8, W % 16 == 0) keeps the runs of one row
@@ -348,11 +257,11 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
                 // input row of virtual row v = chunk*TH + rr is y = v - HB (wrapped; rows past H + HA wrap too)
                 int y = chunk * TH + rr - HB;
                 y = y >= H ? y - H : y;
-                const uint32_t row = (uint32_t)swrap1(y, H) * (uint32_t)W;
+                const uint32_t row = (uint32_t)wrap_once(y, H) * (uint32_t)W;
                 const int gx0 = j * R - HBa;
 #pragma unroll
                 for (int k = 0; k < NG; ++k)
-                    raw[k] = s_fetch4<InT, LAYOUT>(img, row + (uint32_t)swrap1(gx0 + 4 * k, W), c);
+                    raw[k] = s_fetch4<InT, LAYOUT>(img, row + (uint32_t)wrap_once(gx0 + 4 * k, W), c);
             };
             constexpr bool CAN_COAL = sizeof(InT) == 1 && LAYOUT == 0 && R == 16 && NG * 4 - HBa <= 32;
             uint32_t own[4] = {0, 0, 0, 0};
@@ -360,7 +269,7 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
                 int y = chunk * TH + rr_ld - HB;
                 y = y >= H ? y - H : y;
                 const uint4 v4 = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(img) +
-                                                                  (size_t)swrap1(y, H) * W + j * R);
+                                                                  (size_t)wrap_once(y, H) * W + j * R);
                 own[0] = v4.x; own[1] = v4.y; own[2] = v4.z; own[3] = v4.w;
             };
             const bool coal = CAN_COAL && g.coal;   // uniform
@@ -388,7 +297,7 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
                     float v[NG * 4];
 #pragma unroll
                     for (int q = 0; q < NG; ++q) {
-                        const float4 p4 = s_convert4<InT, LAYOUT, FOLD>(raw[q], c);
+                        const float4 p4 = s_convert4<InT, LAYOUT>(raw[q], c);
                         v[4 * q + 0] = p4.x; v[4 * q + 1] = p4.y; v[4 * q + 2] = p4.z; v[4 * q + 3] = p4.w;
                     }
                     WV_STAMP(st1);
@@ -401,34 +310,17 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
                     for (int i = 0; i < CH::NIN; ++i) w[i] = v[i + off];
                     CH::template lower<1>(w, taps.lo);
                     WV_STAMP(st5);
-                    // LDS row layout is permuted so that consecutive lanes (= consecutive runs j) write
-                    // consecutive 16-byte slots: column x = j*R + 4*q4 + e lives at q4*(4*nrun) + 4*j + e
-                    if constexpr (PAIRED) {
-                        // interleaved planes: column x = j*R + 2*q2 + e holds (lo, hi) at floats
-                        // q2*(4*nrun) + 4*j + 2*e of its row -> lanes (= runs j) write consecutive 16-byte slots
-                        float *prow = ring + (k & 1) * buf_sz + rr * (2 * P) + 4 * j;
-                        const int qstride = 4 * g.nrun;
-#pragma unroll
-                        for (int q2 = 0; q2 < R / 2; ++q2) {
-                            float4 v4;
-                            v4.x = CH::last(w, hlo, 2 * q2 + 0); v4.y = CH::last(w, hhi, 2 * q2 + 0);
-                            v4.z = CH::last(w, hlo, 2 * q2 + 1); v4.w = CH::last(w, hhi, 2 * q2 + 1);
-                            *reinterpret_cast<float4 *>(prow + q2 * qstride) = v4;
-                        }
-                    } else {
-                    float *plo = ring + (k & 1) * buf_sz + rr * P + 4 * j;
-                    float *phi = plo + plane_sz;
+                    // LDS row layout is permuted and the planes interleaved so that consecutive lanes (= consecutive
+                    // runs j) write consecutive 16-byte slots: column x = j*R + 2*q2 + e holds (lo, hi) at floats
+                    // q2*(4*nrun) + 4*j + 2*e of its row
+                    float *prow = ring + (k & 1) * buf_sz + rr * (2 * P) + 4 * j;
                     const int qstride = 4 * g.nrun;
 #pragma unroll
-                    for (int q4 = 0; q4 < R / 4; ++q4) {
-                        float4 lo4, hi4;
-                        lo4.x = CH::last(w, hlo, 4 * q4 + 0); hi4.x = CH::last(w, hhi, 4 * q4 + 0);
-                        lo4.y = CH::last(w, hlo, 4 * q4 + 1); hi4.y = CH::last(w, hhi, 4 * q4 + 1);
-                        lo4.z = CH::last(w, hlo, 4 * q4 + 2); hi4.z = CH::last(w, hhi, 4 * q4 + 2);
-                        lo4.w = CH::last(w, hlo, 4 * q4 + 3); hi4.w = CH::last(w, hhi, 4 * q4 + 3);
-                        *reinterpret_cast<float4 *>(plo + q4 * qstride) = lo4;
-                        *reinterpret_cast<float4 *>(phi + q4 * qstride) = hi4;
-                    }
+                    for (int q2 = 0; q2 < R / 2; ++q2) {
+                        float4 v4;
+                        v4.x = CH::last(w, hlo, 2 * q2 + 0); v4.y = CH::last(w, hhi, 2 * q2 + 0);
+                        v4.z = CH::last(w, hlo, 2 * q2 + 1); v4.w = CH::last(w, hhi, 2 * q2 + 1);
+                        *reinterpret_cast<float4 *>(prow + q2 * qstride) = v4;
                     }
                 }
                 WV_STAMP(st2);
@@ -441,91 +333,46 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
     } else {
         // ------------------------------------------------------------------ consumer: pass V
         const bool active = t < W;
-        if (WV_SWT_VPRIO) __builtin_amdgcn_s_setprio(WV_SWT_VPRIO);   // the critical role issues first
-        // this column's slot in the permuted LDS row (see pass H)
-        const int tp = ((t % R) / 4) * (4 * g.nrun) + (t / R) * 4 + (t & 3);
-        const int tp2 = ((t % R) / 2) * (4 * g.nrun) + (t / R) * 4 + 2 * (t & 1);   // PAIRED layout (floats)
+        __builtin_amdgcn_s_setprio(kConsumerPrio);   // the critical role issues first
+        (void)(((t % R) / 4) * (4 * g.nrun) + (t / R) * 4 + (t & 3));   // see the note at the top
+        // this column's (lo, hi) slot in the permuted LDS row (see pass H)
+        const int tp = ((t % R) / 2) * (4 * g.nrun) + (t / R) * 4 + 2 * (t & 1);
+        using VS = VStep<L, NLEV, TH>;
         for (int q = wg_in_xcd; q < nq; q += wgs_per_xcd) {
             const int m = q / g.C, pc = (xcd + g.nxcd * m) * g.C + (q - m * g.C);
             OutT *oplane = reinterpret_cast<OutT *>(out) + (size_t)pc * g.pstride;
-            float tail[PAIRED ? 1 : 2][PAIRED ? 1 : HALO];
-            f32x2 tail2[PAIRED ? HALO : 1];
-            if constexpr (PAIRED) {
+            f32x2 tail[HALO];
 #pragma unroll
-                for (int i = 0; i < HALO; ++i) tail2[i] = f32x2{0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int i = 0; i < HALO; ++i) tail[0][i] = tail[1][i] = 0.f;
-            }
+            for (int i = 0; i < HALO; ++i) tail[i] = f32x2{0.f, 0.f};
             __syncthreads();       // chunk 0 produced
             for (int k = 0; k < nchunks; ++k) {
                 const int y0 = k * TH - HALO;              // first output row this chunk emits (uniform)
                 WV_STAMP(st0);
-                if constexpr (PAIRED) {
-                    if (active) {
-                        using VS = VStep<L, NLEV, TH, f32x2>;
-                        const float *col = ring + (k & 1) * buf_sz + tp2;
-                        f32x2 cur[TH];
-#pragma unroll
-                        for (int i = 0; i < TH; ++i) cur[i] = *reinterpret_cast<const f32x2 *>(col + i * (2 * P));
-                        VS::template lower<1>(cur, tail2, taps.lo);
-                        WV_STAMP(st1);
-                        if (y0 + TH <= 0) {
-                            VS::prime_last(cur, tail2);
-                        } else {
-                            // byte offsets of this lane inside the plane's 4-band block (< 2^32, host check)
-                            // the four band rows are wave-uniform pointers (SGPR pairs, scalar adds): the band stride
-                            // may exceed 32 bits in the band-major layout
-                            const uint32_t o0 = (uint32_t)t * (uint32_t)sizeof(OutT);
-                            const size_t bs = g.bstride;
-                            VS::last(cur, tail2, taps.lo, taps.hi, [&](int i, f32x2 a, f32x2 d) {
-                                const int y = y0 + i;
-                                if (y >= 0 && y < H) {
-                                    OutT *orow = oplane + (size_t)y * W;   // uniform: lives in an SGPR pair
-                                    store_row(orow, o0, (OutT)a.x);             // cA  = (row lo, col lo)
-                                    store_row(orow + bs, o0, (OutT)d.x);        // cH  = (row lo, col hi)
-                                    store_row(orow + 2 * bs, o0, (OutT)a.y);    // cV  = (row hi, col lo)
-                                    store_row(orow + 3 * bs, o0, (OutT)d.y);    // cD  = (row hi, col hi)
-                                }
-                            });
-                        }
-                    }
-                } else
                 if (active) {
+                    const float *col = ring + (k & 1) * buf_sz + tp;
+                    f32x2 cur[TH];
 #pragma unroll
-                    for (int pl = 0; pl < 2; ++pl) {
-                        const float *col = ring + (k & 1) * buf_sz + pl * plane_sz + tp;
-                        float cur[TH];
-#pragma unroll
-                        for (int i = 0; i < TH; ++i) cur[i] = col[i * P];
-                        VStep<L, NLEV, TH>::template lower<1>(cur, tail[pl], taps.lo);
-                        if (pl == 0) WV_STAMP(st1);
-                        if (y0 + TH <= 0) {               // nothing to emit yet: only advance the state
-                            VStep<L, NLEV, TH>::prime_last(cur, tail[pl]);
-                        } else {
-                            // byte offsets of this lane inside the plane's 4-band block (< 2^32, host check)
-                            const uint32_t off_lo = (uint32_t)t * (uint32_t)sizeof(OutT), off_hi = off_lo;
-                            OutT *oplane_lo = oplane + (size_t)(2 * pl) * g.bstride, *oplane_hi = oplane_lo + g.bstride;
-                            const size_t hi_delta = g.bstride;
-                            (void)oplane_hi;
-                            if (WV_SWT_FASTMID && y0 >= 0 && y0 + TH <= H) {   // interior chunk: all TH rows exist
-                                OutT *orow0 = oplane_lo + (size_t)y0 * W;
-                                VStep<L, NLEV, TH>::last(cur, tail[pl], taps.lo, taps.hi, [&](int i, float a, float d) {
-                                    OutT *orow = orow0 + (size_t)i * W;
-                                    store_row(orow, off_lo, (OutT)a);
-                                    store_row(orow + hi_delta, off_hi, (OutT)d);
-                                });
-                            } else {
-                                VStep<L, NLEV, TH>::last(cur, tail[pl], taps.lo, taps.hi, [&](int i, float a, float d) {
-                                    const int y = y0 + i;
-                                    if (y >= 0 && y < H) {
-                                        OutT *orow = oplane_lo + (size_t)y * W;   // uniform: lives in an SGPR pair
-                                        store_row(orow, off_lo, (OutT)a);
-                                        store_row(orow + hi_delta, off_hi, (OutT)d);
-                                    }
-                                });
+                    for (int i = 0; i < TH; ++i) cur[i] = *reinterpret_cast<const f32x2 *>(col + i * (2 * P));
+                    VS::template lower<1>(cur, tail, taps.lo);
+                    WV_STAMP(st1);
+                    if (y0 + TH <= 0) {                    // nothing to emit yet: only advance the state
+                        VS::prime_last(cur, tail);
+                    } else {
+                        // byte offset of this lane inside an output row (< 2^32, host check); the four band rows are
+                        // wave-uniform pointers (SGPR pairs, scalar adds): the band stride may exceed 32 bits in the
+                        // band-major layout
+                        const uint32_t o0 = (uint32_t)t * (uint32_t)sizeof(OutT);
+                        const size_t bs = g.bstride;
+                        VS::last(cur, tail, taps.lo, taps.hi, [&](int i, f32x2 a, f32x2 d) {
+                            const int y = y0 + i;
+                            if (y >= 0 && y < H) {
+                                OutT *orow = oplane + (size_t)y * W;   // uniform: lives in an SGPR pair
+                                store_row(orow, o0, (OutT)a.x);             // cA  = (row lo, col lo)
+                                store_row(orow + bs, o0, (OutT)d.x);        // cH  = (row lo, col hi)
+                                store_row(orow + 2 * bs, o0, (OutT)a.y);    // cV  = (row hi, col lo)
+                                store_row(orow + 3 * bs, o0, (OutT)d.y);    // cD  = (row hi, col hi)
                             }
-                        }
+                        });
                     }
                 }
                 WV_STAMP(st2);
@@ -553,22 +400,81 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
 // (2048 images, back to back) -- polling waves and the shorter per-stage batches cost more than the barrier wait they
 // remove, which the second workgroup of the CU was already filling.  Removed; see DESIGN.md section 5.
 
-template <int L, int NLEV, int R, int TH, int NT, int MINW, typename InT, int LAYOUT, bool BF16>
-static int launch_slide(const void *in, void *out, SlideGeom g, const float *lo, const float *hi, hipStream_t st)
+// LDS ring of width W: runs per row, pitch, bytes.  The planner (slide_fits) and the launch use this one computation.
+struct SlideRing {
+    int nrun, P;
+    size_t lds;
+};
+static SlideRing slide_ring(int W)
 {
-    constexpr int HALO = (L - 1) * ((1 << NLEV) - 1);
-    STaps<L> taps;
-    for (int i = 0; i < L; ++i) { taps.lo[i] = lo[i]; taps.hi[i] = hi[i]; }
-    g.nrun = (int)ceil_div(g.W, R);
-#ifndef WV_SWT_PITCH_PAD
-#define WV_SWT_PITCH_PAD 4
-#endif
-    g.P = g.nrun * R + WV_SWT_PITCH_PAD;          // multiple of 4; rows hold whole runs
-    const size_t lds = (size_t)2 * 2 * TH * g.P * sizeof(float);  // 2 buffers x 2 planes
-    // shapes this kernel does not take: the caller falls back to the tiled kernels
-    if (lds > (size_t)kMaxLdsBytes - 2048 || TH * g.nrun > NT || g.W > NT) return 1;
-    (void)HALO;
-    if (g.W < R + HALO || g.H < TH + 2 * HALO || (uint64_t)g.H * g.W * 4 >= (1ull << 30)) return 1;
+    SlideRing r;
+    r.nrun = (int)ceil_div(W, kSlideR);
+    r.P = r.nrun * kSlideR + kPitchPad;                         // multiple of 4; rows hold whole runs
+    r.lds = (size_t)2 * 2 * kSlideTH * r.P * sizeof(float);     // 2 buffers x 2 planes
+    return r;
+}
+
+// (taps, levels) with a sliding instantiation (swt_slide_launch): the shipped configs (haar L1 = c0, db2 L3 = c1), the other
+// levels of the 2- and 4-tap wavelets, and level 1 of the 8- and 10-tap wavelets the studies sweep (db4, bior4.4).
+static bool slide_config(int L, int n)
+{
+    return ((L == 2 || L == 4) && n >= 1 && n <= 3) || ((L == 8 || L == 10) && n == 1);
+}
+
+bool slide_fits(const SwtShape &s, char *why, size_t why_len)
+{
+#define WV_NO(...) do { if (why) snprintf(why, why_len, __VA_ARGS__); return false; } while (0)
+    if (!slide_config(s.L, s.level))
+        WV_NO("%d taps at level %d (instantiated: 2 or 4 taps at levels 1-3, 8 or 10 taps at level 1)", s.L, s.level);
+    if (s.in_layout != WV_LAYOUT_NCHW && !(s.in_layout == WV_LAYOUT_NHWC && s.C == 3))
+        WV_NO("input layout %d with C = %d (NCHW, or NHWC with C == 3)", s.in_layout, s.C);
+    const int halo = (s.L - 1) * ((1 << s.level) - 1);
+    const int wmin = std::max(40, kSlideR + halo), hmin = std::max(40, kSlideTH + 2 * halo);
+    if (s.W % 4 || s.W < wmin || s.W > kSlideNT) WV_NO("W = %d (W %% 4 == 0, %d <= W <= %d)", s.W, wmin, kSlideNT);
+    if (s.H < hmin) WV_NO("H = %d (H >= %d)", s.H, hmin);
+    const SlideRing r = slide_ring(s.W);
+    if (kSlideTH * r.nrun > kSlideNT || r.lds > (size_t)kMaxLdsBytes - 2048)
+        WV_NO("W = %d (LDS ring of %zu bytes for %d runs)", s.W, r.lds, r.nrun);
+    if ((uint64_t)s.H * s.W * 4 >= (1ull << 30)) WV_NO("H*W = %lld (4*H*W < 2^30)", (long long)s.H * s.W);
+    return true;
+#undef WV_NO
+}
+
+// Diagnostic build (WV_SWT_STAMPS=1): run the STAMP instantiation once, synchronously, and print where each role's
+// cycles go.
+template <typename Kern, typename InT, int L>
+static int run_stamped(Kern kstamp, int64_t grid, size_t lds, hipStream_t st, const InT *in, void *out, SlideGeom g,
+                       const Taps<L> &taps)
+{
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kstamp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t nw = (size_t)grid * (2 * kSlideNT / 64);
+    unsigned long long *dbuf = nullptr;
+    if (hipMalloc(&dbuf, nw * 8 * sizeof(unsigned long long)) != hipSuccess) WV_FAIL(WV_EHIP, "stamps: hipMalloc");
+    g.stamps = dbuf;
+    hipLaunchKernelGGL(kstamp, dim3((unsigned)grid), dim3(2 * kSlideNT), lds, st, in, out, g, taps);
+    std::vector<unsigned long long> hbuf(nw * 8, 0);
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpy(hbuf.data(), dbuf, nw * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipFree(dbuf);
+    double a[2][6] = {{0}, {0}};
+    size_t cnt[2] = {0, 0};
+    for (size_t i = 0; i < nw; ++i) {
+        const int role = (int)hbuf[8 * i + 3];
+        for (int c = 0; c < 6; ++c) a[role][c] += (double)hbuf[8 * i + c];
+        cnt[role]++;
+    }
+    fprintf(stderr, "[swt stamps] V waves=%zu: LDS read+lower(pl0) %.0f | rest(last+stores, pl1) %.0f | barrier %.0f\n", cnt[0],
+            a[0][0] / cnt[0], a[0][1] / cnt[0], a[0][2] / cnt[0]);
+    fprintf(stderr, "[swt stamps] H waves=%zu: wait loads+convert %.0f | issue next loads %.0f | lower levels %.0f | last level+LDS write %.0f | barrier %.0f\n",
+            cnt[1], a[1][0] / cnt[1], a[1][4] / cnt[1], a[1][5] / cnt[1], a[1][1] / cnt[1], a[1][2] / cnt[1]);
+    return WV_OK;
+}
+
+template <int L, int NLEV, typename InT, int LAYOUT, bool BF16>
+static int launch_slide(const void *in, void *out, SlideGeom g, size_t lds, const Taps<L> &taps, hipStream_t st)
+{
+    constexpr int R = kSlideR, TH = kSlideTH, NT = kSlideNT, MINW = kSlideMinW;
     auto kern = k_swt_slide<L, NLEV, R, TH, NT, MINW, InT, LAYOUT, BF16>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
@@ -584,58 +490,32 @@ static int launch_slide(const void *in, void *out, SlideGeom g, const float *lo,
         num_cu = prop.multiProcessorCount;
     }
     const int by_lds = std::max<int>(1, (int)((size_t)kMaxLdsBytes / (lds + 512)));
-    const char *env = ::wv::tune("WV_SWT_WG_PER_CU");
-    const int per_cu = env && atoi(env) > 0 ? atoi(env) : std::min(by_lds, std::max(1, MINW * 256 / (2 * NT)));
+    const int per_cu = std::min(by_lds, std::max(1, MINW * 256 / (2 * NT)));
     const int64_t planes = (int64_t)g.B * g.C;
     int64_t grid = std::min<int64_t>(planes, (int64_t)num_cu * per_cu);
-    const char *cenv = ::wv::tune("WV_SWT_COAL");
     g.coal = std::is_same<InT, uint8_t>::value && LAYOUT == 0 && R == 16 && g.W % 16 == 0 && g.nrun <= 16 &&
-             (int64_t)g.H * g.W % 16 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && !(cenv && atoi(cenv) == 0);
-    const char *xenv = ::wv::tune("WV_SWT_XCD");
-    g.nxcd = xenv ? std::max(1, atoi(xenv)) : 8;
+             (int64_t)g.H * g.W % 16 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    g.nxcd = kXcds;
     if (grid < planes) grid -= grid % g.nxcd;      // persistent launch: same number of workgroups on every XCD
     if (grid <= 0 || grid % g.nxcd) g.nxcd = 1, grid = std::min<int64_t>(planes, (int64_t)num_cu * per_cu);
-    constexpr bool kHasStampBuild = (L == 4 && NLEV == 3) || (L == 2 && NLEV == 1);   // the two shipped configs
-    if constexpr (kHasStampBuild)
-    if (::wv::tune("WV_SWT_STAMPS")) {   // diagnostic build: run once, print where each role's cycles go
-        auto kstamp = k_swt_slide<L, NLEV, R, TH, NT, MINW, InT, LAYOUT, BF16, true>;
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kstamp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        const size_t nw = (size_t)grid * (2 * NT / 64);
-        unsigned long long *dbuf = nullptr;
-        if (hipMalloc(&dbuf, nw * 8 * sizeof(unsigned long long)) != hipSuccess) WV_FAIL(WV_EHIP, "stamps: hipMalloc");
-        g.stamps = dbuf;
-        hipLaunchKernelGGL(kstamp, dim3((unsigned)grid), dim3(2 * NT), lds, st, (const InT *)in, out, g, taps);
-        std::vector<unsigned long long> hbuf(nw * 8, 0);
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(hbuf.data(), dbuf, nw * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        (void)hipFree(dbuf);
-        double a[2][6] = {{0}, {0}};
-        size_t cnt[2] = {0, 0};
-        for (size_t i = 0; i < nw; ++i) {
-            const int role = (int)hbuf[8 * i + 3];
-            for (int c = 0; c < 6; ++c) a[role][c] += (double)hbuf[8 * i + c];
-            cnt[role]++;
-        }
-        fprintf(stderr, "[swt stamps] V waves=%zu: LDS read+lower(pl0) %.0f | rest(last+stores, pl1) %.0f | barrier %.0f\n", cnt[0],
-                a[0][0] / cnt[0], a[0][1] / cnt[0], a[0][2] / cnt[0]);
-        fprintf(stderr, "[swt stamps] H waves=%zu: wait loads+convert %.0f | issue next loads %.0f | lower levels %.0f | last level+LDS write %.0f | barrier %.0f\n",
-                cnt[1], a[1][0] / cnt[1], a[1][4] / cnt[1], a[1][5] / cnt[1], a[1][1] / cnt[1], a[1][2] / cnt[1]);
-        return WV_OK;
-    }
+    if constexpr ((L == 4 && NLEV == 3) || (L == 2 && NLEV == 1))   // the two shipped configs have a STAMP build
+        if (::wv::tune("WV_SWT_STAMPS"))
+            return run_stamped(k_swt_slide<L, NLEV, R, TH, NT, MINW, InT, LAYOUT, BF16, true>, grid, lds, st,
+                               (const InT *)in, out, g, taps);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(2 * NT), lds, st, (const InT *)in, out, g, taps);
     WV_CHECK_LAUNCH("k_swt_slide");
     return WV_OK;
 }
 
-template <int L, int NLEV, int R, int TH, int NT, int MINW>
-static int slide_types(const void *in, int in_dtype, void *out, const SlideGeom &g, const float *lo, const float *hi,
-                       hipStream_t st)
+template <int L, int NLEV>
+static int slide_types(const SwtShape &s, const void *in, void *out, const SlideGeom &g, size_t lds, const float *lo,
+                       const float *hi, hipStream_t st)
 {
-    const bool nhwc3 = g.in_layout == WV_LAYOUT_NHWC && g.C == 3;
-    if (g.in_layout != WV_LAYOUT_NCHW && !nhwc3) return 1;
-#define WV_GO(T, LAY, BF) return launch_slide<L, NLEV, R, TH, NT, MINW, T, LAY, BF>(in, out, g, lo, hi, st)
-    if (in_dtype == WV_DT_U8) {
+    Taps<L> taps;
+    for (int i = 0; i < L; ++i) { taps.lo[i] = lo[i]; taps.hi[i] = hi[i]; }
+    const bool nhwc3 = s.in_layout == WV_LAYOUT_NHWC;   // C == 3 (slide_fits)
+#define WV_GO(T, LAY, BF) return launch_slide<L, NLEV, T, LAY, BF>(in, out, g, lds, taps, st)
+    if (s.in_dtype == WV_DT_U8) {
         if (nhwc3) { if (g.out_bf16) WV_GO(uint8_t, 1, true); WV_GO(uint8_t, 1, false); }
         if (g.out_bf16) WV_GO(uint8_t, 0, true);
         WV_GO(uint8_t, 0, false);
@@ -646,33 +526,21 @@ static int slide_types(const void *in, int in_dtype, void *out, const SlideGeom 
 #undef WV_GO
 }
 
-// (taps, levels) with a sliding instantiation: the shipped configs (haar L1 = c0, db2 L3 = c1), the other levels of
-// the 2- and 4-tap wavelets, and level 1 of the 8- and 10-tap wavelets the studies sweep (db4, bior4.4).  Everything
-// else (and shapes outside the window below) runs on swt_fused.hip / swt.hip.
-static bool slide_config(int L, int n)
+int swt_slide_launch(const SwtShape &s, const void *in, void *out, const float *lo, const float *hi, hipStream_t st,
+                     int out_layout, int64_t band_stride)
 {
-    return ((L == 2 || L == 4) && n >= 1 && n <= 3) || ((L == 8 || L == 10) && n == 1);
-}
-
-bool swt_slide_covers(int L, int n, int W, int H)
-{
-    return slide_config(L, n) && (W % 4) == 0 && W <= 256 && W >= 40 && H >= 40;
-}
-
-int swt_slide_launch(const void *in, int in_dtype, int in_layout, void *out, int out_dtype, int B, int C, int H,
-                     int W, int n, const float *lo, const float *hi, int L, hipStream_t st, int out_layout,
-                     int64_t band_stride)
-{
+    const SlideRing r = slide_ring(s.W);
     SlideGeom g{};
-    g.B = B; g.C = C; g.H = H; g.W = W; g.in_layout = in_layout; g.out_bf16 = out_dtype == WV_DT_BF16;
-    const size_t hw = (size_t)H * W;
+    g.B = s.B; g.C = s.C; g.H = s.H; g.W = s.W; g.in_layout = s.in_layout; g.out_bf16 = s.out_dtype == WV_DT_BF16;
+    g.nrun = r.nrun; g.P = r.P;
+    const size_t hw = (size_t)s.H * s.W;
     if (out_layout == WV_BANDS_OUTER) { g.pstride = hw; g.bstride = (size_t)band_stride; }
     else { g.pstride = 4 * hw; g.bstride = hw; }
-#define WV_CFG(LL, NN) if (L == LL && n == NN) return slide_types<LL, NN, 16, 16, 256, 4>(in, in_dtype, out, g, lo, hi, st)
+#define WV_CFG(LL, NN) if (s.L == LL && s.level == NN) return slide_types<LL, NN>(s, in, out, g, r.lds, lo, hi, st)
     WV_CFG(4, 3); WV_CFG(2, 1);
     WV_CFG(4, 1); WV_CFG(4, 2); WV_CFG(2, 2); WV_CFG(2, 3); WV_CFG(8, 1); WV_CFG(10, 1);
 #undef WV_CFG
-    return 1;
+    WV_FAIL(WV_ENOTSUP, "swt slide: %d taps at level %d", s.L, s.level);   // unreachable after slide_fits()
 }
 
 }  // namespace wv

@@ -62,8 +62,28 @@ def test_argument_validation_happens_on_the_host():
     assert rc == -12 and b"workspace" in lib.wv_last_error()
     assert lib.wv_hamming_topk_workspace_bytes(4, 25000, 1, 5000) == 98 * 256 * 8
     assert lib.wv_hamming_dist(None, one, one, 10, 1, 10, 1, None) == -22
-    assert lib.wv_swt2d_workspace_bytes(2, 3, 224, 224, 3, 4) == 0          # tiled kernel covers it
+    assert lib.wv_swt2d_workspace_bytes(2, 3, 224, 224, 3, 4) == 0          # sliding kernel covers it
     assert lib.wv_swt2d_workspace_bytes(2, 3, 30, 30, 1, 2) == 3 * 2 * 3 * 30 * 30 * 4  # W % 4 != 0
+    assert lib.wv_swt2d_workspace_bytes(2, 3, 48, 224, 3, 4) == 0           # db2 L3 below the sliding window: fused
+    assert lib.wv_swt2d_workspace_bytes(2, 3, 224, 224, 3, 8) == 0          # db4 L3: tiled
+    assert lib.wv_swt2d_workspace_bytes(2, 3, 224, 224, 1, 6) == 3 * 2 * 3 * 224 * 224 * 4  # 6 taps: generic
+
+
+def test_swt_planner_agrees_with_the_kernels(diag):
+    """One planner decides which SWT kernel runs, sizes the workspace and words the band-major refusal: db2 L3 at
+    H = 48 is below the sliding kernel's window (H >= 16 + 2 * 21), so with that path pinned the call goes to the generic
+    kernels and the workspace query says so; the band-major entry point quotes the rule the shape breaks."""
+    lib = _lib.load()
+    diag.setenv("WV_SWT_PATH", "slide")
+    assert lib.wv_swt2d_workspace_bytes(2, 3, 224, 224, 3, 4) == 0
+    assert lib.wv_swt2d_workspace_bytes(2, 3, 48, 224, 3, 4) == 3 * 2 * 3 * 48 * 224 * 4
+    diag.delenv("WV_SWT_PATH")
+    assert lib.wv_swt2d_workspace_bytes(2, 3, 48, 224, 3, 4) == 0
+    one = ctypes.c_void_p(16)  # never dereferenced: the shape is refused first
+    lo = _lib.host_floats([0.5, 0.5, 0.5, 0.5])
+    rc = lib.wv_swt2d_forward_ex(one, _lib.WV_DT_U8, _lib.WV_LAYOUT_NCHW, one, _lib.WV_DT_F32, _lib.WV_BANDS_OUTER,
+                                 2 * 3 * 48 * 224, 2, 3, 48, 224, 3, lo, lo, 4, None, 0, None)
+    assert rc == -95 and b"H = 48 (H >= 58)" in lib.wv_last_error()
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only behaviour")

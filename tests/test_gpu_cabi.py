@@ -54,7 +54,8 @@ def test_side_stream_is_honoured():
 
 
 @pytest.mark.parametrize("path", ["slide", "fused", "tiled", "generic"])
-@pytest.mark.parametrize("wl,lev,H_,W_", [("db2", 3, 224, 224), ("haar", 1, 224, 224), ("db2", 3, 64, 96)])
+@pytest.mark.parametrize("wl,lev,H_,W_", [("db2", 3, 224, 224), ("haar", 1, 224, 224), ("db2", 3, 64, 96),
+                                          ("db2", 3, 48, 224)])   # the last: below the sliding kernel's window
 def test_every_swt_implementation_agrees_with_the_oracle(path, wl, lev, H_, W_, diag):
     from wvhash.transforms import swt2d
     diag.setenv("WV_SWT_PATH", path)

@@ -86,7 +86,8 @@ def test_host_twin_equals_kernel_bit_for_bit(wl, lev, channels_last):
 
 
 @pytest.mark.parametrize("wl,lev,H,W", [("db2", 3, 224, 224), ("haar", 1, 224, 224), ("bior4.4", 1, 56, 256),
-                                        ("db2", 3, 512, 384), ("db4", 2, 96, 96)])   # the last two: not the sliding kernel
+                                        ("db2", 3, 512, 384), ("db4", 2, 96, 96),
+                                        ("db2", 3, 48, 224)])   # the last three: not the sliding kernel
 @pytest.mark.parametrize("out_dtype", [torch.float32, torch.bfloat16])
 def test_band_major_output_is_the_permuted_reference_layout(wl, lev, H, W, out_dtype):
     x = torch.from_numpy(synth.natural_images(5, H, W, seed=W)).permute(0, 3, 1, 2).contiguous().cuda()

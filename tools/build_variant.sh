@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a variant of libwvhash.so with extra -D flags on ONE source file, for same-session A/B timing:
-#   tools/build_variant.sh NAME swt_slide.hip -DWV_SWT_VPRIO=0 ...   ->  tools/_variants/NAME.so
+#   tools/build_variant.sh NAME swt_slide.hip -DWV_SWT_NOSTORE ...   ->  tools/_variants/NAME.so
 # Use it with WVHASH_LIB=tools/_variants/NAME.so python tools/bench_kernels.py ...
 set -euo pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
