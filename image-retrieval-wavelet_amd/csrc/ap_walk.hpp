@@ -9,7 +9,7 @@ namespace wv {
 
 constexpr int kApRounds = 32;                // list positions per thread kept as bits at a time (one chunk of the walk)
 
-// dwords of LDS scratch ap_finish needs: hit counts [kApRounds][NW] + NW doubles (8-byte aligned)
+// dwords of LDS scratch the walk needs: hit counts [kApRounds][NW] + NW doubles (8-byte aligned)
 template <int TPQ>
 __host__ __device__ constexpr int ap_scratch_dwords() { return kApRounds * (TPQ / 64) + 2 * (TPQ / 64) + 2; }
 
@@ -75,21 +75,6 @@ __device__ __forceinline__ void ap_final(const ApState &st, double *wsum, int t,
         *ap_out = st.running ? (float)(s / (double)st.running) : 0.0f;
         if (nrel_out) *nrel_out = (int32_t)st.running;
     }
-}
-
-// One chunk is the whole list (R <= kApRounds rounds): relbits: bit r = relevance of position r * TPQ + t.  cnt[r * NW + wave] =
-// hits of that wave in round r, written by lane 0 of every wave BEFORE the call (the function starts with the group barrier that
-// publishes them).  SYNC: the barrier of the TPQ threads that share the list.
-template <int TPQ, typename SYNC>
-__device__ __forceinline__ void ap_finish(uint32_t relbits, uint32_t *scratch, int R, int t, float *__restrict__ ap_out,
-                                          int32_t *__restrict__ nrel_out, SYNC group_barrier)
-{
-    constexpr int NW = TPQ / 64;
-    double *wsum = reinterpret_cast<double *>(scratch + kApRounds * NW + (kApRounds * NW & 1));
-    group_barrier();
-    ApState st;
-    ap_accum<TPQ>(relbits, scratch, R, 0, t, st);
-    ap_final<TPQ>(st, wsum, t, ap_out, nrel_out, group_barrier);
 }
 
 }  // namespace wv

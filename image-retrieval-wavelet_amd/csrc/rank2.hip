@@ -1,10 +1,10 @@
-// Windowed, branch-free Hamming ranking kernel for gfx950 (second generation of topk.hip's counting sort).
+// Windowed, branch-free Hamming ranking kernel for gfx950.
 //
 // Same contract as k_hamming_topk (topk.hip): the k nearest database codes of every query in ascending
 // (distance, database index) order -- torch.argsort(stable=True) of accuracy_calculator.py:219-223 -- as an exact
 // counting sort: thread t owns the contiguous item range [t*C, (t+1)*C) and a private column of an LDS count table.
-// What changed, and why (rocprofv3 / ISA of the first kernel: 336 exec-mask branches per pass, 34 KB of LDS per
-// query, 122 VGPRs, 1.7x write amplification from scattered 4-byte index stores):
+// Where it differs from the column kernel, and why (rocprofv3 / ISA of that kernel: 336 exec-mask branches per pass,
+// 34 KB of LDS per query, 122 VGPRs, 1.7x write amplification from scattered 4-byte index stores):
 //   * the table covers a WINDOW of 32 distance bins starting at the query's smallest distance, not all nbits+1 bins:
 //     17 KB instead of 34 KB (distances of a query concentrate in far fewer than 32 bins; if the k-th neighbour lies
 //     beyond the window the window slides on and the pass repeats -- exact for any input, one pass in practice);
@@ -16,9 +16,9 @@
 //     row-sharded search, many queries against few rows each.
 //   * a workgroup's time is a chain of latencies (phase stamps), so loads and returning LDS adds are kept
 //     deep in flight: a lane loads 16 bytes of the database image (two 64-bit codes) per instruction, eight loads per
-//     batch, sixteen returning adds before the first rank is used.  The kernel can compute the distances of QB queries
-//     from one pass over the image (template parameter; the queries are then ranked one after the other through the same
-//     LDS) -- measured slower than QB = 1 at every shape, so only QB = 1 is instantiated;
+//     batch, sixteen returning adds before the first rank is used.  Sharing one pass over the image between several
+//     queries of a group (ranked one after the other through the same LDS) was measured slower than one query per pass at
+//     every shape and removed;
 //   * k = 0 is a histogram-only mode (one count pass over all bins), rows16 output writes 16-bit local row numbers:
 //     the two steps of the sharded search (wv_hamming_hist, wv_hamming_topk_rows16).
 //   * optional: average precision of the list without ever writing it (wv_hamming_map_at_k).  calculate_maphashing
@@ -28,8 +28,9 @@
 //     query's classes is its relevance bitmap (N bits, in LDS), and after placement the list in LDS is walked against
 //     the bitmap -- same thread <-> position mapping and summation order as k_map_at_k, bit-identical AP.
 // Covers databases (shards) of at most 32,768 rows -- C <= 128 items per thread, their distances cached in registers as
-// bytes; 16-bit item numbers and counters -- and k small enough for the LDS list; everything else stays on topk.hip's kernel.
-#include "common.hpp"
+// bytes; 16-bit item numbers and counters -- and k small enough for the LDS list; everything else stays on topk.hip's
+// kernel (the rules: rank_plan(), rank.hpp).
+#include "rank.hpp"
 #include "ap_walk.hpp"
 
 namespace wv {
@@ -46,22 +47,6 @@ __device__ unsigned long long g_rank2_stamps[8];
 #define R2_STAMP(i) do { } while (0)
 #define R2_STAMP_INIT do { } while (0)
 #endif
-
-#ifndef WV_R2_WINBINS
-#define WV_R2_WINBINS 32
-#endif
-#ifndef WV_R2_W25
-#define WV_R2_W25 5
-#endif
-// Timing ablations (tools/build_variant.sh ... -DWV_R2_ABL=n; results are wrong by construction): 1 = the list is not stored,
-// 2 = nothing is placed either, 3 = nothing is counted either (distance pass + scans of an empty table), 4 = distance pass only,
-// 5 = full kernel but every placement store goes to the lane's own trash slot (no scatter, no bank conflicts)
-#ifndef WV_R2_ABL
-#define WV_R2_ABL 0
-#endif
-constexpr int kWinBins = WV_R2_WINBINS;      // distance bins per window
-constexpr int kWinRows = kWinBins + 1;       // + the dummy row
-constexpr int kMaxBins2 = 130;               // nbits <= 128
 
 template <int WORDS>
 struct QCode {
@@ -91,40 +76,13 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
 struct Rank2Lds {
     uint32_t *table;     // [kWinRows][TPQ/2] dwords = u16 cell per (row, thread)
     uint16_t *stage;     // [k + TPQ]: ranked item numbers, then one trash slot per lane
-    uint32_t *gbase;     // [kMaxBins2 + 1]: gbase[b] = rows with distance < b (filled as windows complete)
+    uint32_t *gbase;     // [kMaxBins + 1]: gbase[b] = rows with distance < b (filled as windows complete)
     uint32_t *tot;       // [kWinBins]
     uint32_t *misc;      // [4]: group minimum etc.
 };
 
-// average precision instead of (or beside) the list: all pointers NULL = off
-struct Rank2Ap {
-    const uint32_t *cls;     // class-major label bit matrix [64 * lwords][ceil(N / 32)] (rank2_labels_prepare)
-    const uint64_t *qlab;    // [Q][lwords] label words of every query
-    int lwords;              // 1 or 2 (up to 128 classes)
-    float *ap;               // [Q]
-    int32_t *nrel;           // [Q] relevant entries among the k (or NULL)
-    uint64_t *relbits;       // [Q][ceil(k / 64)] instead of ap: the relevance string of the list (sharded mAP)
-    int64_t relbits_ld;      // row pitch of relbits in uint64 (0 = ceil(k / 64))
-    int64_t cum_ld;          // row pitch of the histograms in uint32 (0 = nbits + 2): relbits and cum may share one wire buffer
-};
-
-// words of the relevance bitmap: one bit per database row
-__host__ __device__ inline int rank2_bitmap_words(int64_t N) { return (int)((N + 31) / 32); }
-
-template <int TPQ>
-__host__ __device__ inline size_t rank2_lds_bytes_per_query(int k, int bm_words = 0)
-{
-    size_t b = (size_t)kWinRows * (TPQ / 2) * 4;                 // table
-    b += ((size_t)(k + TPQ) * 2 + 15) / 16 * 16;                 // stage
-    b += (size_t)(kMaxBins2 + 1 + kWinBins + 4 + 3) / 4 * 4 * 4; // gbase, tot, misc
-    b += (size_t)bm_words * 4;                                   // relevance bitmap
-    b = (b + 15) / 16 * 16;
-    const size_t hist = (size_t)(kMaxBins2 + 1) * 17 * 4;        // histogram-only mode: [bins + 1][16] dwords + totals
-    return b > hist ? b : (hist + 15) / 16 * 16;
-}
-
-// One pass over the database image: distances of QB queries -> bytes in registers (dc[qq][i/4] byte i%4 = item i of this
-// thread; 255 = no item), and a lower bound of this thread's smallest distance per query.
+// One pass over the database image: distances of the query -> bytes in registers (dc[i/4] byte i%4 = item i of this
+// thread; 255 = no item), and a lower bound of this thread's smallest distance.
 // Image (rank2_prepare): 16 bytes per (row, thread): two consecutive 64-bit codes of the thread, or one 128-bit code.
 // Nothing in the item loop asks whether an item exists (a compare + select per item was 2 of its 7 VALU instructions):
 // slots beyond the thread's C items and the padding items behind row N - 1 (zero codes in the image) get a distance like
@@ -132,9 +90,9 @@ __host__ __device__ inline size_t rank2_lds_bytes_per_query(int k, int bm_words 
 // and, in the one or few threads behind the last row, one divergent fix-up.  dmin may therefore include a padding item's
 // distance popcount(q): a bound BELOW the true minimum only opens the first window earlier (bins without rows), which
 // is exact.
-template <int WORDS, int TPQ, int NC, int QB>
-__device__ __forceinline__ void rank2_distances(const uint4 *__restrict__ img, const QCode<WORDS> (&qc)[QB], int64_t N, int C,
-                                                int t, uint32_t (&dc)[QB][NC], uint32_t (&dmin)[QB])
+template <int WORDS, int TPQ, int NC>
+__device__ __forceinline__ void rank2_distances(const uint4 *__restrict__ img, const QCode<WORDS> &qc, int64_t N, int C,
+                                                int t, uint32_t (&dc)[NC], uint32_t &dmin)
 {
     constexpr int UNR = WORDS == 1 ? 16 : 8;                     // items per batch: eight 16-byte loads in flight per lane (a
     constexpr int LPB = WORDS == 1 ? UNR / 2 : UNR;              // workgroup's time is a chain of load -> popcount rounds)
@@ -147,12 +105,9 @@ __device__ __forceinline__ void rank2_distances(const uint4 *__restrict__ img, c
     const int nvalid = min(C, max(0, (int)N - first));           // N < 65536, first <= 256 * 128: plain ints
     const int rows = WORDS == 1 ? (C + 1) / 2 : C;               // image rows
     const uint32_t toff = (uint32_t)t * 16u;
+    dmin = 255;
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq) {
-        dmin[qq] = 255;
-#pragma unroll
-        for (int i = 0; i < NC; ++i) dc[qq][i] = 0xffffffffu;
-    }
+    for (int i = 0; i < NC; ++i) dc[i] = 0xffffffffu;
 #pragma unroll
     for (int bi = 0; bi < (NC * 4 + UNR - 1) / UNR; ++bi) {
         if (bi * UNR < C) {                                      // uniform
@@ -160,35 +115,28 @@ __device__ __forceinline__ void rank2_distances(const uint4 *__restrict__ img, c
 #pragma unroll
             for (int u = 0; u < LPB; ++u)                        // uniform row base (SGPRs) + the lane's 32-bit byte offset
                 raw[u] = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(img) +
-#ifdef WV_R2_SAMEROW   /* timing probe: every load hits the same 4 KB of the image (L1-resident) */
-                                                          (size_t)min((bi * LPB + u) & 1, rows - 1) * (TPQ * 16) + toff);
-#else
                                                           (size_t)min(bi * LPB + u, rows - 1) * (TPQ * 16) + toff);
-#endif
 #pragma unroll
-            for (int qq = 0; qq < QB; ++qq) {
+            for (int u4 = 0; u4 < UNR / 4; ++u4) {
+                if (bi * (UNR / 4) + u4 >= NC) continue;         // NC odd: the last batch has one cache word
+                uint32_t word = 0;
 #pragma unroll
-                for (int u4 = 0; u4 < UNR / 4; ++u4) {
-                    if (bi * (UNR / 4) + u4 >= NC) continue;     // NC odd: the last batch has one cache word
-                    uint32_t word = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int u = 4 * u4 + j;
-                        uint32_t d;
-                        if constexpr (WORDS == 1) {
-                            const uint4 v = raw[u >> 1];
-                            const uint32_t lo32 = (u & 1) ? v.z : v.x, hi32 = (u & 1) ? v.w : v.y;
-                            d = (uint32_t)__popc(lo32 ^ (uint32_t)qc[qq].w[0]) + (uint32_t)__popc(hi32 ^ (uint32_t)(qc[qq].w[0] >> 32));
-                        } else {
-                            const uint4 v = raw[u];
-                            d = (uint32_t)__popc(v.x ^ (uint32_t)qc[qq].w[0]) + (uint32_t)__popc(v.y ^ (uint32_t)(qc[qq].w[0] >> 32)) +
-                                (uint32_t)__popc(v.z ^ (uint32_t)qc[qq].w[1]) + (uint32_t)__popc(v.w ^ (uint32_t)(qc[qq].w[1] >> 32));
-                        }
-                        dmin[qq] = min(dmin[qq], d);             // slots beyond C repeat the thread's last row: real distances
-                        word |= d << (8 * j);
+                for (int j = 0; j < 4; ++j) {
+                    const int u = 4 * u4 + j;
+                    uint32_t d;
+                    if constexpr (WORDS == 1) {
+                        const uint4 v = raw[u >> 1];
+                        const uint32_t lo32 = (u & 1) ? v.z : v.x, hi32 = (u & 1) ? v.w : v.y;
+                        d = (uint32_t)__popc(lo32 ^ (uint32_t)qc.w[0]) + (uint32_t)__popc(hi32 ^ (uint32_t)(qc.w[0] >> 32));
+                    } else {
+                        const uint4 v = raw[u];
+                        d = (uint32_t)__popc(v.x ^ (uint32_t)qc.w[0]) + (uint32_t)__popc(v.y ^ (uint32_t)(qc.w[0] >> 32)) +
+                            (uint32_t)__popc(v.z ^ (uint32_t)qc.w[1]) + (uint32_t)__popc(v.w ^ (uint32_t)(qc.w[1] >> 32));
                     }
-                    dc[qq][bi * (UNR / 4) + u4] = word;
+                    dmin = min(dmin, d);                         // slots beyond C repeat the thread's last row: real distances
+                    word |= d << (8 * j);
                 }
+                dc[bi * (UNR / 4) + u4] = word;
             }
         }
     }
@@ -196,18 +144,14 @@ __device__ __forceinline__ void rank2_distances(const uint4 *__restrict__ img, c
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
         const int keep = min(4, max(0, C - 4 * i));              // item slots of word i below C
-        const uint32_t fill = keep >= 4 ? 0u : (0xffffffffu << (8 * keep));
-#pragma unroll
-        for (int qq = 0; qq < QB; ++qq) dc[qq][i] |= fill;
+        dc[i] |= keep >= 4 ? 0u : (0xffffffffu << (8 * keep));
     }
     // ... and the threads behind the database's last row (nvalid < C: the last thread with rows and every one after it)
     if (nvalid < C) {
 #pragma unroll
         for (int i = 0; i < NC; ++i) {
             const int keep = min(4, max(0, nvalid - 4 * i));
-            const uint32_t fill = keep >= 4 ? 0u : (0xffffffffu << (8 * keep));
-#pragma unroll
-            for (int qq = 0; qq < QB; ++qq) dc[qq][i] |= fill;
+            dc[i] |= keep >= 4 ? 0u : (0xffffffffu << (8 * keep));
         }
     }
 }
@@ -219,7 +163,7 @@ __device__ __forceinline__ void rank2_hist_only(const uint32_t (&dc)[NC], int64_
                                                 uint32_t *__restrict__ cum_out, uint8_t *lds_raw, int t)
 {
     uint32_t *table = reinterpret_cast<uint32_t *>(lds_raw);     // [nbins + 1][16] dwords (the window table's space: 8.3 KB of 16.9)
-    uint32_t *tot = table + (kMaxBins2 + 1) * 16;                // [kMaxBins2 + 1]
+    uint32_t *tot = table + (kMaxBins + 1) * 16;                // [kMaxBins + 1]
     for (int i = t; i < (nbins + 1) * 16; i += TPQ) table[i] = 0;
     group_sync<TPQ>();
     const uint32_t c = (uint32_t)(t & 31);
@@ -370,7 +314,7 @@ __device__ __forceinline__ Rank2Lds rank2_lds(uint8_t *lds_raw, int k)
     L.stage = reinterpret_cast<uint16_t *>(p);
     p += ((size_t)(k + TPQ) * 2 + 15) / 16 * 16;
     L.gbase = reinterpret_cast<uint32_t *>(p);
-    L.tot = L.gbase + kMaxBins2 + 1;
+    L.tot = L.gbase + kMaxBins + 1;
     L.misc = L.tot + kWinBins;
     return L;
 }
@@ -522,7 +466,7 @@ __device__ __forceinline__ void rank2_rank(const uint32_t (&dc)[NC], uint32_t dm
         char *row0 = tbl + cell_addr;
 #pragma unroll
         for (int bw = 0; bw < NC; bw += 2) {
-            if (bw * 4 < C && (WV_R2_ABL < 3 || WV_R2_ABL == 5 || k < 0)) {         // uniform; items >= C of the batch hold 255 -> dummy row
+            if (bw * 4 < C) {                                     // uniform; items >= C of the batch hold 255 -> dummy row
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     if (bw + (j >> 2) < NC) {
@@ -609,7 +553,7 @@ __device__ __forceinline__ void rank2_rank(const uint32_t (&dc)[NC], uint32_t dm
             // cost here).
 #pragma unroll
             for (int bw = 0; bw < NC; bw += 4) {
-                if (bw * 4 < C && (WV_R2_ABL < 2 || WV_R2_ABL == 5 || k < 0)) {     // uniform
+                if (bw * 4 < C) {                                 // uniform
                     uint32_t old[16];
 #pragma unroll
                     for (int j = 0; j < 16; ++j) {
@@ -625,7 +569,7 @@ __device__ __forceinline__ void rank2_rank(const uint32_t (&dc)[NC], uint32_t dm
                     for (int j = 0; j < 16; ++j) {
                         if (bw + (j >> 2) < NC) {
                             const uint32_t pos2 = (old[j] >> cell_shift) & 0xffffu;      // byte offset in the list
-                            *reinterpret_cast<uint16_t *>(stage_b + min(WV_R2_ABL == 5 ? (pos2 | 0x1ffffu) : pos2, trash)) =
+                            *reinterpret_cast<uint16_t *>(stage_b + min(pos2, trash)) =
                                 (uint16_t)(first + bw * 4 + j);
                         }
                     }
@@ -710,7 +654,7 @@ int rank2_labels_prepare(const uint64_t *dblab, void *cls, int64_t N, int lwords
 }
 
 // minimum waves per SIMD the register allocation has to leave room for (the LDS footprint admits at least as many)
-constexpr int rank2_min_waves(int nc, int qb) { return nc * qb <= 8 ? 7 : (nc * qb <= 16 ? 6 : (nc * qb <= 25 ? WV_R2_W25 : (nc * qb <= 50 ? 4 : 3))); }
+constexpr int rank2_min_waves(int nc) { return nc <= 8 ? 7 : (nc <= 16 ? 6 : (nc <= 25 ? 5 : (nc <= 50 ? 4 : 3))); }
 
 // AP = true: the instantiation behind wv_hamming_map_at_k (its own kernels: the plain ranking keeps its registers)
 //
@@ -720,8 +664,10 @@ constexpr int rank2_min_waves(int nc, int qb) { return nc * qb <= 8 ? 7 : (nc * 
 // workgroups 41.0 us, 1024 workgroups x 2 queries 47.5 us, 256 x 8 96 us.  The hardware's dispatch already is that queue;
 // a query's time is a chain of latencies (12 us for a workgroup alone on its CU) that co-resident workgroups stretch to
 // ~20 us at five per CU, whatever order the phases are issued in.
-template <int WORDS, int TPQ, int NC, int QB, bool AP>
-__global__ __launch_bounds__(256, rank2_min_waves(NC, QB)) void k_rank_window(const uint64_t *__restrict__ q, const uint4 *__restrict__ img,
+// Sharing one pass over the image between several queries of a group was measured three times and lost every time (DESIGN.md
+// 4.2): what the distance pass needs is bytes in flight (latency x concurrency), not fewer loads.
+template <int WORDS, int TPQ, int NC, bool AP>
+__global__ __launch_bounds__(256, rank2_min_waves(NC)) void k_rank_window(const uint64_t *__restrict__ q, const uint4 *__restrict__ img,
                                                      int32_t *__restrict__ idx, uint16_t *__restrict__ rows16,
                                                      uint8_t *__restrict__ dist, int Q, int64_t N, int C, int nbins, int k,
                                                      int64_t idx_offset, uint32_t *__restrict__ cum, int lds_per_group, Rank2Ap apx)
@@ -729,87 +675,51 @@ __global__ __launch_bounds__(256, rank2_min_waves(NC, QB)) void k_rank_window(co
     extern __shared__ uint4 lds4[];
     constexpr int GPW = 256 / TPQ;                              // query groups per workgroup
     const int g = threadIdx.x / TPQ, t = threadIdx.x % TPQ;
-    const int q0 = (blockIdx.x * GPW + g) * QB;                 // first query of this group
-    if (q0 >= Q) return;                                         // whole waves only (TPQ == 64): no barrier is skipped
+    const int qi = blockIdx.x * GPW + g;                        // this group's query
+    if (qi >= Q) return;                                         // whole waves only (TPQ == 64): no barrier is skipped
     uint8_t *lds = reinterpret_cast<uint8_t *>(lds4) + (size_t)g * lds_per_group;
-    QCode<WORDS> qc[QB];
+    QCode<WORDS> qc;
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq) {
-        const int qi = min(q0 + qq, Q - 1);                      // tail group: recompute the last query, never store it twice
-#pragma unroll
-        for (int w = 0; w < WORDS; ++w) {
-            const uint64_t v = q[(int64_t)qi * WORDS + w];
-            // the query is uniform over its group: keep it in SGPRs
-            qc[qq].w[w] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-        }
+    for (int w = 0; w < WORDS; ++w) {
+        const uint64_t v = q[(int64_t)qi * WORDS + w];
+        // the query is uniform over its group: keep it in SGPRs
+        qc.w[w] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
     }
     if (k != 0) rank2_zero_table<TPQ>(lds, t);                  // LDS stores in the shadow of the image loads
-    uint32_t dc[QB][NC], dmin[QB];
-    rank2_distances<WORDS, TPQ, NC, QB>(img, qc, N, C, t, dc, dmin);
+    uint32_t dc[NC], dmin;
+    rank2_distances<WORDS, TPQ, NC>(img, qc, N, C, t, dc, dmin);
 #pragma unroll
-    for (int qq = 0; qq < QB; ++qq) {
-        const int qi = q0 + qq;
-        if (qi >= Q) break;                                      // uniform over the group
+    for (int once = 0; once < 1; ++once) {   // one trip: written straight-line, the compiler orders and allocates the kernel differently
         if (k == 0) {                                            // histogram only
-            rank2_hist_only<TPQ, NC>(dc[qq], N, C, nbins, cum + (int64_t)qi * (nbins + 1), lds, t);
+            rank2_hist_only<TPQ, NC>(dc, N, C, nbins, cum + (int64_t)qi * (nbins + 1), lds, t);
             continue;
         }
-        if (qq > 0) rank2_zero_table<TPQ>(lds, t);              // (the previous query's rank ended with a group barrier)
         group_sync<TPQ>();                                       // the count table is zero
-        if (WV_R2_ABL == 4 && k > 0) {                          // ablation: keep the distances alive, stop here
-            uint32_t x = dmin[qq];
-#pragma unroll
-            for (int i = 0; i < NC; ++i) x ^= dc[qq][i];
-            if (x == 0x12345678u && idx) idx[(int64_t)qi * k] = (int32_t)x;
-            continue;
-        }
         if constexpr (AP) {
             const uint64_t lw = apx.qlab[(int64_t)qi * apx.lwords], lw2 = apx.lwords > 1 ? apx.qlab[(int64_t)qi * apx.lwords + 1] : 0;
             const uint64_t ql = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lw >> 32)) << 32) |
                                 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lw);
             const uint64_t ql2 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lw2 >> 32)) << 32) |
                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lw2);
-            rank2_rank<TPQ, NC, true>(dc[qq], dmin[qq], N, C, nbins, k,
+            rank2_rank<TPQ, NC, true>(dc, dmin, N, C, nbins, k,
                                       cum ? cum + (int64_t)qi * (apx.cum_ld ? apx.cum_ld : nbins + 1) : nullptr, nullptr, lds, t,
                                       apx.cls, ql, ql2, apx.ap ? apx.ap + qi : nullptr, apx.nrel ? apx.nrel + qi : nullptr,
                                       apx.relbits ? apx.relbits + (int64_t)qi * (apx.relbits_ld ? apx.relbits_ld : (k + 63) / 64)
                                                   : nullptr);
         } else {
-            rank2_rank<TPQ, NC>(dc[qq], dmin[qq], N, C, nbins, k, cum ? cum + (int64_t)qi * (nbins + 1) : nullptr,
+            rank2_rank<TPQ, NC>(dc, dmin, N, C, nbins, k, cum ? cum + (int64_t)qi * (nbins + 1) : nullptr,
                                 dist ? dist + (int64_t)qi * k : nullptr, lds, t);
-            if (WV_R2_ABL == 0 || WV_R2_ABL == 5 || k < 0)
-                rank2_copy_list<TPQ>(lds, k, idx_offset, idx ? idx + (int64_t)qi * k : nullptr,
-                                     rows16 ? rows16 + (int64_t)qi * k : nullptr, t);
-            if (qq + 1 < QB) group_sync<TPQ>();                  // the list has left the stage before the next query fills it
+            rank2_copy_list<TPQ>(lds, k, idx_offset, idx ? idx + (int64_t)qi * k : nullptr,
+                                 rows16 ? rows16 + (int64_t)qi * k : nullptr, t);
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------ host side
-// which thread count per query a shape takes: 0 = not covered by this kernel
-int rank2_tpq(int Q, int64_t N, int k)
+int rank2_prepare(const uint64_t *db, void *img, int64_t N, int words, RankKernel kern, hipStream_t st)
 {
-    const char *force = ::wv::tune("WV_TOPK_V2");                   // "0": off, "64" / "256": pin the variant (tests, tuning)
-    if (force && force[0] == '0') return 0;
-    if (N >= 65536 || 2 * (k + 128) >= 65536) return 0;         // list cells count bytes in 16 bits
-    const bool fits256 = N <= 256 * 128 && rank2_lds_bytes_per_query<256>(k) <= 100 * 1024;
-    const bool fits64 = ceil_div(N, 64) <= 64 && 4 * rank2_lds_bytes_per_query<64>(k) <= 100 * 1024;
-    if (force && atoi(force) == 64 && fits64) return 64;        // a pinned variant that does not fit the shape is ignored
-    if (force && atoi(force) == 256 && fits256) return 256;
-    // one wave per query pays when each query has little work and there are enough queries to fill the chip
-    if (fits64 && N <= 4096 && Q >= 4096) return 64;
-    return fits256 ? 256 : (fits64 ? 64 : 0);
-}
-
-size_t rank2_image_bytes(int64_t N, int words, int tpq)
-{
-    const int64_t C = ceil_div(N, tpq), rows = words == 1 ? (C + 1) / 2 : C;
-    return (size_t)rows * tpq * 16;
-}
-
-int rank2_prepare(const uint64_t *db, void *img, int64_t N, int words, int tpq, hipStream_t st)
-{
+    const int tpq = rank_threads_per_query(kern);
     const int C = (int)ceil_div(N, tpq);
     const int64_t total = (int64_t)(words == 1 ? (C + 1) / 2 : C) * tpq;
     const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(total, 256), 4096);
@@ -821,79 +731,59 @@ int rank2_prepare(const uint64_t *db, void *img, int64_t N, int words, int tpq, 
     return WV_OK;
 }
 
-template <int WORDS, int TPQ, int NC, int QB>
-static int launch_rank2_qb(const uint64_t *q, const void *img, int32_t *idx, uint16_t *rows16, uint8_t *dist, int Q, int64_t N,
-                           int C, int nbins, int k, int64_t idx_offset, uint32_t *cum, const Rank2Ap &apx, hipStream_t st)
+namespace {
+struct WindowArgs {
+    const uint64_t *q;
+    const void *img;
+    int32_t *idx;
+    uint16_t *rows16;
+    uint8_t *dist;
+    uint32_t *cum;
+    int Q;
+    int64_t N;
+    int nbins, k;
+    int64_t idx_offset;
+    hipStream_t st;
+    bool fused;
+    Rank2Ap apx;
+};
+
+template <int WORDS, int TPQ, int NC>
+int launch_window(const RankPlan &plan, const WindowArgs &a)
 {
     constexpr int GPW = 256 / TPQ;
-    const size_t per_g = rank2_lds_bytes_per_query<TPQ>(k, (apx.ap || apx.relbits) ? rank2_bitmap_words(N) : 0);
-    size_t lds = per_g * GPW;
-    if (const char *pad = ::wv::tune("WV_R2_PAD_LDS")) lds += (size_t)atoi(pad);   // diagnostic build: fewer workgroups per CU
-    auto kern = (apx.ap || apx.relbits) ? k_rank_window<WORDS, TPQ, NC, QB, true> : k_rank_window<WORDS, TPQ, NC, QB, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) WV_FAIL(WV_EHIP, "rank_window: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
+    auto kern = a.fused ? k_rank_window<WORDS, TPQ, NC, true> : k_rank_window<WORDS, TPQ, NC, false>;
+    if (plan.lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds);
+        if (e != hipSuccess) WV_FAIL(WV_EHIP, "rank_window: hipFuncSetAttribute(%zu): %s", plan.lds, hipGetErrorString(e));
     }
-    const int64_t grid = ceil_div(Q, GPW * QB);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, q, (const uint4 *)img, idx, rows16, dist,
-                       Q, N, C, nbins, k, idx_offset, cum, (int)per_g, apx);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(a.Q, GPW)), dim3(256), plan.lds, a.st, a.q, (const uint4 *)a.img, a.idx, a.rows16,
+                       a.dist, a.Q, a.N, plan.C, a.nbins, a.k, a.idx_offset, a.cum, (int)(plan.lds / GPW), a.apx);
     WV_CHECK_LAUNCH("k_rank_window");
     return WV_OK;
 }
 
-template <int WORDS, int TPQ, int NC, int QBMAX>
-static int launch_rank2_nc(const uint64_t *q, const void *img, int32_t *idx, uint16_t *rows16, uint8_t *dist, int Q, int64_t N,
-                           int C, int nbins, int k, int64_t idx_offset, uint32_t *cum, const Rank2Ap &apx, hipStream_t st)
-{
-    // Sharing one pass over the image between QBMAX queries of a group (ranked one after the other) was measured on
-    // MI355X three times: round 2 (c1: 66 vs 50 us); round 3 with the distance pass known to be 45 % of the launch (19.6 of
-    // 43.7 us with everything after it removed) and the leaner item loops, at 168 VGPRs / 3 waves per SIMD: 62-64 vs 43-45 us,
-    // histogram-only launches 33 vs 22 us; and capped at 128 VGPRs / 4 waves per SIMD (8 queries resident per CU instead of 5):
-    // lists 47.2-47.6 vs 44.2-45.9 us, ranking + AP 63-65 vs 59.4-59.9, histogram-only 22.3 vs 22.6 -- half the loads in the
-    // same time.  What the distance pass needs is bytes in flight (latency x concurrency), not fewer loads.  The kernel keeps
-    // the template parameter; only QB = 1 is instantiated.
-    (void)QBMAX;
-    return launch_rank2_qb<WORDS, TPQ, NC, 1>(q, img, idx, rows16, dist, Q, N, C, nbins, k, idx_offset, cum, apx, st);
-}
-
+// the instantiation for the plan's NC bucket (one wave per query: C <= 64, so NC <= 16)
 template <int WORDS, int TPQ>
-static int launch_rank2_t(const uint64_t *q, const void *img, int32_t *idx, uint16_t *rows16, uint8_t *dist, int Q, int64_t N,
-                          int nbins, int k, int64_t idx_offset, uint32_t *cum, const Rank2Ap &apx, hipStream_t st)
+int launch_window_nc(const RankPlan &plan, const WindowArgs &a)
 {
-    const int C = (int)ceil_div(N, TPQ);
-#define WV_R2(NCW, QBM) return launch_rank2_nc<WORDS, TPQ, NCW, QBM>(q, img, idx, rows16, dist, Q, N, C, nbins, k, idx_offset, cum, apx, st)
-    if (C <= 16) WV_R2(4, 8);
-    if (C <= 32) WV_R2(8, 4);
-    if (C <= 64) WV_R2(16, 2);
+    if (plan.NC == 4) return launch_window<WORDS, TPQ, 4>(plan, a);
+    if (plan.NC == 8) return launch_window<WORDS, TPQ, 8>(plan, a);
     if constexpr (TPQ == 256) {
-        if (C <= 100) WV_R2(25, 2);
-        WV_R2(32, 2);
-    } else {
-        return 1;                                                // one wave per query is for short rows only
+        if (plan.NC == 25) return launch_window<WORDS, TPQ, 25>(plan, a);
+        if (plan.NC == 32) return launch_window<WORDS, TPQ, 32>(plan, a);
     }
-#undef WV_R2
+    return launch_window<WORDS, TPQ, 16>(plan, a);
 }
+}  // namespace
 
-// img must be the image for `tpq` threads per query (rank2_prepare)
-// idx (int32 global indices) or rows16 (16-bit local row numbers) receives the list; k == 0: histogram only
-int rank2_launch(const uint64_t *q, const void *img, int32_t *idx, uint16_t *rows16, uint8_t *dist, int Q, int64_t N, int nbits,
-                 int k, int64_t idx_offset, uint32_t *cum, int tpq, hipStream_t st, const void *lab_img, const uint64_t *qlab,
-                 float *ap, int32_t *nrel, uint64_t *relbits, int64_t relbits_ld, int64_t cum_ld, int lwords)
+int rank2_launch(const RankPlan &plan, const uint64_t *q, const void *img, int32_t *idx, uint16_t *rows16, uint8_t *dist,
+                 uint32_t *cum, int Q, int64_t N, int nbits, int k, int64_t idx_offset, hipStream_t st, const Rank2Ap *apx)
 {
-    const int nbins = nbits + 1, words = (nbits + 63) / 64;
-    Rank2Ap apx{reinterpret_cast<const uint32_t *>(lab_img), qlab, lwords, ap, nrel, relbits, relbits_ld, cum_ld};
-    if (ap || relbits) {
-        if (!lab_img || !qlab || k < 1 || lwords < 1 || lwords > 2) return 1;
-        const size_t per_g = tpq == 64 ? 4 * rank2_lds_bytes_per_query<64>(k, rank2_bitmap_words(N))
-                                       : rank2_lds_bytes_per_query<256>(k, rank2_bitmap_words(N));
-        if (per_g > 100 * 1024) return 1;
-    }
-    if (words == 1) {
-        if (tpq == 64) return launch_rank2_t<1, 64>(q, img, idx, rows16, dist, Q, N, nbins, k, idx_offset, cum, apx, st);
-        return launch_rank2_t<1, 256>(q, img, idx, rows16, dist, Q, N, nbins, k, idx_offset, cum, apx, st);
-    }
-    if (tpq == 64) return launch_rank2_t<2, 64>(q, img, idx, rows16, dist, Q, N, nbins, k, idx_offset, cum, apx, st);
-    return launch_rank2_t<2, 256>(q, img, idx, rows16, dist, Q, N, nbins, k, idx_offset, cum, apx, st);
+    const WindowArgs a{q, img, idx, rows16, dist, cum, Q, N, nbits + 1, k, idx_offset, st, apx != nullptr, apx ? *apx : Rank2Ap{}};
+    const bool wave = plan.kernel == RankKernel::window64;
+    if (nbits <= 64) return wave ? launch_window_nc<1, 64>(plan, a) : launch_window_nc<1, 256>(plan, a);
+    return wave ? launch_window_nc<2, 64>(plan, a) : launch_window_nc<2, 256>(plan, a);
 }
 
 }  // namespace wv

@@ -14,38 +14,14 @@
 // database is pre-transposed once per call into dbT[r][t] = code[t*C + r] so that the
 // per-thread contiguous ranges are read with fully coalesced loads.  The distance row is not
 // scattered at all: it is regenerated from the bin boundaries (sorted => run-length).
-#include "common.hpp"
+//
+// This is the column kernel: it takes any N and any k.  Databases (shards) of at most 32,768 rows go to the windowed
+// kernel (rank2.hip); rank_plan() (rank.hpp) decides which.  The file also holds the ranking entry points, the merges
+// of sorted shard lists and the AP kernels over written lists.
+#include "rank.hpp"
 #include "ap_walk.hpp"
-#include <type_traits>
 
 namespace wv {
-
-constexpr int kTopkThreads = 256;
-
-// second-generation kernel (rank2.hip): windowed count table, branch-free, LDS-assembled list
-int rank2_tpq(int Q, int64_t N, int k);
-size_t rank2_image_bytes(int64_t N, int words, int tpq);
-int rank2_prepare(const uint64_t *db, void *img, int64_t N, int words, int tpq, hipStream_t st);
-size_t rank2_labels_bytes(int64_t N, int lwords);
-int rank2_labels_prepare(const uint64_t *dblab, void *cls, int64_t N, int lwords, hipStream_t st);
-// lab_img (the class-major label bit matrix) / qlab / ap / nrel: average precision of the list (wv_hamming_map_at_k); all NULL otherwise
-int rank2_launch(const uint64_t *q, const void *img, int32_t *idx, uint16_t *rows16, uint8_t *dist, int Q, int64_t N, int nbits,
-                 int k, int64_t idx_offset, uint32_t *cum, int tpq, hipStream_t st, const void *lab_img = nullptr,
-                 const uint64_t *qlab = nullptr, float *ap = nullptr, int32_t *nrel = nullptr, uint64_t *relbits = nullptr,
-                 int64_t relbits_ld = 0, int64_t cum_ld = 0, int lwords = 1);
-// the one-wave-per-query image exists for databases (shards) of at most this many rows
-constexpr int64_t kImg64MaxRows = 64 * 64;
-// images of the windowed kernel exist for databases it can take at all (16-bit item numbers, <= 128 items per thread)
-constexpr int64_t kImg256MaxRows = 256 * 128;
-// prepared ranking blob: [first-generation column image][windowed kernel, 256 threads/query][.., 64 threads/query]
-static inline size_t old_image_bytes(int64_t N, int words) { return (size_t)ceil_div(N, kTopkThreads) * kTopkThreads * words * sizeof(uint64_t); }
-static inline size_t r2_off256(int64_t N, int words) { return (size_t)align_up((int64_t)old_image_bytes(N, words), 256); }
-static inline size_t r2_off64(int64_t N, int words)
-{
-    return r2_off256(N, words) + (N <= kImg256MaxRows ? (size_t)align_up((int64_t)rank2_image_bytes(N, words, 256), 256) : 0);
-}
-__device__ int g_topk_dbg = 0;   // WV_TOPK_DBG (timing experiments only): 1 = no list stores, 2 = skip phase 2, 4 = skip phase 1
-constexpr int kMaxBins = 130;  // nbits <= 128 (+1 bin for the padding value of ragged shard lists)
 
 // ------------------------------------------------------------------------ item sources
 // CodeSource: items are database codes, distance = popcount(q ^ code), id = row + offset
@@ -91,6 +67,19 @@ struct RowSource {
     __device__ __forceinline__ int32_t id(int64_t item) const { return (int32_t)item; }
 };
 
+// Exclusive scan over the bins of per-bin totals held 3 bins per lane of one wave (lane l: bins 3l .. 3l + 2; 192 >=
+// kMaxBins): base[b] = sum of the bins below b.  Returns the sum of the bins below the lane's first.
+__device__ __forceinline__ uint32_t bin_scan3(const uint32_t (&t)[3], int nbins, uint32_t *base, int lane)
+{
+    const int b0 = 3 * lane;
+    const uint32_t incl = wave_incl_scan_u32(t[0] + t[1] + t[2]);
+    const uint32_t excl = incl - (t[0] + t[1] + t[2]);
+    if (b0 < nbins) base[b0] = excl;
+    if (b0 + 1 < nbins) base[b0 + 1] = excl + t[0];
+    if (b0 + 2 < nbins) base[b0 + 2] = excl + t[0] + t[1];
+    return excl;
+}
+
 // ------------------------------------------------------------------------ the ranking core
 // LDS: hist[nbins][256] (u32, or u16 pairs when n_items < 65536), tot[kMaxBins], base[kMaxBins + 1], misc
 //
@@ -133,9 +122,10 @@ struct Hist {
     static __host__ __device__ size_t words(int nbins) { return (size_t)nbins * (U16 ? kTopkThreads / 2 : kTopkThreads); }
 };
 
-// STAGED: the ranked indices are first placed in an LDS row (scattered 4-byte LDS writes), then copied out
-// with 16-byte coalesced stores -- instead of k scattered 4-byte global stores per query.
-template <typename Source, bool U16, bool STAGED>
+// The ranked indices leave with k scattered 4-byte global stores per query.  Placing them in an LDS row first and copying
+// it out with 16-byte coalesced stores was measured on MI355X (c1 shape): it costs a resident workgroup per CU (53 KB vs
+// 34 KB of LDS) and ran 163 us vs 117 us -- the kernel is latency-bound, so occupancy wins -- and was removed.
+template <typename Source, bool U16>
 __device__ __forceinline__ void rank_one_query(const Source &src, int64_t n_items, int C, int nbins,
                                                int k, int32_t *__restrict__ idx_out,
                                                uint8_t *__restrict__ dist_out, uint32_t *lds,
@@ -145,8 +135,6 @@ __device__ __forceinline__ void rank_one_query(const Source &src, int64_t n_item
     uint32_t *tot = lds + Hist<U16>::words(nbins);     // kMaxBins
     uint32_t *base = tot + kMaxBins;                   // kMaxBins + 1
     uint32_t *misc = base + kMaxBins + 1;              // [0] = threshold bin T
-    // staging row, 16-byte aligned: starts at the rounded-down word count used by rank_lds_bytes()
-    int32_t *stage = reinterpret_cast<int32_t *>(lds + (Hist<U16>::words(nbins) + kMaxBins + kMaxBins + 1 + 4 + 3) / 4 * 4);
     const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
 
     {   // zero the table with 16-byte stores
@@ -164,36 +152,33 @@ __device__ __forceinline__ void rank_one_query(const Source &src, int64_t n_item
     constexpr int UNR = 16;
     using Raw = typename Source::Raw;
     const int nfull = C / UNR;
-    const int dbg = g_topk_dbg;
     // Columns of at most kCacheItems items keep their distances (one byte each) in registers between the
     // two phases, so phase 2 neither reloads the codes nor recomputes the popcounts.
     constexpr int kCacheItems = 128, kCacheBatches = kCacheItems / UNR;
     const bool cached = C <= kCacheItems;            // uniform
     uint32_t dcache[kCacheItems / 4];
     if (cached) {
-        if (!(dbg & 4)) {
 #pragma unroll
-            for (int bi = 0; bi < kCacheBatches; ++bi) {
-                if (bi * UNR < C) {                   // uniform
-                    Raw cur[UNR];
+        for (int bi = 0; bi < kCacheBatches; ++bi) {
+            if (bi * UNR < C) {                       // uniform
+                Raw cur[UNR];
 #pragma unroll
-                    for (int u = 0; u < UNR; ++u) cur[u] = src.fetch(min(bi * UNR + u, C - 1), tid, first + bi * UNR + u);
+                for (int u = 0; u < UNR; ++u) cur[u] = src.fetch(min(bi * UNR + u, C - 1), tid, first + bi * UNR + u);
 #pragma unroll
-                    for (int u4 = 0; u4 < UNR / 4; ++u4) {
-                        uint32_t word = 0;
+                for (int u4 = 0; u4 < UNR / 4; ++u4) {
+                    uint32_t word = 0;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int u = 4 * u4 + j;
-                            const int d = src.dist(cur[u]);
-                            word |= (uint32_t)d << (8 * j);
-                            if (bi * UNR + u < nvalid) hist.add(d, tid);
-                        }
-                        dcache[bi * (UNR / 4) + u4] = word;
+                    for (int j = 0; j < 4; ++j) {
+                        const int u = 4 * u4 + j;
+                        const int d = src.dist(cur[u]);
+                        word |= (uint32_t)d << (8 * j);
+                        if (bi * UNR + u < nvalid) hist.add(d, tid);
                     }
+                    dcache[bi * (UNR / 4) + u4] = word;
                 }
             }
         }
-    } else if (!(dbg & 4)) {
+    } else {
         Raw cur[UNR], nxt[UNR];
         if (nfull > 0) {
 #pragma unroll
@@ -225,16 +210,10 @@ __device__ __forceinline__ void rank_one_query(const Source &src, int64_t n_item
 
     // ---- exclusive scan over bins (wave 0; up to 3 bins per lane covers 192 >= 130 bins)
     if (wv == 0) {
-        uint32_t t0 = 0, t1 = 0, t2 = 0;
         const int b0 = 3 * lane;
-        if (b0 < nbins) t0 = tot[b0];
-        if (b0 + 1 < nbins) t1 = tot[b0 + 1];
-        if (b0 + 2 < nbins) t2 = tot[b0 + 2];
-        const uint32_t incl = wave_incl_scan_u32(t0 + t1 + t2);
-        const uint32_t excl = incl - (t0 + t1 + t2);
-        if (b0 < nbins) base[b0] = excl;
-        if (b0 + 1 < nbins) base[b0 + 1] = excl + t0;
-        if (b0 + 2 < nbins) base[b0 + 2] = excl + t0 + t1;
+        const uint32_t t[3] = {b0 < nbins ? tot[b0] : 0u, b0 + 1 < nbins ? tot[b0 + 1] : 0u, b0 + 2 < nbins ? tot[b0 + 2] : 0u};
+        const uint32_t t0 = t[0], t1 = t[1], t2 = t[2];
+        const uint32_t excl = bin_scan3(t, nbins, base, lane), incl = excl + t0 + t1 + t2;
         if (lane == 63) base[nbins] = incl;  // = n_items
         // threshold bin: first bin whose inclusive count reaches k
         int cand = nbins;  // sentinel
@@ -267,28 +246,27 @@ __device__ __forceinline__ void rank_one_query(const Source &src, int64_t n_item
     __syncthreads();
 
     // ---- phase 2: stable placement of the items in bins <= T (returning LDS adds, UNR in flight)
+    // `store` is always true (every caller has checked k >= 1 on the host), and uniform.  ANDed into the store conditions it keeps each batch's sixteen stores one chain of
+    // skip-branches; without it the compiler duplicates the chain into a taken and a skipped copy (measured: c3 shard + 1 %),
+    // and with a likely-hint in its place shards ranked at k = N ran 10 % slower.
+    const bool store = k > 0;
     if (cached) {
-        if (!(dbg & 2)) {
 #pragma unroll
-            for (int bi = 0; bi < kCacheBatches; ++bi) {
-                if (bi * UNR < C) {
-                    uint32_t pos[UNR];
+        for (int bi = 0; bi < kCacheBatches; ++bi) {
+            if (bi * UNR < C) {
+                uint32_t pos[UNR];
 #pragma unroll
-                    for (int u = 0; u < UNR; ++u) {
-                        const int d = (dcache[bi * (UNR / 4) + u / 4] >> (8 * (u & 3))) & 0xff;
-                        pos[u] = 0xffffffffu;
-                        if (bi * UNR + u < nvalid && d <= T) pos[u] = hist.fetch_inc(d, tid);
-                    }
-#pragma unroll
-                    for (int u = 0; u < UNR; ++u)
-                        if (pos[u] < (uint32_t)k && !(dbg & 1)) {
-                            if (STAGED) stage[pos[u]] = src.id(first + bi * UNR + u);
-                            else idx_out[pos[u]] = src.id(first + bi * UNR + u);
-                        }
+                for (int u = 0; u < UNR; ++u) {
+                    const int d = (dcache[bi * (UNR / 4) + u / 4] >> (8 * (u & 3))) & 0xff;
+                    pos[u] = 0xffffffffu;
+                    if (bi * UNR + u < nvalid && d <= T) pos[u] = hist.fetch_inc(d, tid);
                 }
+#pragma unroll
+                for (int u = 0; u < UNR; ++u)
+                    if (pos[u] < (uint32_t)k && store) idx_out[pos[u]] = src.id(first + bi * UNR + u);
             }
         }
-    } else if (!(dbg & 2)) {
+    } else {
         Raw cur[UNR], nxt[UNR];
         if (nfull > 0) {
 #pragma unroll
@@ -309,10 +287,7 @@ __device__ __forceinline__ void rank_one_query(const Source &src, int64_t n_item
             }
 #pragma unroll
             for (int u = 0; u < UNR; ++u)
-                if (pos[u] < (uint32_t)k && !(dbg & 1)) {
-                    if (STAGED) stage[pos[u]] = src.id(first + r + u);
-                    else idx_out[pos[u]] = src.id(first + r + u);
-                }
+                if (pos[u] < (uint32_t)k && store) idx_out[pos[u]] = src.id(first + r + u);
 #pragma unroll
             for (int u = 0; u < UNR; ++u) cur[u] = nxt[u];
         }
@@ -321,21 +296,8 @@ __device__ __forceinline__ void rank_one_query(const Source &src, int64_t n_item
             const int d = src.dist(src.fetch(r, tid, item));
             if (d <= T) {
                 const uint32_t pos = hist.fetch_inc(d, tid);
-                if (pos < (uint32_t)k && !(dbg & 1)) {
-                    if (STAGED) stage[pos] = src.id(item);
-                    else idx_out[pos] = src.id(item);
-                }
+                if (pos < (uint32_t)k && store) idx_out[pos] = src.id(item);
             }
-        }
-    }
-    if (STAGED) {   // coalesced copy-out of the ranked row
-        __syncthreads();
-        if ((k & 3) == 0 && (reinterpret_cast<uintptr_t>(idx_out) & 15) == 0) {
-            const int4 *s4 = reinterpret_cast<const int4 *>(stage);
-            int4 *o4 = reinterpret_cast<int4 *>(idx_out);
-            for (int i = tid; i < k / 4; i += kTopkThreads) o4[i] = s4[i];
-        } else {
-            for (int i = tid; i < k; i += kTopkThreads) idx_out[i] = stage[i];
         }
     }
 
@@ -373,26 +335,6 @@ __device__ __forceinline__ void rank_one_query(const Source &src, int64_t n_item
     }
 }
 
-constexpr int kStageMaxK = 8192;   // ranked rows up to this length are staged in LDS (32 KB)
-static inline size_t rank_fixed_words(int nbins, bool u16)
-{
-    const size_t h = (size_t)nbins * (u16 ? kTopkThreads / 2 : kTopkThreads);
-    return (h + kMaxBins + kMaxBins + 1 + 4 + 3) / 4 * 4;   // 16-byte aligned start of the staging row
-}
-// Measured on MI355X (c1 shape): staging costs a resident workgroup per CU (53 KB vs 34 KB of LDS) and
-// runs 163 us vs 117 us with direct scattered stores -- the kernel is latency-bound, so occupancy wins.
-// Kept selectable (WV_TOPK_STAGE=1) for shapes where the table is small.
-static inline bool rank_staged(int k, int nbins, bool u16)
-{
-    static const bool enabled = ::wv::tune("WV_TOPK_STAGE") && ::wv::tune("WV_TOPK_STAGE")[0] == '1';
-    return enabled && k <= kStageMaxK && (rank_fixed_words(nbins, u16) + (size_t)k + 4) * 4 <= (size_t)kMaxLdsBytes - 4096;
-}
-static inline size_t rank_lds_bytes(int nbins, bool u16, int k)
-{
-    return (rank_fixed_words(nbins, u16) + (rank_staged(k, nbins, u16) ? (size_t)(k + 3) / 4 * 4 : 0)) * sizeof(uint32_t);
-}
-static inline bool rank_u16(int64_t n_items) { return n_items < 65536; }
-
 // ------------------------------------------------------------------------ kernels
 template <int WORDS>
 __global__ __launch_bounds__(kTopkThreads) void k_transpose_db(const uint64_t *__restrict__ db,
@@ -410,7 +352,7 @@ __global__ __launch_bounds__(kTopkThreads) void k_transpose_db(const uint64_t *_
     }
 }
 
-template <int WORDS, bool U16, bool STAGED>
+template <int WORDS, bool U16>
 __global__ __launch_bounds__(kTopkThreads) void k_hamming_topk(const uint64_t *__restrict__ q,
                                                                const uint64_t *__restrict__ dbT,
                                                                int32_t *__restrict__ idx,
@@ -425,12 +367,12 @@ __global__ __launch_bounds__(kTopkThreads) void k_hamming_topk(const uint64_t *_
     src.idx_offset = idx_offset;
 #pragma unroll
     for (int w = 0; w < WORDS; ++w) src.qw[w] = q[(int64_t)qi * WORDS + w];
-    rank_one_query<CodeSource<WORDS>, U16, STAGED>(src, N, C, nbins, k, idx + (int64_t)qi * k,
+    rank_one_query<CodeSource<WORDS>, U16>(src, N, C, nbins, k, idx + (int64_t)qi * k,
                                            dist ? dist + (int64_t)qi * k : nullptr, reinterpret_cast<uint32_t *>(lds4),
                                            cum ? cum + (int64_t)qi * (nbins + 1) : nullptr);
 }
 
-template <bool U16, bool STAGED>
+template <bool U16>
 __global__ __launch_bounds__(kTopkThreads) void k_rank_from_dist(const uint8_t *__restrict__ dmat,
                                                                  int64_t ld, int64_t N,
                                                                  int32_t *__restrict__ idx,
@@ -442,11 +384,48 @@ __global__ __launch_bounds__(kTopkThreads) void k_rank_from_dist(const uint8_t *
     RowSource src;
     src.row = dmat + (int64_t)qi * ld;
     src.n = N;
-    rank_one_query<RowSource, U16, STAGED>(src, N, C, nbins, k, idx + (int64_t)qi * k, dist ? dist + (int64_t)qi * k : nullptr,
+    rank_one_query<RowSource, U16>(src, N, C, nbins, k, idx + (int64_t)qi * k, dist ? dist + (int64_t)qi * k : nullptr,
                                    reinterpret_cast<uint32_t *>(lds4));
 }
 
 // ------------------------------------------------------------------------ merge of sorted shard lists
+// Steps the three merge kernels share.  start[g][b] ([G][nbins + 1]) = first position of shard g's list with distance >= b.
+
+// start[] from the shards' cumulative histograms (cum_ld: their row pitch in uint32): run boundaries are min(cum[b], kin)
+__device__ __forceinline__ void merge_starts_from_cum(const uint32_t *__restrict__ cum, int64_t cum_ld, int G, int Q, int qi, int kin,
+                                                      int nbins, int32_t *start, int tid)
+{
+    for (int u = tid; u < G * (nbins + 1); u += 256) {
+        const int g = u / (nbins + 1), b = u - g * (nbins + 1);
+        start[u] = (int32_t)min(cum[((int64_t)g * Q + qi) * cum_ld + b], (uint32_t)kin);
+    }
+}
+
+// one wave: base[b] = entries of all shards with distance < b (totals per bin, then their exclusive scan)
+__device__ __forceinline__ void merge_bin_bases(const int32_t *start, int G, int nbins, uint32_t *base, int lane)
+{
+    uint32_t t[3] = {0, 0, 0};
+    const int b0 = 3 * lane;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        if (b0 + j < nbins)
+            for (int g = 0; g < G; ++g) t[j] += (uint32_t)(start[g * (nbins + 1) + b0 + j + 1] - start[g * (nbins + 1) + b0 + j]);
+    bin_scan3(t, nbins, base, lane);
+}
+
+// delta[g][b] ([G][nbins]): entry p of shard g, distance b, goes to output position p + delta[g][b]
+__device__ __forceinline__ void merge_deltas(const int32_t *start, const uint32_t *base, int G, int nbins, int32_t *delta, int tid)
+{
+    for (int b = tid; b < nbins; b += 256) {
+        uint32_t run = base[b];
+        for (int g = 0; g < G; ++g) {
+            const int s0 = start[g * (nbins + 1) + b], s1 = start[g * (nbins + 1) + b + 1];
+            delta[g * nbins + b] = (int32_t)run - s0;
+            run += (uint32_t)(s1 - s0);
+        }
+    }
+}
+
 // The G input lists of a query are each sorted by (distance, index) and come from contiguous row shards in
 // rank order, so the merged order is: by distance bin, then by shard, then by position inside the shard's
 // run of that distance.  Run boundaries come from binary searches on the sorted distance rows (no per-item
@@ -478,28 +457,9 @@ __global__ __launch_bounds__(256) void k_merge_sorted(const int32_t *__restrict_
         start[u] = lo;
     }
     __syncthreads();
-    if (wv == 0) {   // totals per bin and their exclusive scan (up to 3 bins per lane)
-        uint32_t t[3] = {0, 0, 0};
-        const int b0 = 3 * lane;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (b0 + j < nbins)
-                for (int g = 0; g < G; ++g) t[j] += (uint32_t)(start[g * (nbins + 1) + b0 + j + 1] - start[g * (nbins + 1) + b0 + j]);
-        const uint32_t incl = wave_incl_scan_u32(t[0] + t[1] + t[2]);
-        const uint32_t excl = incl - (t[0] + t[1] + t[2]);
-        if (b0 < nbins) base[b0] = excl;
-        if (b0 + 1 < nbins) base[b0 + 1] = excl + t[0];
-        if (b0 + 2 < nbins) base[b0 + 2] = excl + t[0] + t[1];
-    }
+    if (wv == 0) merge_bin_bases(start, G, nbins, base, lane);
     __syncthreads();
-    for (int b = tid; b < nbins; b += 256) {
-        uint32_t run = base[b];
-        for (int g = 0; g < G; ++g) {
-            const int s0 = start[g * (nbins + 1) + b], s1 = start[g * (nbins + 1) + b + 1];
-            delta[g * nbins + b] = (int32_t)run - s0;
-            run += (uint32_t)(s1 - s0);
-        }
-    }
+    merge_deltas(start, base, G, nbins, delta, tid);
     __syncthreads();
     for (int g = 0; g < G; ++g) {
         const uint8_t *row = dq + g * shard_stride;
@@ -654,34 +614,12 @@ __global__ __launch_bounds__(256) void k_merge_cum(const uint16_t *__restrict__ 
     int32_t *delta = start + G * (nbins + 1);                     // [G][nbins]
     uint32_t *base = reinterpret_cast<uint32_t *>(delta + G * nbins);   // [nbins + 1]
     const int qi = blockIdx.x, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
-    for (int u = tid; u < G * (nbins + 1); u += 256) {
-        const int g = u / (nbins + 1), b = u - g * (nbins + 1);
-        start[u] = (int32_t)min(cum[((int64_t)g * Q + qi) * (nbins + 1) + b], (uint32_t)kin);
-    }
+    merge_starts_from_cum(cum, nbins + 1, G, Q, qi, kin, nbins, start, tid);
     __syncthreads();
     if (need_out && wv == 1) merge_report_need(cum, nbins + 1, G, Q, qi, nbins, k, need_out, lane);
-    if (wv == 0) {   // totals per bin and their exclusive scan (up to 3 bins per lane)
-        uint32_t t[3] = {0, 0, 0};
-        const int b0 = 3 * lane;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (b0 + j < nbins)
-                for (int g = 0; g < G; ++g) t[j] += (uint32_t)(start[g * (nbins + 1) + b0 + j + 1] - start[g * (nbins + 1) + b0 + j]);
-        const uint32_t incl = wave_incl_scan_u32(t[0] + t[1] + t[2]);
-        const uint32_t excl = incl - (t[0] + t[1] + t[2]);
-        if (b0 < nbins) base[b0] = excl;
-        if (b0 + 1 < nbins) base[b0 + 1] = excl + t[0];
-        if (b0 + 2 < nbins) base[b0 + 2] = excl + t[0] + t[1];
-    }
+    if (wv == 0) merge_bin_bases(start, G, nbins, base, lane);
     __syncthreads();
-    for (int b = tid; b < nbins; b += 256) {
-        uint32_t run = base[b];
-        for (int g = 0; g < G; ++g) {
-            const int s0 = start[g * (nbins + 1) + b], s1 = start[g * (nbins + 1) + b + 1];
-            delta[g * nbins + b] = (int32_t)run - s0;
-            run += (uint32_t)(s1 - s0);
-        }
-    }
+    merge_deltas(start, base, G, nbins, delta, tid);
     __syncthreads();
     for (int g = 0; g < G; ++g) {
         const uint16_t *irow = idx_local + ((int64_t)g * Q + qi) * kin;
@@ -712,14 +650,6 @@ static int set_lds_attr(const void *fn, size_t bytes, const char *what)
     return WV_OK;
 }
 
-// calls f(std::bool_constant<U16>, std::bool_constant<STAGED>) for the runtime pair
-template <typename F>
-static int dispatch_rank(bool u16, bool staged, F f)
-{
-    if (u16) return staged ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
-    return staged ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
-}
-
 template <int WORDS>
 static int launch_transpose(const uint64_t *db, uint64_t *dbT, int64_t N, hipStream_t st)
 {
@@ -731,63 +661,81 @@ static int launch_transpose(const uint64_t *db, uint64_t *dbT, int64_t N, hipStr
     return WV_OK;
 }
 
-// dbT == nullptr: build the column image into `ws` first (one extra small launch per call)
-template <int WORDS>
-static int launch_topk(const uint64_t *q, const uint64_t *db, const uint64_t *dbT_ready, int32_t *idx, uint8_t *dist,
-                       int Q, int64_t N, int nbits, int k, int64_t idx_offset, void *ws, hipStream_t st,
-                       uint32_t *cum = nullptr)
+// The image the plan's kernel reads: inside the prepared blob, or built into the workspace first (one extra small launch
+// per call).
+static int rank_image(const RankPlan &plan, const uint64_t *db, const void *prepared, void *ws, int64_t N, int words,
+                      hipStream_t st, const void **img)
 {
-    const int C = (int)ceil_div(N, kTopkThreads);
-    const int nbins = nbits + 1;
-    const uint64_t *dbT = dbT_ready;
-    if (const int tpq = rank2_tpq(Q, N, k)) {
-        const void *img = nullptr;
-        if (dbT_ready) {
-            img = (const char *)dbT_ready + (tpq == 256 ? r2_off256(N, WORDS) : r2_off64(N, WORDS));
-        } else {
-            int rc0 = rank2_prepare(db, ws, N, WORDS, tpq, st);
-            if (rc0) return rc0;
-            img = ws;
-        }
-        const int rc2 = rank2_launch(q, img, idx, nullptr, dist, Q, N, nbits, k, idx_offset, cum, tpq, st);
-        if (rc2 <= 0) return rc2;                                // 1 = shape not covered after all: first-generation kernel
+    if (prepared) {
+        *img = blob_image(prepared, N, words, plan.kernel);
+        return WV_OK;
     }
-    if (!dbT) {
-        int rc0 = launch_transpose<WORDS>(db, (uint64_t *)ws, N, st);
-        if (rc0) return rc0;
-        dbT = (const uint64_t *)ws;
-    }
-    const bool u16 = rank_u16(N), staged = rank_staged(k, nbins, u16);
-    const size_t lds = rank_lds_bytes(nbins, u16, k);
-    if (const char *e = ::wv::tune("WV_TOPK_DBG")) {
-        const int v = atoi(e);
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_topk_dbg), &v, sizeof(int));
-    }
-    int rc = dispatch_rank(u16, staged, [&](auto U, auto S) {
-        auto kern = k_hamming_topk<WORDS, decltype(U)::value, decltype(S)::value>;
-        int r0 = set_lds_attr(reinterpret_cast<const void *>(kern), lds, "hamming_topk");
-        if (r0) return r0;
-        hipLaunchKernelGGL(kern, dim3(Q), dim3(kTopkThreads), lds, st, q, dbT, idx, dist, N, C, nbins, k, idx_offset, cum);
-        return (int)WV_OK;
-    });
+    *img = ws;
+    if (plan.kernel != RankKernel::column) return rank2_prepare(db, ws, N, words, plan.kernel, st);
+    return words == 1 ? launch_transpose<1>(db, (uint64_t *)ws, N, st) : launch_transpose<2>(db, (uint64_t *)ws, N, st);
+}
+
+template <int WORDS>
+static int launch_column(const RankPlan &plan, const uint64_t *q, const void *img, int32_t *idx, uint8_t *dist, int Q, int64_t N,
+                         int nbits, int k, int64_t idx_offset, uint32_t *cum, hipStream_t st)
+{
+    auto kern = column_u16(N) ? k_hamming_topk<WORDS, true> : k_hamming_topk<WORDS, false>;
+    int rc = set_lds_attr(reinterpret_cast<const void *>(kern), plan.lds, "hamming_topk");
     if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3(Q), dim3(kTopkThreads), plan.lds, st, q, (const uint64_t *)img, idx, dist, N, plan.C, nbits + 1, k,
+                       idx_offset, cum);
     WV_CHECK_LAUNCH("k_hamming_topk");
     return WV_OK;
 }
 
-size_t topk_prepared_bytes(int64_t N, int words)
+// int32 lists (+ distance rows, + histograms) from the codes: wv_hamming_topk / _prepared / _ex
+static int launch_topk(const uint64_t *q, const uint64_t *db, const void *prepared, int32_t *idx, uint8_t *dist, int Q, int64_t N,
+                       int nbits, int k, int64_t idx_offset, void *ws, hipStream_t st, uint32_t *cum = nullptr)
 {
-    size_t b = r2_off64(N, words);
-    if (N <= kImg64MaxRows) b += rank2_image_bytes(N, words, 64);
-    return b;
+    const RankPlan plan = rank_plan(Q, N, nbits, k, RankMode::lists);
+    const void *img = nullptr;
+    int rc = rank_image(plan, db, prepared, ws, N, (nbits + 63) / 64, st, &img);
+    if (rc) return rc;
+    if (plan.kernel != RankKernel::column) return rank2_launch(plan, q, img, idx, nullptr, dist, cum, Q, N, nbits, k, idx_offset, st);
+    if (nbits <= 64) return launch_column<1>(plan, q, img, idx, dist, Q, N, nbits, k, idx_offset, cum, st);
+    return launch_column<2>(plan, q, img, idx, dist, Q, N, nbits, k, idx_offset, cum, st);
 }
 
-int topk_prepare(const uint64_t *db, void *dbT, int64_t N, int words, hipStream_t st)
+static int require_nbits(const char *what, int nbits)
 {
-    int rc = words == 1 ? launch_transpose<1>(db, (uint64_t *)dbT, N, st) : launch_transpose<2>(db, (uint64_t *)dbT, N, st);
-    if (!rc && N <= kImg256MaxRows) rc = rank2_prepare(db, (char *)dbT + r2_off256(N, words), N, words, 256, st);
-    if (!rc && N <= kImg64MaxRows) rc = rank2_prepare(db, (char *)dbT + r2_off64(N, words), N, words, 64, st);
-    return rc;
+    WV_REQUIRE(nbits >= 1 && nbits <= 128, "%s: nbits=%d (supported: 1..128)", what, nbits);
+    return WV_OK;
+}
+
+// The argument checks the ranking entry points share: buffers, shape and code width (all a call without k needs) ...
+static int validate_rank_shape(const char *what, bool buffers, int Q, int64_t N, int nbits)
+{
+    WV_REQUIRE(buffers, "%s: null buffer", what);
+    WV_REQUIRE(Q >= 0 && N >= 1, "%s: bad shape Q=%d N=%lld", what, Q, (long long)N);
+    return require_nbits(what, nbits);
+}
+
+// ... and the list length
+static int validate_rank_args(const char *what, bool buffers, int Q, int64_t N, int nbits, int k)
+{
+    if (int rc = validate_rank_shape(what, buffers, Q, N, nbits)) return rc;
+    WV_REQUIRE(k >= 1 && k <= N, "%s: k=%d must be in [1, N=%lld] (torch.topk raises too)", what, k, (long long)N);
+    return WV_OK;
+}
+
+// ... and of those that return global row numbers as int32
+static int validate_rank_ids(const char *what, bool buffers, int Q, int64_t N, int nbits, int k, int64_t idx_offset)
+{
+    if (int rc = validate_rank_args(what, buffers, Q, N, nbits, k)) return rc;
+    WV_REQUIRE(N + idx_offset <= 0x7fffffffLL && idx_offset >= 0, "%s: indices exceed int32", what);
+    return WV_OK;
+}
+
+static int require_workspace(const char *what, const void *workspace, size_t workspace_bytes, int Q, int64_t N, int nbits, int k)
+{
+    const size_t need = wv_hamming_topk_workspace_bytes(Q, N, (nbits + 63) / 64, k);
+    if (!workspace || workspace_bytes < need) WV_FAIL(WV_ENOMEM, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    return WV_OK;
 }
 
 }  // namespace wv
@@ -796,36 +744,26 @@ using namespace wv;
 
 extern "C" size_t wv_hamming_topk_workspace_bytes(int Q, int64_t N, int words, int k)
 {
-    (void)Q; (void)k;
+    (void)Q; (void)k;                                            // ABI: sized without knowing the call, so for any plan's image
     if (N <= 0 || words <= 0) return 0;
-    // one database image, for whichever kernel the call takes
-    return std::max(std::max(old_image_bytes(N, words), rank2_image_bytes(N, words, 256)), rank2_image_bytes(N, words, 64));
+    return std::max({rank_image_bytes(RankKernel::column, N, words), rank_image_bytes(RankKernel::window256, N, words),
+                     rank_image_bytes(RankKernel::window64, N, words)});
 }
 
 extern "C" int wv_hamming_topk(const uint64_t *q, const uint64_t *db, int32_t *idx, uint8_t *dist,
                                int Q, int64_t N, int nbits, int k, int64_t idx_offset,
                                void *workspace, size_t workspace_bytes, void *stream)
 {
-    WV_REQUIRE(q && db && idx, "hamming_topk: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1, "hamming_topk: bad shape Q=%d N=%lld", Q, (long long)N);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_topk: nbits=%d (supported: 1..128)", nbits);
-    WV_REQUIRE(k >= 1 && k <= N, "hamming_topk: k=%d must be in [1, N=%lld] (torch.topk raises too)", k,
-               (long long)N);
-    WV_REQUIRE(N + idx_offset <= 0x7fffffffLL && idx_offset >= 0, "hamming_topk: indices exceed int32");
-    const int words = (nbits + 63) / 64;
-    const size_t need = wv_hamming_topk_workspace_bytes(Q, N, words, k);
-    if (!workspace || workspace_bytes < need)
-        WV_FAIL(WV_ENOMEM, "hamming_topk: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (int rc = validate_rank_ids("hamming_topk", q && db && idx, Q, N, nbits, k, idx_offset)) return rc;
+    if (int rc = require_workspace("hamming_topk", workspace, workspace_bytes, Q, N, nbits, k)) return rc;
     if (Q == 0) return WV_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (words == 1) return launch_topk<1>(q, db, nullptr, idx, dist, Q, N, nbits, k, idx_offset, workspace, st);
-    return launch_topk<2>(q, db, nullptr, idx, dist, Q, N, nbits, k, idx_offset, workspace, st);
+    return launch_topk(q, db, nullptr, idx, dist, Q, N, nbits, k, idx_offset, workspace, (hipStream_t)stream);
 }
 
 extern "C" size_t wv_db_prepared_bytes(int64_t N, int words)
 {
     if (N <= 0 || words < 1 || words > 4) return 0;
-    return align_up((int64_t)dist_prepared_bytes(N, words), 256) + (words <= 2 ? topk_prepared_bytes(N, words) : 0);
+    return blob_layout(N, words).total;
 }
 
 extern "C" int wv_db_prepare(const uint64_t *db, int64_t N, int words, void *prepared, size_t prepared_bytes,
@@ -833,30 +771,24 @@ extern "C" int wv_db_prepare(const uint64_t *db, int64_t N, int words, void *pre
 {
     WV_REQUIRE(db && prepared, "db_prepare: null buffer");
     WV_REQUIRE(N >= 1 && words >= 1 && words <= 4, "db_prepare: bad shape N=%lld words=%d", (long long)N, words);
-    const size_t need = wv_db_prepared_bytes(N, words);
-    if (prepared_bytes < need) WV_FAIL(WV_ENOMEM, "db_prepare: buffer %zu < %zu bytes", prepared_bytes, need);
+    const BlobLayout L = blob_layout(N, words);
+    if (prepared_bytes < L.total) WV_FAIL(WV_ENOMEM, "db_prepare: buffer %zu < %zu bytes", prepared_bytes, L.total);
     hipStream_t st = (hipStream_t)stream;
+    char *blob = (char *)prepared;
     int rc = dist_prepare(db, prepared, N, words, st);
-    if (rc) return rc;
-    if (words <= 2)
-        rc = topk_prepare(db, (char *)prepared + align_up((int64_t)dist_prepared_bytes(N, words), 256), N, words, st);
+    if (rc || words > 2) return rc;                              // the ranking images exist for codes of <= 2 words
+    rc = words == 1 ? launch_transpose<1>(db, (uint64_t *)(blob + L.column), N, st) : launch_transpose<2>(db, (uint64_t *)(blob + L.column), N, st);
+    if (!rc && N <= kImg256MaxRows) rc = rank2_prepare(db, blob + L.window256, N, words, RankKernel::window256, st);
+    if (!rc && N <= kImg64MaxRows) rc = rank2_prepare(db, blob + L.window64, N, words, RankKernel::window64, st);
     return rc;
 }
 
 extern "C" int wv_hamming_topk_prepared(const uint64_t *q, const void *prepared, int32_t *idx, uint8_t *dist, int Q,
                                         int64_t N, int nbits, int k, int64_t idx_offset, void *stream)
 {
-    WV_REQUIRE(q && prepared && idx, "hamming_topk_prepared: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1, "hamming_topk_prepared: bad shape Q=%d N=%lld", Q, (long long)N);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_topk_prepared: nbits=%d (supported: 1..128)", nbits);
-    WV_REQUIRE(k >= 1 && k <= N, "hamming_topk_prepared: k=%d must be in [1, N=%lld]", k, (long long)N);
-    WV_REQUIRE(N + idx_offset <= 0x7fffffffLL && idx_offset >= 0, "hamming_topk_prepared: indices exceed int32");
+    if (int rc = validate_rank_ids("hamming_topk_prepared", q && prepared && idx, Q, N, nbits, k, idx_offset)) return rc;
     if (Q == 0) return WV_OK;
-    const int words = (nbits + 63) / 64;
-    const uint64_t *dbT = (const uint64_t *)((const char *)prepared + align_up((int64_t)dist_prepared_bytes(N, words), 256));
-    hipStream_t st = (hipStream_t)stream;
-    if (words == 1) return launch_topk<1>(q, nullptr, dbT, idx, dist, Q, N, nbits, k, idx_offset, nullptr, st);
-    return launch_topk<2>(q, nullptr, dbT, idx, dist, Q, N, nbits, k, idx_offset, nullptr, st);
+    return launch_topk(q, nullptr, prepared, idx, dist, Q, N, nbits, k, idx_offset, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int wv_topk_merge(const int32_t *idx_in, const uint8_t *dist_in, int G, int Q, int kin,
@@ -864,7 +796,7 @@ extern "C" int wv_topk_merge(const int32_t *idx_in, const uint8_t *dist_in, int 
 {
     WV_REQUIRE(idx_in && dist_in && idx_out, "topk_merge: null buffer");
     WV_REQUIRE(G >= 1 && Q >= 0 && kin >= 1, "topk_merge: bad shape G=%d Q=%d kin=%d", G, Q, kin);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "topk_merge: nbits=%d (supported: 1..128)", nbits);
+    if (int rc = require_nbits("topk_merge", nbits)) return rc;
     WV_REQUIRE(k >= 1 && (int64_t)k <= (int64_t)G * kin, "topk_merge: k=%d > G*kin", k);
     if (Q == 0) return WV_OK;
     const int nbins = nbits + 2;  // dist = nbits + 1 marks padding entries: they rank after every real one
@@ -892,28 +824,13 @@ __global__ __launch_bounds__(256) void k_merge_relbits_ap(const uint32_t *__rest
     uint32_t *base = reinterpret_cast<uint32_t *>(start + G * (nbins + 1));   // [nbins + 1]
     uint32_t *M = base + nbins + 1;                               // merged relevance string, k bits (+ spill word)
     const int mwords = (k + 31) / 32 + 1;
-    uint32_t *scratch = M + mwords + (mwords & 1);                // ap_finish: 8-byte aligned
+    uint32_t *scratch = M + mwords + (mwords & 1);                // ap_final's doubles: 8-byte aligned
     const int qi = blockIdx.x, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
-    for (int u = tid; u < G * (nbins + 1); u += 256) {
-        const int g = u / (nbins + 1), b = u - g * (nbins + 1);
-        start[u] = (int32_t)min(cum[((int64_t)g * Q + qi) * cum_ld + b], (uint32_t)kin);
-    }
+    merge_starts_from_cum(cum, cum_ld, G, Q, qi, kin, nbins, start, tid);
     for (int u = tid; u < mwords; u += 256) M[u] = 0;
     __syncthreads();
     if (need_out && wv == 1) merge_report_need(cum, cum_ld, G, Q, qi, nbins, k, need_out, lane);
-    if (wv == 0) {   // totals per bin and their exclusive scan (up to 3 bins per lane)
-        uint32_t t[3] = {0, 0, 0};
-        const int b0 = 3 * lane;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (b0 + j < nbins)
-                for (int g = 0; g < G; ++g) t[j] += (uint32_t)(start[g * (nbins + 1) + b0 + j + 1] - start[g * (nbins + 1) + b0 + j]);
-        const uint32_t incl = wave_incl_scan_u32(t[0] + t[1] + t[2]);
-        const uint32_t excl = incl - (t[0] + t[1] + t[2]);
-        if (b0 < nbins) base[b0] = excl;
-        if (b0 + 1 < nbins) base[b0 + 1] = excl + t[0];
-        if (b0 + 2 < nbins) base[b0 + 2] = excl + t[0] + t[1];
-    }
+    if (wv == 0) merge_bin_bases(start, G, nbins, base, lane);
     __syncthreads();
     for (int u = tid; u < G * nbins; u += 256) {                  // one run per (bin, shard)
         const int b = u / G, g = u - b * G;
@@ -971,7 +888,7 @@ extern "C" int wv_topk_merge_cum_need(const uint16_t *idx_local, const uint32_t 
 {
     WV_REQUIRE(idx_local && cum && idx_out, "topk_merge_cum: null buffer");
     WV_REQUIRE(G >= 1 && Q >= 0 && kin >= 1 && k >= 1, "topk_merge_cum: bad shape G=%d Q=%d kin=%d k=%d", G, Q, kin, k);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "topk_merge_cum: nbits=%d (supported: 1..128)", nbits);
+    if (int rc = require_nbits("topk_merge_cum", nbits)) return rc;
     WV_REQUIRE(shard_rows >= 1 && shard_rows <= 65536, "topk_merge_cum: %lld rows per shard do not fit 16-bit local indices",
                (long long)shard_rows);
     WV_REQUIRE((int64_t)G * shard_rows <= 0x7fffffffLL, "topk_merge_cum: indices exceed int32");
@@ -988,24 +905,14 @@ extern "C" int wv_topk_merge_cum_need(const uint16_t *idx_local, const uint32_t 
 extern "C" int wv_rank_from_dist(const uint8_t *dist_matrix, int64_t ld_dist, int Q, int64_t N,
                                  int nbits, int32_t *idx, uint8_t *dist, int k, void *stream)
 {
-    WV_REQUIRE(dist_matrix && idx, "rank_from_dist: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1 && ld_dist >= N, "rank_from_dist: bad shape");
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "rank_from_dist: nbits=%d (supported: 1..128)", nbits);
-    WV_REQUIRE(k >= 1 && k <= N && N <= 0x7fffffffLL, "rank_from_dist: k=%d must be in [1, N]", k);
+    if (int rc = validate_rank_ids("rank_from_dist", dist_matrix && idx, Q, N, nbits, k, 0)) return rc;
+    WV_REQUIRE(ld_dist >= N, "rank_from_dist: row pitch %lld < N=%lld", (long long)ld_dist, (long long)N);
     if (Q == 0) return WV_OK;
-    const int C = (int)ceil_div(N, kTopkThreads);
-    const int nbins = nbits + 1;
-    const bool u16 = rank_u16(N), staged = rank_staged(k, nbins, u16);
-    const size_t lds = rank_lds_bytes(nbins, u16, k);
-    int rc = dispatch_rank(u16, staged, [&](auto U, auto S) {
-        auto kern = k_rank_from_dist<decltype(U)::value, decltype(S)::value>;
-        int r0 = set_lds_attr(reinterpret_cast<const void *>(kern), lds, "rank_from_dist");
-        if (r0) return r0;
-        hipLaunchKernelGGL(kern, dim3(Q), dim3(kTopkThreads), lds, (hipStream_t)stream, dist_matrix, ld_dist, N, idx,
-                           dist, k, C, nbins);
-        return (int)WV_OK;
-    });
-    if (rc) return rc;
+    const RankPlan plan = rank_plan_column(N, nbits);            // stored distance rows: the column kernel is the only taker
+    auto kern = column_u16(N) ? k_rank_from_dist<true> : k_rank_from_dist<false>;
+    if (int rc = set_lds_attr(reinterpret_cast<const void *>(kern), plan.lds, "rank_from_dist")) return rc;
+    hipLaunchKernelGGL(kern, dim3(Q), dim3(kTopkThreads), plan.lds, (hipStream_t)stream, dist_matrix, ld_dist, N, idx, dist, k,
+                       plan.C, nbits + 1);
     WV_CHECK_LAUNCH("k_rank_from_dist");
     return WV_OK;
 }
@@ -1048,24 +955,11 @@ extern "C" int wv_hamming_topk_ex(const uint64_t *q, const uint64_t *db, const v
                                   uint8_t *dist, uint32_t *cum, int Q, int64_t N, int nbits, int k, int64_t idx_offset,
                                   void *workspace, size_t workspace_bytes, void *stream)
 {
-    WV_REQUIRE(q && idx && (db || prepared), "hamming_topk_ex: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1, "hamming_topk_ex: bad shape Q=%d N=%lld", Q, (long long)N);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_topk_ex: nbits=%d (supported: 1..128)", nbits);
-    WV_REQUIRE(k >= 1 && k <= N, "hamming_topk_ex: k=%d must be in [1, N=%lld]", k, (long long)N);
-    WV_REQUIRE(N + idx_offset <= 0x7fffffffLL && idx_offset >= 0, "hamming_topk_ex: indices exceed int32");
+    if (int rc = validate_rank_ids("hamming_topk_ex", q && idx && (db || prepared), Q, N, nbits, k, idx_offset)) return rc;
     if (Q == 0) return WV_OK;
-    const int words = (nbits + 63) / 64;
-    hipStream_t st = (hipStream_t)stream;
-    const uint64_t *dbT = nullptr;
-    if (prepared) {
-        dbT = (const uint64_t *)((const char *)prepared + align_up((int64_t)dist_prepared_bytes(N, words), 256));
-    } else {
-        const size_t need = wv_hamming_topk_workspace_bytes(Q, N, words, k);
-        if (!workspace || workspace_bytes < need)
-            WV_FAIL(WV_ENOMEM, "hamming_topk_ex: workspace %zu < %zu bytes", workspace_bytes, need);
-    }
-    if (words == 1) return launch_topk<1>(q, db, dbT, idx, dist, Q, N, nbits, k, idx_offset, workspace, st, cum);
-    return launch_topk<2>(q, db, dbT, idx, dist, Q, N, nbits, k, idx_offset, workspace, st, cum);
+    if (!prepared)
+        if (int rc = require_workspace("hamming_topk_ex", workspace, workspace_bytes, Q, N, nbits, k)) return rc;
+    return launch_topk(q, db, prepared, idx, dist, Q, N, nbits, k, idx_offset, workspace, (hipStream_t)stream, cum);
 }
 
 // ---------------------------------------------------------------------------------- mAP without the lists
@@ -1087,74 +981,57 @@ extern "C" int wv_rank_labels_prepare(const uint64_t *dblab, int64_t N, int lwor
     return rank2_labels_prepare(dblab, prepared_labels, N, lwords, (hipStream_t)stream);
 }
 
+// ranking + AP / relevance strings (RankMode::ap, relbits): windowed kernel on the prepared images, or WV_ENOTSUP
+static int fused_call(const char *what, RankMode mode, const uint64_t *q, const void *prepared, const Rank2Ap &apx, uint32_t *cum, int Q,
+                      int64_t N, int nbits, int k, void *stream)
+{
+    const RankPlan plan = rank_plan(Q, N, nbits, k, mode);
+    if (plan.kernel == RankKernel::none) return rank_refuse(what, plan, N, k);
+    return rank2_launch(plan, q, blob_image(prepared, N, (nbits + 63) / 64, plan.kernel), nullptr, nullptr, nullptr, cum, Q, N, nbits, k,
+                        0, (hipStream_t)stream, &apx);
+}
+
 extern "C" int wv_hamming_map_at_k(const uint64_t *q, const void *prepared, const void *prepared_labels, const uint64_t *qlab,
                                    int lwords, int Q, int64_t N, int nbits, int k, float *ap, int32_t *nrel, void *stream)
 {
     WV_REQUIRE(lwords >= 1, "hamming_map_at_k: lwords=%d", lwords);
     if (lwords > 2) WV_FAIL(WV_ENOTSUP, "hamming_map_at_k: %d label words (more than 128 classes): wv_hamming_topk + wv_map_at_k", lwords);
-    WV_REQUIRE(q && prepared && prepared_labels && qlab && ap, "hamming_map_at_k: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1, "hamming_map_at_k: bad shape Q=%d N=%lld", Q, (long long)N);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_map_at_k: nbits=%d (supported: 1..128)", nbits);
-    WV_REQUIRE(k >= 1 && k <= N, "hamming_map_at_k: k=%d must be in [1, N=%lld]", k, (long long)N);
+    if (int rc = validate_rank_args("hamming_map_at_k", q && prepared && prepared_labels && qlab && ap, Q, N, nbits, k)) return rc;
     if (Q == 0) return WV_OK;
-    const int words = (nbits + 63) / 64;
-    int tpq = rank2_tpq(Q, N, k);
-    if (tpq == 64 && k > 32 * 64 && N <= kImg256MaxRows) tpq = 256;      // the AP walk keeps 32 list positions per thread
-    if (!tpq || N > kImg256MaxRows || (tpq == 64 && N > kImg64MaxRows))
-        WV_FAIL(WV_ENOTSUP, "hamming_map_at_k: %lld rows / k=%d are outside the windowed kernel (wv_hamming_topk + wv_map_at_k)",
-                (long long)N, k);
-    const char *base = (const char *)prepared + align_up((int64_t)dist_prepared_bytes(N, words), 256);
-    const void *img = base + (tpq == 256 ? r2_off256(N, words) : r2_off64(N, words));
-    const int rc = rank2_launch(q, img, nullptr, nullptr, nullptr, Q, N, nbits, k, 0, nullptr, tpq, (hipStream_t)stream,
-                                prepared_labels, qlab, ap, nrel, nullptr, 0, 0, lwords);
-    if (rc > 0) WV_FAIL(WV_ENOTSUP, "hamming_map_at_k: k=%d is outside the fused kernel (wv_hamming_topk + wv_map_at_k)", k);
-    return rc;
+    const Rank2Ap apx{(const uint32_t *)prepared_labels, qlab, lwords, ap, nrel, nullptr, 0, 0};
+    return fused_call("hamming_map_at_k", RankMode::ap, q, prepared, apx, nullptr, Q, N, nbits, k, stream);
 }
 
 // ---------------------------------------------------------------------------------- sharded search, two steps
-static int shard_call(const char *what, const uint64_t *q, const uint64_t *db, const void *prepared, uint16_t *rows16,
+// 16-bit lists and / or histograms of one shard (RankMode::rows16, hist): windowed kernel, or WV_ENOTSUP
+static int shard_call(const char *what, RankMode mode, const uint64_t *q, const uint64_t *db, const void *prepared, uint16_t *rows16,
                       uint32_t *cum, int Q, int64_t N, int nbits, int k, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const int words = (nbits + 63) / 64;
-    const int tpq = rank2_tpq(Q, N, std::max(k, 1));
-    if (!tpq) WV_FAIL(WV_ENOTSUP, "%s: shards of %lld rows / lists of %d entries are outside the windowed kernel "
-                                  "(rows <= 32768, 16-bit row numbers)", what, (long long)N, k);
+    const RankPlan plan = rank_plan(Q, N, nbits, k, mode);
+    if (plan.kernel == RankKernel::none) return rank_refuse(what, plan, N, k);
+    if (!prepared)
+        if (int rc = require_workspace(what, workspace, workspace_bytes, Q, N, nbits, k)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const void *img = nullptr;
-    if (prepared) {
-        const char *base = (const char *)prepared + align_up((int64_t)dist_prepared_bytes(N, words), 256);
-        img = base + (tpq == 256 ? r2_off256(N, words) : r2_off64(N, words));
-    } else {
-        const size_t need = wv_hamming_topk_workspace_bytes(Q, N, words, k);
-        if (!workspace || workspace_bytes < need) WV_FAIL(WV_ENOMEM, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-        int rc0 = rank2_prepare(db, workspace, N, words, tpq, st);
-        if (rc0) return rc0;
-        img = workspace;
-    }
-    const int rc = rank2_launch(q, img, nullptr, rows16, nullptr, Q, N, nbits, k, 0, cum, tpq, st);
-    if (rc > 0) WV_FAIL(WV_ENOTSUP, "%s: shape outside the windowed kernel", what);
-    return rc;
+    if (int rc = rank_image(plan, db, prepared, workspace, N, (nbits + 63) / 64, st, &img)) return rc;
+    return rank2_launch(plan, q, img, nullptr, rows16, nullptr, cum, Q, N, nbits, k, 0, st);
 }
 
 extern "C" int wv_hamming_hist(const uint64_t *q, const uint64_t *db, const void *prepared, uint32_t *cum, int Q, int64_t N,
                                int nbits, void *workspace, size_t workspace_bytes, void *stream)
 {
-    WV_REQUIRE(q && cum && (db || prepared), "hamming_hist: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1, "hamming_hist: bad shape Q=%d N=%lld", Q, (long long)N);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_hist: nbits=%d (supported: 1..128)", nbits);
+    if (int rc = validate_rank_shape("hamming_hist", q && cum && (db || prepared), Q, N, nbits)) return rc;
     if (Q == 0) return WV_OK;
-    return shard_call("hamming_hist", q, db, prepared, nullptr, cum, Q, N, nbits, 0, workspace, workspace_bytes, stream);
+    return shard_call("hamming_hist", RankMode::hist, q, db, prepared, nullptr, cum, Q, N, nbits, 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int wv_hamming_shard_prefix(const uint64_t *q, const uint64_t *db, const void *prepared, uint16_t *rows, uint32_t *cum,
                                        int Q, int64_t N, int nbits, int k, void *workspace, size_t workspace_bytes, void *stream)
 {
-    WV_REQUIRE(q && rows && cum && (db || prepared), "hamming_shard_prefix: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1, "hamming_shard_prefix: bad shape Q=%d N=%lld", Q, (long long)N);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_shard_prefix: nbits=%d (supported: 1..128)", nbits);
-    WV_REQUIRE(k >= 1 && k <= N, "hamming_shard_prefix: k=%d must be in [1, N=%lld]", k, (long long)N);
+    if (int rc = validate_rank_args("hamming_shard_prefix", q && rows && cum && (db || prepared), Q, N, nbits, k)) return rc;
     if (Q == 0) return WV_OK;
-    return shard_call("hamming_shard_prefix", q, db, prepared, rows, cum, Q, N, nbits, k, workspace, workspace_bytes, stream);
+    return shard_call("hamming_shard_prefix", RankMode::rows16, q, db, prepared, rows, cum, Q, N, nbits, k, workspace, workspace_bytes,
+                      stream);
 }
 
 extern "C" int wv_hamming_shard_relbits(const uint64_t *q, const void *prepared, const void *prepared_labels, const uint64_t *qlab,
@@ -1165,22 +1042,11 @@ extern "C" int wv_hamming_shard_relbits(const uint64_t *q, const void *prepared,
     if (lwords > 2) WV_FAIL(WV_ENOTSUP, "hamming_shard_relbits: %d label words (more than 128 classes)", lwords);
     WV_REQUIRE((relbits_ld == 0 || relbits_ld >= (k + 63) / 64) && (cum_ld == 0 || cum_ld >= nbits + 2),
                "hamming_shard_relbits: row pitches %lld / %lld too small", (long long)relbits_ld, (long long)cum_ld);
-    WV_REQUIRE(q && prepared && prepared_labels && qlab && relbits && cum, "hamming_shard_relbits: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1, "hamming_shard_relbits: bad shape Q=%d N=%lld", Q, (long long)N);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_shard_relbits: nbits=%d (supported: 1..128)", nbits);
-    WV_REQUIRE(k >= 1 && k <= N, "hamming_shard_relbits: k=%d must be in [1, N=%lld]", k, (long long)N);
+    if (int rc = validate_rank_args("hamming_shard_relbits", q && prepared && prepared_labels && qlab && relbits && cum, Q, N, nbits, k))
+        return rc;
     if (Q == 0) return WV_OK;
-    const int words = (nbits + 63) / 64;
-    int tpq = rank2_tpq(Q, N, k);
-    if (tpq == 64 && k > 32 * 64 && N <= kImg256MaxRows) tpq = 256;
-    if (!tpq || N > kImg256MaxRows || (tpq == 64 && N > kImg64MaxRows))
-        WV_FAIL(WV_ENOTSUP, "hamming_shard_relbits: %lld rows / k=%d are outside the windowed kernel", (long long)N, k);
-    const char *base = (const char *)prepared + align_up((int64_t)dist_prepared_bytes(N, words), 256);
-    const void *img = base + (tpq == 256 ? r2_off256(N, words) : r2_off64(N, words));
-    const int rc = rank2_launch(q, img, nullptr, nullptr, nullptr, Q, N, nbits, k, 0, cum, tpq, (hipStream_t)stream, prepared_labels,
-                                qlab, nullptr, nullptr, relbits, relbits_ld, cum_ld, lwords);
-    if (rc > 0) WV_FAIL(WV_ENOTSUP, "hamming_shard_relbits: k=%d is outside the fused kernel", k);
-    return rc;
+    const Rank2Ap apx{(const uint32_t *)prepared_labels, qlab, lwords, nullptr, nullptr, relbits, relbits_ld, cum_ld};
+    return fused_call("hamming_shard_relbits", RankMode::relbits, q, prepared, apx, cum, Q, N, nbits, k, stream);
 }
 
 extern "C" int wv_merge_relbits_map(const uint64_t *relbits, int64_t relbits_ld, const uint32_t *cum, int64_t cum_ld, int G, int Q,
@@ -1190,7 +1056,7 @@ extern "C" int wv_merge_relbits_map(const uint64_t *relbits, int64_t relbits_ld,
                "merge_relbits_map: row pitches %lld / %lld too small", (long long)relbits_ld, (long long)cum_ld);
     WV_REQUIRE(relbits && cum && ap, "merge_relbits_map: null buffer");
     WV_REQUIRE(G >= 1 && Q >= 0 && kin >= 1 && k >= 1, "merge_relbits_map: bad shape G=%d Q=%d kin=%d k=%d", G, Q, kin, k);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "merge_relbits_map: nbits=%d (supported: 1..128)", nbits);
+    if (int rc = require_nbits("merge_relbits_map", nbits)) return rc;
     if (Q == 0) return WV_OK;
     const int nbins = nbits + 1, w32 = 2 * (int)ceil_div(kin, 64), mwords = (k + 31) / 32 + 1;
     const size_t lds = ((size_t)G * (nbins + 1) + nbins + 1 + mwords + (mwords & 1) + ap_scratch_dwords<256>() + 4) * 4;
@@ -1205,10 +1071,8 @@ extern "C" int wv_merge_relbits_map(const uint64_t *relbits, int64_t relbits_ld,
 extern "C" int wv_hamming_topk_rows16(const uint64_t *q, const uint64_t *db, const void *prepared, uint16_t *rows, int Q,
                                       int64_t N, int nbits, int k, void *workspace, size_t workspace_bytes, void *stream)
 {
-    WV_REQUIRE(q && rows && (db || prepared), "hamming_topk_rows16: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1, "hamming_topk_rows16: bad shape Q=%d N=%lld", Q, (long long)N);
-    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_topk_rows16: nbits=%d (supported: 1..128)", nbits);
-    WV_REQUIRE(k >= 1 && k <= N, "hamming_topk_rows16: k=%d must be in [1, N=%lld]", k, (long long)N);
+    if (int rc = validate_rank_args("hamming_topk_rows16", q && rows && (db || prepared), Q, N, nbits, k)) return rc;
     if (Q == 0) return WV_OK;
-    return shard_call("hamming_topk_rows16", q, db, prepared, rows, nullptr, Q, N, nbits, k, workspace, workspace_bytes, stream);
+    return shard_call("hamming_topk_rows16", RankMode::rows16, q, db, prepared, rows, nullptr, Q, N, nbits, k, workspace, workspace_bytes,
+                      stream);
 }

@@ -22,6 +22,7 @@ WV_METRIC_IP, WV_METRIC_L2, WV_METRIC_L2_SQUARED = 0, 1, 2
 WV_RANK_DESCENDING, WV_RANK_SQRT = 1, 2
 ABI_VERSION = 5        # what include/wvhash.h documents; load() refuses a library that reports another one
 WV_BANDS_INNER, WV_BANDS_OUTER = 0, 1
+WV_ENOTSUP = -95            # return code: the shape is outside the kernel asked for (callers fall back)
 
 
 class WvhashUnavailable(RuntimeError):

@@ -225,62 +225,45 @@ def _shard_db_args(db, words, nbits, what):
     return prepared, N
 
 
+def _shard_step(what, q_packed, db, nbits, k, workspace, want_rows, want_cum):
+    """One call of the sharded search's kernel on one shard -> (rows int16 [Q, k] or None, cum int32 [Q, nbits + 2] or None)."""
+    lib = _lib.require_gpu()
+    Q, words = q_packed.shape
+    prepared, N = _shard_db_args(db, words, nbits, what)
+    dev = q_packed.device
+    rows = torch.empty((Q, k), dtype=torch.int16, device=dev) if want_rows else None
+    cum = torch.empty((Q, nbits + 2), dtype=torch.int32, device=dev) if want_cum else None
+    ws = None
+    if not prepared:
+        ws = (workspace or TopkWorkspace()).get(lib.wv_hamming_topk_workspace_bytes(Q, N, words, max(k, 1)), dev)
+    src = (None if prepared else _lib.ptr(db), _lib.ptr(db.blob) if prepared else None)
+    tail = (_lib.ptr(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_ptr())
+    with torch.cuda.device(dev):
+        if not want_rows:
+            rc = lib.wv_hamming_hist(_lib.ptr(q_packed), *src, _lib.ptr(cum), Q, N, nbits, *tail)
+        elif not want_cum:
+            rc = lib.wv_hamming_topk_rows16(_lib.ptr(q_packed), *src, _lib.ptr(rows), Q, N, nbits, k, *tail)
+        else:
+            rc = lib.wv_hamming_shard_prefix(_lib.ptr(q_packed), *src, _lib.ptr(rows), _lib.ptr(cum), Q, N, nbits, k, *tail)
+        _lib.check(rc, "wv_" + what)
+    return rows, cum
+
+
 def hamming_hist(q_packed, db, nbits, workspace=None):
     """Cumulative distance histogram of every query over the rows of `db` (no list is built):
     cum int32 [Q, nbits + 2], cum[q, b] = rows with distance < b.  First step of the sharded search."""
-    lib = _lib.require_gpu()
-    Q, words = q_packed.shape
-    prepared, N = _shard_db_args(db, words, nbits, "hamming_hist")
-    dev = q_packed.device
-    cum = torch.empty((Q, nbits + 2), dtype=torch.int32, device=dev)
-    ws, ws_bytes = None, 0
-    if not prepared:
-        ws_bytes = lib.wv_hamming_topk_workspace_bytes(Q, N, words, 1)
-        ws = (workspace or TopkWorkspace()).get(ws_bytes, dev)
-    with torch.cuda.device(dev):
-        rc = lib.wv_hamming_hist(_lib.ptr(q_packed), None if prepared else _lib.ptr(db), _lib.ptr(db.blob) if prepared else None,
-                                 _lib.ptr(cum), Q, N, nbits, _lib.ptr(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0),
-                                 _lib.stream_ptr())
-        _lib.check(rc, "wv_hamming_hist")
-    return cum
+    return _shard_step("hamming_hist", q_packed, db, nbits, 0, workspace, False, True)[1]
 
 
 def hamming_topk_rows16(q_packed, db, nbits, k, workspace=None):
     """The k nearest rows of `db` per query, ascending (distance, row), as 16-bit LOCAL row numbers (int16 storage of
     uint16 values [Q, k]): the wire format of the sharded search (topk_merge_cum)."""
-    lib = _lib.require_gpu()
-    Q, words = q_packed.shape
-    prepared, N = _shard_db_args(db, words, nbits, "hamming_topk_rows16")
-    dev = q_packed.device
-    rows = torch.empty((Q, k), dtype=torch.int16, device=dev)
-    ws = None
-    if not prepared:
-        ws = (workspace or TopkWorkspace()).get(lib.wv_hamming_topk_workspace_bytes(Q, N, words, k), dev)
-    with torch.cuda.device(dev):
-        rc = lib.wv_hamming_topk_rows16(_lib.ptr(q_packed), None if prepared else _lib.ptr(db),
-                                        _lib.ptr(db.blob) if prepared else None, _lib.ptr(rows), Q, N, nbits, k, _lib.ptr(ws),
-                                        ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_ptr())
-        _lib.check(rc, "wv_hamming_topk_rows16")
-    return rows
+    return _shard_step("hamming_topk_rows16", q_packed, db, nbits, k, workspace, True, False)[0]
 
 
 def hamming_shard_prefix(q_packed, db, nbits, k, workspace=None):
     """hamming_topk_rows16 and hamming_hist in one pass -> (rows int16 [Q, k], cum int32 [Q, nbits + 2])."""
-    lib = _lib.require_gpu()
-    Q, words = q_packed.shape
-    prepared, N = _shard_db_args(db, words, nbits, "hamming_shard_prefix")
-    dev = q_packed.device
-    rows = torch.empty((Q, k), dtype=torch.int16, device=dev)
-    cum = torch.empty((Q, nbits + 2), dtype=torch.int32, device=dev)
-    ws = None
-    if not prepared:
-        ws = (workspace or TopkWorkspace()).get(lib.wv_hamming_topk_workspace_bytes(Q, N, words, k), dev)
-    with torch.cuda.device(dev):
-        rc = lib.wv_hamming_shard_prefix(_lib.ptr(q_packed), None if prepared else _lib.ptr(db),
-                                         _lib.ptr(db.blob) if prepared else None, _lib.ptr(rows), _lib.ptr(cum), Q, N, nbits, k,
-                                         _lib.ptr(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_ptr())
-        _lib.check(rc, "wv_hamming_shard_prefix")
-    return rows, cum
+    return _shard_step("hamming_shard_prefix", q_packed, db, nbits, k, workspace, True, True)
 
 
 def topk_merge(idx_in, dist_in, k, nbits):
@@ -411,7 +394,7 @@ def hamming_map_at_k(q_packed, db, labels, qlab_packed, nbits, k):
             rc = lib.wv_hamming_map_at_k(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
                                          _lib.ptr(qlab_packed.contiguous()), labels.words, Q, db.N, nbits, k, _lib.ptr(ap), _lib.ptr(nrel),
                                          _lib.stream_ptr())
-            if rc == -95:      # WV_ENOTSUP
+            if rc == _lib.WV_ENOTSUP:
                 return None
             _lib.check(rc, "wv_hamming_map_at_k")
     return ap, nrel
@@ -450,7 +433,7 @@ def hamming_shard_relbits(q_packed, db, labels, qlab_packed, nbits, k, wire=None
             rc = lib.wv_hamming_shard_relbits(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
                                               _lib.ptr(qlab_packed.contiguous()), labels.words, wire.data_ptr() + 8 * hist_words, ld,
                                               wire.data_ptr(), 2 * ld, Q, db.N, nbits, k, _lib.stream_ptr())
-            if rc == -95:      # WV_ENOTSUP
+            if rc == _lib.WV_ENOTSUP:
                 return None
             _lib.check(rc, "wv_hamming_shard_relbits")
     return wire

@@ -69,7 +69,7 @@ def swt2d(x, wavelet="haar", level=1, channels_last=False, out_dtype=torch.float
                 rc = lib.wv_swt2d_forward_ex(_lib.ptr(x[b0:b1]), _in_dtype(x), layout, _lib.ptr(out[0, b0:b1]), odt,
                                              _lib.WV_BANDS_OUTER, B * C * H * W, b1 - b0, C, H, W, level, flo, fhi,
                                              len(lo), _lib.ptr(ws), ctypes.c_size_t(ws_bytes), _lib.stream_ptr())
-                if rc == -95:     # WV_ENOTSUP: shape outside the sliding kernel -> reference layout, re-laid out once
+                if rc == _lib.WV_ENOTSUP:     # shape outside the sliding kernel -> reference layout, re-laid out once
                     inner = swt2d(x, wavelet, level, channels_last=channels_last, out_dtype=out_dtype)
                     out.copy_(inner.permute(2, 0, 1, 3, 4))
                     return out

@@ -60,6 +60,20 @@ def test_argument_validation_happens_on_the_host():
     assert rc == -22
     rc = lib.wv_hamming_topk(one, one, one, one, 4, 100, 64, 10, 0, one, 8, None)
     assert rc == -12 and b"workspace" in lib.wv_last_error()
+    big = 1 << 30
+    for k in (-1, -5, 0, 101):                           # every ranking entry point refuses a list length outside [1, N]
+        calls = {"hamming_topk": lib.wv_hamming_topk(one, one, one, one, 4, 100, 64, k, 0, one, big, None),
+                 "hamming_topk_prepared": lib.wv_hamming_topk_prepared(one, one, one, one, 4, 100, 64, k, 0, None),
+                 "hamming_topk_ex": lib.wv_hamming_topk_ex(one, one, None, one, one, one, 4, 100, 64, k, 0, one, big, None),
+                 "hamming_topk_rows16": lib.wv_hamming_topk_rows16(one, one, None, one, 4, 100, 64, k, one, big, None),
+                 "hamming_shard_prefix": lib.wv_hamming_shard_prefix(one, one, None, one, one, 4, 100, 64, k, one, big, None),
+                 "hamming_map_at_k": lib.wv_hamming_map_at_k(one, one, one, one, 1, 4, 100, 64, k, one, one, None),
+                 "hamming_shard_relbits": lib.wv_hamming_shard_relbits(one, one, one, one, 1, one, 0, one, 0, 4, 100, 64, k, None),
+                 "rank_from_dist": lib.wv_rank_from_dist(one, 100, 4, 100, 64, one, one, k, None)}
+        assert calls == {name: -22 for name in calls}, (k, calls)
+    assert lib.wv_hamming_topk(one, one, one, one, 4, 100, 64, -1, 0, one, big, None) == -22 and b"k=-1" in lib.wv_last_error()
+    assert lib.wv_hamming_hist(one, one, None, one, 4, 0, 64, one, big, None) == -22      # the one call without k: shape, width
+    assert lib.wv_hamming_hist(one, one, None, one, 4, 100, 129, one, big, None) == -22
     assert lib.wv_hamming_topk_workspace_bytes(4, 25000, 1, 5000) == 98 * 256 * 8
     assert lib.wv_hamming_dist(None, one, one, 10, 1, 10, 1, None) == -22
     assert lib.wv_swt2d_workspace_bytes(2, 3, 224, 224, 3, 4) == 0          # sliding kernel covers it

@@ -35,9 +35,8 @@ def main():
         qp = H.pack_codes(q.cuda())
         prep = H.PreparedDB(H.pack_codes(r.cuda()), nbits)
         ref = None
-        for variant, qb in (("0", "1"), ("256", "1"), ("256", "8"), ("64", "1"), ("64", "8")):
+        for variant in ("0", "256", "64"):
             os.environ["WV_TOPK_V2"] = variant
-            os.environ["WV_TOPK_QB"] = qb
             try:
                 us = timeit(lambda: H.hamming_topk(qp, prep, nbits, k, want_dist=not cum, want_cum=cum))
             except Exception as e:  # noqa: BLE001
@@ -47,9 +46,8 @@ def main():
             same = "" if ref is None else f"  identical to variant 0: {torch.equal(out[0], ref)}"
             ref = out[0] if ref is None else ref
             bytes_alg = (Q + N) * nbits // 8 + Q * k * (4 if cum else 5)
-            print(f"{name} Q={Q} N={N} {nbits}b k={k}: variant {variant} qb {'max' if qb != '1' else '1'}: {us:7.1f} us  {bytes_alg / us / 1e3:7.1f} GB/s{same}", flush=True)
+            print(f"{name} Q={Q} N={N} {nbits}b k={k}: variant {variant}: {us:7.1f} us  {bytes_alg / us / 1e3:7.1f} GB/s{same}", flush=True)
     os.environ.pop("WV_TOPK_V2", None)
-    os.environ.pop("WV_TOPK_QB", None)
 
 
 if __name__ == "__main__":

@@ -26,9 +26,8 @@ def main():
         ql, rl = synth.multi_hot_labels(Q, 38, 0.10, 1), synth.multi_hot_labels(N, 38, 0.10, 2)
         q, r = synth.structured_codes(ql, nbits, 3, 4), synth.structured_codes(rl, nbits, 3, 5)
         qp, prep = H.pack_codes(q.cuda()), H.PreparedDB(H.pack_codes(r.cuda()), nbits)
-        for variant, qb in (("256", "1"), ("256", "8"), ("64", "8")):
+        for variant in ("256", "64"):
             os.environ["WV_TOPK_V2"] = variant
-            os.environ["WV_TOPK_QB"] = qb
             try:
                 H.hamming_topk(qp, prep, nbits, k, want_dist=not cum, want_cum=cum)
             except Exception:  # noqa: BLE001
@@ -39,7 +38,7 @@ def main():
             torch.cuda.synchronize()
             fn(buf)
             tot = sum(buf[:8])
-            print(f"{name} variant {variant} qb {qb}: total {tot / Q:.0f} cycles/query: " +
+            print(f"{name} variant {variant}: total {tot / Q:.0f} cycles/query: " +
                   ", ".join(f"{n} {buf[i] / Q:.0f}" for i, n in enumerate(NAMES)), flush=True)
 
 
