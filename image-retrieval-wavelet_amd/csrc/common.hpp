@@ -85,4 +85,24 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     return v;
 }
 
+// GELU(v) = 0.5 v (1 + erf(v / sqrt 2)) (nn.GELU() default, multi_dino_attention.py:1098).  erfc(|x|) by Abramowitz &
+// Stegun 7.1.26 (absolute error <= 1.5e-7, i.e. fp32 rounding of an O(1) value), 1 + erf taken as erfc(|x|) on the
+// negative side so that nothing cancels: 14 instructions against ~40 of the library erff.  -DWV_HF_EXACT_ERF restores
+// erff.  Used by the one-launch front (head_front.hip) and the bf16 products (head_bf16.hip).
+__device__ __forceinline__ float gelu_erf(float v)
+{
+#ifdef WV_HF_EXACT_ERF
+    return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+#else
+    const float x = fabsf(v) * 0.70710678118654752440f;
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, x, 1.0f));   // v_rcp_f32 (1 ulp); the IEEE division is 11 instructions
+    float p = fmaf(1.061405429f, t, -1.453152027f);
+    p = fmaf(p, t, 1.421413741f);
+    p = fmaf(p, t, -0.284496736f);
+    p = fmaf(p, t, 0.254829592f);
+    const float erfc_abs = p * t * __expf(-x * x);
+    return 0.5f * v * (v >= 0.f ? 2.0f - erfc_abs : erfc_abs);
+#endif
+}
+
 }  // namespace wv

@@ -496,8 +496,8 @@ __global__ __launch_bounds__(256) void k_layernorm(const float *__restrict__ x, 
     }
 }
 
-static void launch_layernorm(const float *x, const float *w, const float *b, float *y, int64_t rows, int E, float eps,
-                             int nparts, hipStream_t st)
+void launch_layernorm(const float *x, const float *w, const float *b, float *y, int64_t rows, int E, float eps, int nparts,
+                      hipStream_t st)
 {
     const dim3 grid((unsigned)ceil_div(rows, 4));
     if (E <= 512) hipLaunchKernelGGL(k_layernorm<8>, grid, dim3(256), 0, st, x, w, b, y, rows, E, eps, nparts);
@@ -856,6 +856,40 @@ static int check_head(const wv_head_params *p, int B)
                "band_attn_pool: null weight pointer");
     return WV_OK;
 }
+
+// head_bf16.hip runs the stages that stay fp32 in either precision through these
+namespace wv {
+
+int head_check_params(const wv_head_params *p, int B) { return check_head(p, B); }
+
+void head_launch_qproj(const wv_head_params *p, float *Qp, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_qproj, dim3((unsigned)ceil_div(p->num_queries * p->embed_dim, 4)), dim3(256), 0, st, p->q_eff,
+                       p->in_proj_w, p->in_proj_b, Qp, p->num_queries, p->embed_dim);
+}
+
+size_t head_attn_core_lds(const wv_head_params *p)
+{
+    const size_t E = p->embed_dim, Nq = p->num_queries, S = p->num_tokens;
+    return (S * (2 * E + 4) + Nq * E + Nq * p->num_heads * S) * sizeof(float);
+}
+
+void head_launch_attn_core(const wv_head_params *p, const float *Qp, const float *KV, float *ctx, int B, hipStream_t st)
+{
+    const size_t sm = head_attn_core_lds(p);
+    if (sm > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_attn_core), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+    hipLaunchKernelGGL(k_attn_core, dim3(B), dim3(256), sm, st, Qp, KV, ctx, B, p->embed_dim, p->num_heads, p->num_queries,
+                       p->num_tokens);
+}
+
+void head_launch_mean_rows(const float *x, float *y, int64_t groups, int n, int E, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_mean_rows, dim3((unsigned)std::min<int64_t>(ceil_div(groups * E, 256), 4096)), dim3(256), 0, st, x, y,
+                       groups, n, E);
+}
+
+}  // namespace wv
 
 extern "C" size_t wv_band_attn_pool_workspace_bytes(const wv_head_params *p, int B)
 {

@@ -2,6 +2,8 @@
 //   wv_band_attn_pool_cpu <- wv_band_attn_pool   CrossAttentionBottleneckHead*.forward in eval mode
 //                                                (/root/reference/main/models/multi_dino_attention.py:1111-1141; :1030, :568, :448)
 //   wv_hash_tail_cpu      <- wv_hash_tail        hash_fc -> BatchNorm1d(eval) -> sign (+ bit packing)  (:829-833)
+//   wv_band_attn_pool_bf16_cpu <- wv_band_attn_pool_bf16   the same forward with both operands of the five dense weight
+//                                                products rounded to bf16 (nearest even) and nothing else changed
 // for a model whose tensors live on the host (module.to('cpu') -- explicit, never a silent fallback).
 //
 // fp32 throughout, like the kernels; every contraction is the same on any machine: eight interleaved fused-multiply-add
@@ -97,18 +99,56 @@ void layer_norm(float *x, int E, const float *w, const float *b, float eps)
 
 inline float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 
-}  // namespace
-
-extern "C" int wv_band_attn_pool_cpu(const wv_head_params *p, const float *feats, int B, float *out)
+// bf16 value (round to nearest even) of an fp32 number, as an fp32 number
+inline float bf16_round(float f)
 {
-    HH_REQUIRE(p && feats && out, "band_attn_pool_cpu: null buffer");
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return f;   // NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    u &= 0xffff0000u;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+std::vector<float> bf16_copy(const float *x, size_t n)
+{
+    std::vector<float> r(n);
+    for (size_t i = 0; i < n; ++i) r[i] = bf16_round(x[i]);
+    return r;
+}
+
+// The forward of both precisions.  bf16 = true: every operand of the five dense weight products is rounded to bf16 where it
+// is read (weights once, up front); products of bf16 values are exact in fp32 and the accumulation is the fp32 chain of
+// linear(), so nothing else changes.  what: the entry point's name in error texts.
+int pool_cpu(const wv_head_params *p, const void *feats_any, int feat_dtype, int B, float *out, bool bf16, const char *what)
+{
+    HH_REQUIRE(p && feats_any && out, "%s: null buffer", what);
     const int E = p->embed_dim, H = p->num_heads, Nq = p->num_queries, S = p->num_tokens;
     HH_REQUIRE(E >= 8 && E % 8 == 0 && H >= 1 && E % H == 0 && Nq >= 1 && S >= 1 && S <= 64 && B >= 0,
-               "band_attn_pool_cpu: bad configuration E=%d heads=%d Nq=%d S=%d B=%d", E, H, Nq, S, B);
+               "%s: bad configuration E=%d heads=%d Nq=%d S=%d B=%d", what, E, H, Nq, S, B);
     HH_REQUIRE(p->q_eff && p->in_proj_w && p->in_proj_b && p->attn_out_w && p->attn_out_b && p->norm1_w && p->norm1_b &&
                    p->mlp0_w && p->mlp0_b && p->mlp2_w && p->mlp2_b && p->out_w && p->out_b && p->norm2_w && p->norm2_b,
-               "band_attn_pool_cpu: null parameter");
+               "%s: null parameter", what);
     if (B == 0) return WV_OK;
+    const float *feats = feat_dtype == WV_DT_F32 ? static_cast<const float *>(feats_any) : nullptr;
+    const uint16_t *feats16 = static_cast<const uint16_t *>(feats_any);
+    const size_t ro_k = p->pool_mean ? (size_t)E : (size_t)Nq * E;
+    std::vector<float> wkv_r, wo_r, w0_r, w2_r, wout_r, op;     // op: the rounded copy of an activation operand
+    const float *wkv = p->in_proj_w + (size_t)E * E, *wo = p->attn_out_w, *w0 = p->mlp0_w, *w2 = p->mlp2_w, *wout = p->out_w;
+    if (bf16) {
+        wkv = (wkv_r = bf16_copy(wkv, (size_t)2 * E * E)).data();
+        wo = (wo_r = bf16_copy(wo, (size_t)E * E)).data();
+        w0 = (w0_r = bf16_copy(w0, (size_t)4 * E * E)).data();
+        w2 = (w2_r = bf16_copy(w2, (size_t)4 * E * E)).data();
+        wout = (wout_r = bf16_copy(wout, (size_t)E * ro_k)).data();
+    }
+    auto operand = [&](const std::vector<float> &x) {
+        if (!bf16) return x.data();
+        op.resize(x.size());
+        for (size_t i = 0; i < x.size(); ++i) op[i] = bf16_round(x[i]);
+        return (const float *)op.data();
+    };
     const int d = E / H;
     const float scale = 1.f / sqrtf((float)d);
     // Q = q_eff Wq^T + bq: the query tokens are parameters, projected once (p->q_proj is a DEVICE pointer in the GPU path;
@@ -119,9 +159,20 @@ extern "C" int wv_band_attn_pool_cpu(const wv_head_params *p, const float *feats
         y((size_t)Nq * E), pooled((size_t)E);
     const int64_t sB = (int64_t)B * E;
     for (int b = 0; b < B; ++b) {
-        for (int s = 0; s < S; ++s) memcpy(kv.data() + (size_t)s * E, feats + s * sB + (int64_t)b * E, sizeof(float) * E);
+        for (int s = 0; s < S; ++s) {
+            float *dst = kv.data() + (size_t)s * E;
+            if (feats) {
+                memcpy(dst, feats + s * sB + (int64_t)b * E, sizeof(float) * E);
+            } else {
+                const uint16_t *src = feats16 + s * sB + (int64_t)b * E;
+                for (int i = 0; i < E; ++i) {
+                    const uint32_t u = (uint32_t)src[i] << 16;
+                    memcpy(dst + i, &u, 4);
+                }
+            }
+        }
         // K | V = kv [Wk; Wv]^T + [bk; bv]  (rows E..3E of the packed in-projection)
-        linear(kv.data(), E, S, p->in_proj_w + (size_t)E * E, p->in_proj_b + E, 2 * E, E, KV.data(), 2 * E);
+        linear(operand(kv), E, S, wkv, p->in_proj_b + E, 2 * E, E, KV.data(), 2 * E);
         for (int h = 0; h < H; ++h)
             for (int nq = 0; nq < Nq; ++nq) {
                 float sc[64], mx = -INFINITY;
@@ -143,15 +194,15 @@ extern "C" int wv_band_attn_pool_cpu(const wv_head_params *p, const float *feats
                 }
             }
         // x = LN1(q + attn.out_proj(ctx));  x = x + mlp.2(GELU(mlp.0(x)))
-        linear(ctx.data(), E, Nq, p->attn_out_w, p->attn_out_b, E, E, x.data(), E);
+        linear(operand(ctx), E, Nq, wo, p->attn_out_b, E, E, x.data(), E);
         for (int nq = 0; nq < Nq; ++nq) {
             float *xr = x.data() + (size_t)nq * E;
             for (int i = 0; i < E; ++i) xr[i] += p->q_eff[(size_t)nq * E + i];
             layer_norm(xr, E, p->norm1_w, p->norm1_b, p->ln_eps);
         }
-        linear(x.data(), E, Nq, p->mlp0_w, p->mlp0_b, 4 * E, E, hid.data(), 4 * E);
+        linear(operand(x), E, Nq, w0, p->mlp0_b, 4 * E, E, hid.data(), 4 * E);
         for (size_t i = 0; i < hid.size(); ++i) hid[i] = gelu_erf(hid[i]);
-        linear(hid.data(), 4 * E, Nq, p->mlp2_w, p->mlp2_b, E, 4 * E, y.data(), E);
+        linear(operand(hid), 4 * E, Nq, w2, p->mlp2_b, E, 4 * E, y.data(), E);
         for (size_t i = 0; i < x.size(); ++i) x[i] += y[i];
         // read-out: mean over the queries then Linear(E -> E), or Linear(Nq E -> E) on the concatenation; LN2
         float *ob = out + (size_t)b * E;
@@ -161,13 +212,28 @@ extern "C" int wv_band_attn_pool_cpu(const wv_head_params *p, const float *feats
                 for (int nq = 0; nq < Nq; ++nq) a += x[(size_t)nq * E + i];
                 pooled[(size_t)i] = a / (float)Nq;
             }
-            linear(pooled.data(), E, 1, p->out_w, p->out_b, E, E, ob, E);
+            linear(operand(pooled), E, 1, wout, p->out_b, E, E, ob, E);
         } else {
-            linear(x.data(), (int64_t)Nq * E, 1, p->out_w, p->out_b, E, Nq * E, ob, E);
+            linear(operand(x), (int64_t)Nq * E, 1, wout, p->out_b, E, Nq * E, ob, E);
         }
         layer_norm(ob, E, p->norm2_w, p->norm2_b, p->ln_eps);
     }
     return WV_OK;
+}
+
+}  // namespace
+
+extern "C" int wv_band_attn_pool_cpu(const wv_head_params *p, const float *feats, int B, float *out)
+{
+    return pool_cpu(p, feats, WV_DT_F32, B, out, false, "band_attn_pool_cpu");
+}
+
+extern "C" int wv_band_attn_pool_bf16_cpu(const wv_head_params *p, const void *feats, int feat_dtype, int B, float *out)
+{
+    HH_REQUIRE(feat_dtype == WV_DT_F32 || feat_dtype == WV_DT_BF16, "band_attn_pool_bf16_cpu: feat_dtype=%d (WV_DT_F32 or WV_DT_BF16)",
+               feat_dtype);
+    HH_REQUIRE(!p || p->embed_dim % 32 == 0, "band_attn_pool_bf16_cpu: embed_dim=%d must be a multiple of 32", p->embed_dim);
+    return pool_cpu(p, feats, feat_dtype, B, out, true, "band_attn_pool_bf16_cpu");
 }
 
 extern "C" int wv_hash_tail_cpu(const float *fused, int B, int E, const float *hash_w, const float *hash_b, const float *bn_w,

@@ -114,6 +114,11 @@ SIGNATURES = {
     "wv_rank_scores_cpu": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp]),
     "wv_band_attn_pool_cpu": (_i, [ctypes.POINTER(HeadParams), _vp, _i, _vp]),
     "wv_hash_tail_cpu": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
+    "wv_band_attn_bf16_prepared_bytes": (_sz, [ctypes.POINTER(HeadParams)]),
+    "wv_band_attn_bf16_prepare": (_i, [ctypes.POINTER(HeadParams), _vp, _vp]),
+    "wv_band_attn_pool_bf16_workspace_bytes": (_sz, [ctypes.POINTER(HeadParams), _i]),
+    "wv_band_attn_pool_bf16": (_i, [ctypes.POINTER(HeadParams), _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "wv_band_attn_pool_bf16_cpu": (_i, [ctypes.POINTER(HeadParams), _vp, _i, _i, _vp]),
 }
 
 _LIB = None

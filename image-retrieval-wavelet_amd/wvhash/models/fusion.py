@@ -2,7 +2,8 @@
 /root/reference/main/models/multi_dino_attention.py (CrossAttentionBottleneckHead :1001-1062,
 ...Advanced :1064-1141, ...Pooled :484-599, ...Decoupled :336-481, get_fusion_head :602-690).
 
-Eval-mode forward on GPU tensors runs the HIP/MFMA kernels (wv_band_attn_pool).  Training-mode
+Eval-mode forward on GPU tensors runs the HIP/MFMA kernels (wv_band_attn_pool; with `head.matrix_dtype = "bf16"` or
+"auto" the opt-in bf16 matrix-core path, wv_band_attn_pool_bf16).  Training-mode
 forward (dropout, autograd, ortho loss) is stock PyTorch on the GPU: training is outside the
 accelerated path.  There is no CPU execution path.
 """
@@ -18,28 +19,47 @@ from .. import _lib
 LOGGER = logging.getLogger("RETRIEVAL")
 
 
-def _stacked(features_list):
+def _stacked(features_list, keep_bf16=False):
     """S x [B, E] -> one [S, B, E] fp32 tensor.  Band features that already lie back to back in one allocation
-    (slices of a preallocated [S, B, E] buffer the backbones wrote into) are used in place, without a copy."""
+    (slices of a preallocated [S, B, E] buffer the backbones wrote into) are used in place, without a copy.
+    keep_bf16 (the bf16 head): features that are all bf16 stay bf16 -- in place or stacked, never upcast."""
     f0 = features_list[0]
-    if f0.dtype == torch.float32 and f0.dim() == 2 and f0.is_contiguous():
-        base, step = f0.untyped_storage().data_ptr(), f0.numel() * 4
-        if all(f.dtype == torch.float32 and f.shape == f0.shape and f.is_contiguous()
+    dtype = torch.bfloat16 if keep_bf16 and all(f.dtype == torch.bfloat16 for f in features_list) else torch.float32
+    if f0.dtype == dtype and f0.dim() == 2 and f0.is_contiguous():
+        base, step = f0.untyped_storage().data_ptr(), f0.numel() * f0.element_size()
+        if all(f.dtype == dtype and f.shape == f0.shape and f.is_contiguous()
                and f.untyped_storage().data_ptr() == base and f.data_ptr() == f0.data_ptr() + i * step
                for i, f in enumerate(features_list)):
             return f0.as_strided((len(features_list),) + tuple(f0.shape), (f0.numel(), f0.shape[1], 1))
-    return torch.stack([f.float() for f in features_list], dim=0).contiguous()
+    return torch.stack([f.to(dtype) for f in features_list], dim=0).contiguous()
+
+
+def resolve_matrix_dtype(value, device_type="cuda"):
+    """`matrix_dtype` of a head or a call -> None (the fp32 matrix-core path) or "bf16".  Accepted: None, torch.bfloat16 /
+    "bf16" / "bfloat16", and "auto" = bf16 exactly when the call runs under torch.autocast(device_type, dtype=torch.bfloat16)."""
+    if value is None:
+        return None
+    if value is torch.bfloat16 or value in ("bf16", "bfloat16"):
+        return "bf16"
+    if isinstance(value, str) and value == "auto":
+        return "bf16" if torch.is_autocast_enabled(device_type) and torch.get_autocast_dtype(device_type) == torch.bfloat16 else None
+    raise ValueError(f"matrix_dtype must be None, torch.bfloat16 / 'bf16' or 'auto', got {value!r}")
 
 
 def band_attn_pool(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mean=False,
-                   workspace=None, qproj_cache=None, qproj_key=None):
+                   workspace=None, qproj_cache=None, qproj_key=None, matrix_dtype=None, bf16_cache=None):
     """HIP forward of the attention-pooling core.  features_list: S x [B, E] CUDA fp32.
+    matrix_dtype: None = the fp32 matrix-core path; torch.bfloat16 / "bf16" / "auto" (see resolve_matrix_dtype) = the bf16
+    path (wv_band_attn_pool_bf16: bf16 operands, fp32 accumulation, fp32 output), which also takes bf16 features as they
+    are; bf16_cache: a dict owned by the module for that path's prepared blob -- separate from qproj_cache, so that
+    alternating precisions rebuilds neither.
     qproj_cache: a dict owned by the module; holds what is made from parameters alone -- the projected query tokens and,
     for the configurations with a one-launch front (wv_band_attn_prepared_bytes), the fragment-ordered copy of the
     weights -- so that it is rebuilt when a parameter changes, not in every call; qproj_key identifies the parameters
     q_eff was made from (storage pointers + version counters)."""
     lib = _lib.require_gpu()
-    feats = _stacked(features_list)                                                   # [S, B, E]
+    use_bf16 = resolve_matrix_dtype(matrix_dtype) == "bf16"
+    feats = _stacked(features_list, keep_bf16=use_bf16)                               # [S, B, E]
     S, B, E = feats.shape
     q_src = q_eff
     q_eff = q_eff.detach().float().reshape(-1, E).contiguous()
@@ -61,6 +81,8 @@ def band_attn_pool(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, out_pro
     if B == 0:
         return out
     p.prepared = None
+    if use_bf16:
+        return _band_attn_pool_bf16(lib, p, feats, out, workspace, bf16_cache, qproj_key, q_src, attn, mlp0, mlp2, out_proj)
     if qproj_cache is not None:
         # the query tokens and the weights are parameters: key on their storage and version counters
         watched = (attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, mlp0.weight, mlp2.weight)
@@ -93,12 +115,45 @@ def band_attn_pool(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, out_pro
     return out
 
 
-def band_attn_pool_host(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mean=False):
+def _band_attn_pool_bf16(lib, p, feats, out, workspace, cache, qproj_key, q_src, attn, mlp0, mlp2, out_proj):
+    """The bf16 matrix-core path: prepared blob (projected queries + bf16 weights) from `cache`, then one call."""
+    S, B, E = feats.shape
+    dev = feats.device
+    watched = (attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, mlp0.weight, mlp2.weight, out_proj.weight)
+    key = (qproj_key if qproj_key is not None else (q_src.data_ptr(), q_src._version),
+           tuple((t.data_ptr(), t._version) for t in watched), attn.num_heads, S, p.pool_mean, dev)
+    entry = cache.get("entry") if cache is not None else None
+    if entry is None or entry[0] != key:
+        with torch.cuda.device(dev):
+            nbytes = lib.wv_band_attn_bf16_prepared_bytes(ctypes.byref(p))
+            if not nbytes:      # never a silent fp32 run
+                raise _lib.WvhashError("wv_band_attn_bf16_prepared_bytes: " + lib.wv_last_error().decode(errors="replace"))
+            blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.wv_band_attn_bf16_prepare(ctypes.byref(p), _lib.ptr(blob), _lib.stream_ptr()), "wv_band_attn_bf16_prepare")
+        entry = (key, blob)
+        if cache is not None:
+            cache["entry"] = entry          # one assignment: a replica that reads the dict sees the old or the new pair
+    blob = entry[1]
+    ws_bytes = lib.wv_band_attn_pool_bf16_workspace_bytes(ctypes.byref(p), B)
+    if workspace is None or workspace.numel() < ws_bytes or workspace.device != dev:
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    dt = _lib.WV_DT_BF16 if feats.dtype == torch.bfloat16 else _lib.WV_DT_F32
+    with torch.cuda.device(dev):
+        rc = lib.wv_band_attn_pool_bf16(ctypes.byref(p), _lib.ptr(blob), _lib.ptr(feats), dt, B, _lib.ptr(out), _lib.ptr(workspace),
+                                        ctypes.c_size_t(workspace.numel()), _lib.stream_ptr())
+        _lib.check(rc, "wv_band_attn_pool_bf16")
+    return out
+
+
+def band_attn_pool_host(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mean=False, matrix_dtype=None):
     """The same forward on HOST tensors through the library's host twin (wv_band_attn_pool_cpu, csrc/host_head.cpp): for a
     model that was moved to the CPU on purpose.  fp32, machine-independent summation order; agrees with the kernels to
-    fp32 rounding."""
+    fp32 rounding.  matrix_dtype as in band_attn_pool: "bf16" runs wv_band_attn_pool_bf16_cpu (operands of the weight
+    products rounded to bf16, everything else as here; bf16 features are read as they are)."""
     lib = _lib.load()
-    feats = torch.stack([f.detach().float() for f in features_list], dim=0).contiguous()        # [S, B, E]
+    use_bf16 = resolve_matrix_dtype(matrix_dtype, "cpu") == "bf16"
+    fdt = torch.bfloat16 if use_bf16 and all(f.dtype == torch.bfloat16 for f in features_list) else torch.float32
+    feats = torch.stack([f.detach().to(fdt) for f in features_list], dim=0).contiguous()        # [S, B, E]
     S, B, E = feats.shape
     q_eff = q_eff.detach().float().reshape(-1, E).contiguous()
     keep = [t.detach().float().contiguous() for t in
@@ -115,6 +170,10 @@ def band_attn_pool_host(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, ou
     p.q_proj = None
     p.prepared = None
     out = torch.empty((B, E), dtype=torch.float32)
+    if use_bf16:
+        dt = _lib.WV_DT_BF16 if fdt == torch.bfloat16 else _lib.WV_DT_F32
+        _lib.check(lib.wv_band_attn_pool_bf16_cpu(ctypes.byref(p), _lib.ptr(feats), dt, B, _lib.ptr(out)), "wv_band_attn_pool_bf16_cpu")
+        return out
     _lib.check(lib.wv_band_attn_pool_cpu(ctypes.byref(p), _lib.ptr(feats), B, _lib.ptr(out)), "wv_band_attn_pool_cpu")
     return out
 
@@ -148,6 +207,9 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
         self._ws = None
         self._zero_loss = None
         self._qproj_cache = {}
+        # None: fp32 matrix cores (default); torch.bfloat16 / "bf16": the bf16 path; "auto": bf16 under bf16 autocast
+        self.matrix_dtype = None
+        self._bf16_cache = {}
 
     # -- pieces shared by the four variants ------------------------------------------------
     def compute_ortho_loss(self):
@@ -201,7 +263,8 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
             self.last_ortho_loss = torch.zeros(())
             with torch.no_grad():
                 return band_attn_pool_host(kv_list, self.effective_queries(), self.attn, self.norm1, self.norm2,
-                                           self.mlp[0], self.mlp[2], self.out_proj, self._pool == "mean")
+                                           self.mlp[0], self.mlp[2], self.out_proj, self._pool == "mean",
+                                           matrix_dtype=self.matrix_dtype)
 
         if self._hip_ok(kv_list):
             # torch.zeros launches a fill on the stream; torch.tensor(0.0, device=...) is a blocking host-to-device
@@ -212,7 +275,8 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
             with torch.no_grad():
                 out = band_attn_pool(kv_list, self.effective_queries(), self.attn, self.norm1, self.norm2,
                                      self.mlp[0], self.mlp[2], self.out_proj, self._pool == "mean", self._ws,
-                                     self._qproj_cache, self._query_key())
+                                     self._qproj_cache, self._query_key(), matrix_dtype=self.matrix_dtype,
+                                     bf16_cache=self._bf16_cache)
             return out
 
         # training / unsupported shapes: stock PyTorch on the GPU (outside the accelerated path)
@@ -301,18 +365,25 @@ def get_fusion_head(fusion_config, output_dims):
         sub_band_dropout_p=fusion_config.get('sub_band_dropout_p', 0.3),
         ortho_weight=fusion_config.get('ortho_weight', 0.1),
     )
+    head = None
     if fusion_type in ('cross_attention_bottleneck', 'cross_attention_advanced'):
-        return _HIP_TYPES[fusion_type](output_dims, embed_dim, **common)
-    if fusion_type == 'cross_attention_pooled':
-        return CrossAttentionBottleneckHeadPooled(
+        head = _HIP_TYPES[fusion_type](output_dims, embed_dim, **common)
+    elif fusion_type == 'cross_attention_pooled':
+        head = CrossAttentionBottleneckHeadPooled(
             output_dims, embed_dim, use_all_tokens=fusion_config.get('use_all_tokens', False),
             query_pool=fusion_config.get('query_pool', 'mean'), **common)
-    if fusion_type == 'cross_attention_decoupled':
-        return CrossAttentionBottleneckHeadDecoupled(
+    elif fusion_type == 'cross_attention_decoupled':
+        head = CrossAttentionBottleneckHeadDecoupled(
             output_dims, embed_dim, use_all_tokens=fusion_config.get('use_all_tokens', False),
             query_scale_init=fusion_config.get('query_scale_init', 4.0),
             normalize_queries=fusion_config.get('normalize_queries', True),
             learn_query_scale=fusion_config.get('learn_query_scale', True), **common)
+    if head is not None:
+        # optional, absent in every reference YAML: the matrix-core dtype of the eval-mode forward
+        head.matrix_dtype = fusion_config.get('matrix_dtype')
+        if head.matrix_dtype != "auto":
+            resolve_matrix_dtype(head.matrix_dtype)          # an unknown value raises here, not at the first forward
+        return head
     # every other type (standard, temperature, semantic, gated, temperature_gated, self_attention, cbam, eca; unknown
     # names fall back to standard like the reference): stock PyTorch modules with the reference's state_dict keys
     from .fusion_extra import build_extra_head

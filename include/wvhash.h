@@ -44,7 +44,8 @@ extern "C" {
 #define WV_LAYOUT_NHWC 1 /* [B][H][W][C]  (PIL / numpy, what np.array(img) yields) */
 
 const char *wv_last_error(void);
-/* 5 = this header.  History: 5 added WV_METRIC_L2_SQUARED, wv_rank_scores[_cpu] and the host twins wv_knn_float_cpu,
+/* 5 = this header.  History: the bf16 head entry points (wv_band_attn_bf16_prepare ... wv_band_attn_pool_bf16_cpu) were added
+ * under 5 -- new symbols only, no struct or existing signature changed; 5 added WV_METRIC_L2_SQUARED, wv_rank_scores[_cpu] and the host twins wv_knn_float_cpu,
  * wv_band_attn_pool_cpu, wv_hash_tail_cpu; 4 added the host twins of the ranking side (wv_pack_bits_cpu ... wv_hit_prefix_cpu); 2 added wv_head_params.q_proj, the host twins, wv_swt2d_forward_ex, the two-step shard entry
  * points and wv_map_at_k_ld; 3 added wv_head_params.prepared / wv_band_attn_prepare (one-launch head front), the ranking + AP
  * entry points (wv_hamming_map_at_k, wv_rank_labels_prepare), wv_hamming_shard_prefix / wv_topk_merge_cum_need and the
@@ -411,6 +412,33 @@ int wv_band_attn_pool_cpu(const wv_head_params *p, const float *feats, int B, fl
 int wv_hash_tail_cpu(const float *fused, int B, int E, const float *hash_w, const float *hash_b, const float *bn_w,
                      const float *bn_b, const float *bn_mean, const float *bn_var, float bn_eps, int nbits,
                      float *logits_out, float *codes_out, uint64_t *packed_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Opt-in bf16 matrix-core path of the same head: what the reference computes when its forward runs under
+ * torch.autocast(dtype=torch.bfloat16) (main/models/net.py:475, config/model/...: with_autocast: True).  fp32 stays the
+ * default; nothing above changes.  Numerical contract, the same for the kernels and the host twin:
+ *   - both operands of every dense weight product (K | V in-projection, attention out-projection, mlp.0, mlp.2, read-out) are
+ *     bf16, rounded to nearest even; the weights once, by wv_band_attn_bf16_prepare, from the fp32 state_dict tensors `p`
+ *     points to; activations where they are read as an operand;
+ *   - every product accumulates in fp32 (v_mfma_f32_32x32x16_bf16); the query projection, biases, residual adds, the softmax
+ *     over the band tokens, both LayerNorms and GELU are fp32; out is fp32 [B][E];
+ *   - feats: [S][B][E] as fp32 (WV_DT_F32) or bf16 (WV_DT_BF16), read in place -- no converted copy is made.
+ * The hashing tail stays fp32: wv_hash_tail takes this path's fp32 output as it takes the fp32 head's (the product is
+ * nbits x E, e.g. 64 x 384, and not worth a second kernel).
+ * Covers every configuration wv_band_attn_pool accepts with E % 32 == 0.  prepared blob (device memory, made again whenever
+ * q_eff, in_proj_*, attn_out_w, mlp0_w, mlp2_w or out_w change): the projected queries and the bf16 copies of the five weight
+ * matrices; p->q_proj and p->prepared are ignored.  wv_band_attn_bf16_prepared_bytes returns 0 for a configuration the
+ * path does not cover.  Errors: WV_EINVAL for E % 32 != 0, a null blob or an unknown feat_dtype (checked on the host before
+ * anything is launched), WV_ENOTSUP for a shape outside the kernels -- never a silent fp32 run.
+ * Host twin (HOST pointers, no blob: it rounds the weights itself): wv_band_attn_pool_cpu with the operands rounded as above
+ * and nothing else -- same fixed summation order, no rounding of intermediates between products.
+ * ------------------------------------------------------------------------------------------ */
+size_t wv_band_attn_bf16_prepared_bytes(const wv_head_params *p);
+int wv_band_attn_bf16_prepare(const wv_head_params *p, void *prepared_out, void *stream);
+size_t wv_band_attn_pool_bf16_workspace_bytes(const wv_head_params *p, int B);
+int wv_band_attn_pool_bf16(const wv_head_params *p, const void *prepared_bf16, const void *feats, int feat_dtype, int B,
+                           float *out, void *workspace, size_t workspace_bytes, void *stream);
+int wv_band_attn_pool_bf16_cpu(const wv_head_params *p, const void *feats, int feat_dtype, int B, float *out);
 
 #ifdef __cplusplus
 }
