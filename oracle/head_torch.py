@@ -33,8 +33,18 @@ def effective_queries(sd, normalize_queries=False, prefix=""):
 
 
 def band_attn_pool(features_list, sd, num_heads=8, pool="concat", normalize_queries=False,
-                   prefix="", return_weights=False, dtype=None):
-    """features_list: 4 x [B, E] (CLS feature per band LL, LH, HL, HH) -> [B, E]."""
+                   prefix="", return_weights=False, dtype=None, matrix_dtype=None):
+    """features_list: 4 x [B, E] (CLS feature per band LL, LH, HL, HH) -> [B, E].
+
+    matrix_dtype="bf16" states the numerical contract of the bf16 matrix-core head (include/wvhash.h,
+    wv_band_attn_pool_bf16): BOTH operands of the five dense weight products -- K | V in-projection,
+    attention out-projection, mlp.0, mlp.2, read-out -- are rounded to bf16 (torch's round to nearest
+    even, applied to the fp32 value of the operand) and nothing else is: the query projection, the
+    biases, q + attn_out, the attention core, both LayerNorms, GELU and the MLP residual keep `dtype`.
+    With dtype=torch.float64 that is the contract without accumulation error.  None: no rounding."""
+    if matrix_dtype not in (None, "bf16"):
+        raise ValueError(f"matrix_dtype must be None or 'bf16', got {matrix_dtype!r}")
+    r = (lambda t: t.float().bfloat16().to(t.dtype)) if matrix_dtype == "bf16" else (lambda t: t)
     g = lambda k: sd[prefix + k] if dtype is None else sd[prefix + k].to(dtype)
     feats = [f if dtype is None else f.to(dtype) for f in features_list]
     kv = torch.stack(feats, dim=1)                                  # [B, S=4, E]
@@ -46,21 +56,21 @@ def band_attn_pool(features_list, sd, num_heads=8, pool="concat", normalize_quer
     hd = E // num_heads
     w_in, b_in = g("attn.in_proj_weight"), g("attn.in_proj_bias")
     Q = q @ w_in[:E].t() + b_in[:E]
-    K = kv @ w_in[E:2 * E].t() + b_in[E:2 * E]
-    V = kv @ w_in[2 * E:].t() + b_in[2 * E:]
+    K = r(kv) @ r(w_in[E:2 * E]).t() + b_in[E:2 * E]
+    V = r(kv) @ r(w_in[2 * E:]).t() + b_in[2 * E:]
     Qh = Q.view(B, Nq, num_heads, hd).transpose(1, 2)               # [B, h, Nq, hd]
     Kh = K.view(B, S, num_heads, hd).transpose(1, 2)
     Vh = V.view(B, S, num_heads, hd).transpose(1, 2)
     scores = (Qh @ Kh.transpose(-1, -2)) / math.sqrt(hd)            # [B, h, Nq, S]
     P = torch.softmax(scores, dim=-1)
     ctx = (P @ Vh).transpose(1, 2).reshape(B, Nq, E)
-    attn_out = ctx @ g("attn.out_proj.weight").t() + g("attn.out_proj.bias")
+    attn_out = r(ctx) @ r(g("attn.out_proj.weight")).t() + g("attn.out_proj.bias")
     x = F.layer_norm(q + attn_out, (E,), g("norm1.weight"), g("norm1.bias"), 1e-5)
-    h = x @ g("mlp.0.weight").t() + g("mlp.0.bias")
+    h = r(x) @ r(g("mlp.0.weight")).t() + g("mlp.0.bias")
     h = F.gelu(h)                                                   # exact erf GELU
-    x = x + (h @ g("mlp.2.weight").t() + g("mlp.2.bias"))
+    x = x + (r(h) @ r(g("mlp.2.weight")).t() + g("mlp.2.bias"))
     x = x.mean(dim=1) if pool == "mean" else x.reshape(B, -1)
-    x = x @ g("out_proj.weight").t() + g("out_proj.bias")
+    x = r(x) @ r(g("out_proj.weight")).t() + g("out_proj.bias")
     out = F.layer_norm(x, (E,), g("norm2.weight"), g("norm2.bias"), 1e-5)
     if return_weights:
         return out, P.mean(dim=1)                                   # MHA averages heads

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import head_contract as hc
 from oracle import head_torch
 from wvhash import synth
 from wvhash.models import get_fusion_head, hash_tail, SharedDinoHashing, MultiDinoHashing
@@ -73,6 +74,52 @@ def test_batch_sizes_against_oracle(B, front, diag):
     assert (y.cpu() - ref).abs().max().item() < ATOL
     ref64 = head_torch.band_attn_pool(feats[:1] if False else feats, sd, 8, dtype=torch.float64)
     assert (y.cpu().double() - ref64).abs().max().item() < ATOL
+
+
+def run_fronts(head, dev, diag):
+    """The head's output with no pin and, where the configuration has a one-launch front, with either front pinned."""
+    outs = {}
+    with torch.no_grad():
+        diag.delenv("WV_HEAD_FRONT", raising=False)
+        outs["auto"] = head(dev).cpu()
+        if head._qproj_cache["blob"] is not None:
+            for front in ("0", "1"):
+                diag.setenv("WV_HEAD_FRONT", front)
+                outs[front] = head(dev).cpu()
+    return outs
+
+
+@pytest.mark.parametrize("B", [1, 17, 65, 129])
+@pytest.mark.parametrize("config", ["e32_h4_q3_concat", "e96_h8_q5_concat", "e160_h8_q3_mean", "e64_h4_q4_concat", "e384_h8_q7_mean"])
+def test_shape_sweep_against_the_fp64_oracle(config, B, diag):
+    """Embedding widths that are no multiple of the 64 / 96 / 128 tiles (32, 96, 160: column guards, K steps that are no
+    multiple of 64), query counts that divide neither 4 nor 8 (3, 5, 7: the broadcast residual row = output row mod Nq), the
+    mean read-out, and row counts 4B, B Nq, B on both sides of the 64 and 128 tile edges (tests/head_contract.py, the sweep
+    the bf16 head runs).  None of these configurations has a one-launch front; one that does runs under either pin too."""
+    ys = hc.yardstick(config, B)
+    head = hc.module(config).cuda()
+    assert head.matrix_dtype is None
+    for front, y in run_fronts(head, [f.cuda() for f in ys.feats], diag).items():
+        err = (y.double() - ys.plain64).abs().max().item()
+        print(f"{config} B={B} front={front}: max |y - fp64 oracle| = {err:.2e}")
+        assert err < ATOL, (config, B, front)
+
+
+@pytest.mark.parametrize("config,B", [("e96_h8_q5_concat", 65), ("e384_h8_q4_concat", 65), ("e384_h8_q4_concat", 120)])
+def test_a_row_does_not_depend_on_its_position(config, B, diag):
+    """Same B, same dispatch: permuting the samples permutes the output rows bit for bit, on the separate launches and on
+    the one-launch front (E = 384, Nq = 4 has one)."""
+    ys = hc.yardstick(config, B)
+    head = hc.module(config).cuda()
+    base = run_fronts(head, [f.cuda() for f in ys.feats], diag)
+    assert ("1" in base) == (config == "e384_h8_q4_concat")
+    perms = {"reversed": torch.arange(B - 1, -1, -1), "shuffled": torch.randperm(B, generator=torch.Generator().manual_seed(B))}
+    for name, perm in perms.items():
+        got = run_fronts(head, [f[perm].contiguous().cuda() for f in ys.feats], diag)
+        for front, y in base.items():
+            assert (y.double() - ys.plain64).abs().max().item() < ATOL, (config, B, front)
+            bad = (got[front] != y[perm]).any(dim=1).nonzero().flatten().tolist()
+            assert not bad, f"front={front}, {name}: rows {bad[:8]} of the permuted batch differ"
 
 
 @pytest.mark.parametrize("nq,heads,B", [(4, 8, 2048), (4, 8, 1155), (8, 8, 600), (4, 12, 100), (8, 6, 37), (4, 16, 9),

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from head_contract import check_gap_bounds
 from oracle import head_torch
 from wvhash import synth
 
@@ -40,6 +41,26 @@ def test_fp64_restatement_bounds_fp32_error(gold):
     sd, feats, heads, pool, dec = rebuild(gold, "adv_e384_nq4")
     y64 = head_torch.band_attn_pool(feats, sd, heads, pool, dtype=torch.float64)
     assert np.abs(y64.numpy() - gold["adv_e384_nq4/out"]).max() < 1e-5
+
+
+def test_bf16_emulation_is_a_bf16_head_by_the_reference_gap(golden_dir):
+    """matrix_dtype="bf16" evaluated in fp32 sits inside the gap between the reference module's own fp32 and bf16-autocast
+    runs on the seven golden cases (the three bounds the kernel and the host twin are held to in tests/test_host_head_bf16.py),
+    and matrix_dtype=None is the restatement as it was, bit for bit."""
+    g16 = np.load(f"{golden_dir}/head_bf16_golden.npz")
+    names = head_cases(g16)
+    assert len(names) == 7
+    for n in names:
+        sd, feats, heads, pool, dec = rebuild(g16, n)
+        feats = [f.bfloat16().float() for f in feats]                 # the fixture's inputs are bf16-representable
+        kw = dict(num_heads=heads, pool=pool, normalize_queries=dec)
+        plain = head_torch.band_attn_pool(feats, sd, **kw)
+        assert torch.equal(head_torch.band_attn_pool(feats, sd, matrix_dtype=None, **kw), plain)
+        y = head_torch.band_attn_pool(feats, sd, matrix_dtype="bf16", **kw)
+        assert y.dtype == torch.float32
+        check_gap_bounds(y, plain, torch.from_numpy(g16[n + "/out32"]), g16[n + "/gap"], n)
+    with pytest.raises(ValueError, match="matrix_dtype"):
+        head_torch.band_attn_pool(feats, sd, matrix_dtype="fp16", **kw)
 
 
 def test_hash_tail_matches_reference_modules(gold):
