@@ -15,18 +15,11 @@
 // 4 or 8 queries) and batches that fill the chip, everything before the read-out is ONE kernel
 // (head_front.hip) fed by a weight stream wv_band_attn_prepare makes once per parameter update; the
 // batch-invariant query projection is likewise made once (wv_band_attn_qproj) and cached by the module.
-#include "common.hpp"
+#include "head.hpp"
 
 namespace wv {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;   // native vector: arrays of it stay in registers
-
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_ADD_ROW = 2, EPI_ADD_BCAST = 3 };
-
-// C[M][N] = epi(A[M][K] . W[N][K]^T + bias[N])
-//   EPI_ADD_ROW   : + R[m][n]                    (residual of the same shape)
-//   EPI_ADD_BCAST : + R[(m % rmod)][n]           (query tokens broadcast over the batch)
+// C[M][N] = epi(A[M][K] . W[N][K]^T + bias[N]), epilogues: head.hpp (store_block, GELU through erff).
 // Wave tile = (32*TM) x (32*TN); workgroup = 2 x 2 waves.  Same operand scheme as k_scores
 // (knn_float.hip): lane l feeds row l&31, lane half h covers k in [8c+4h, 8c+4h+4).
 template <int TM, int TN, int EPI>
@@ -72,21 +65,8 @@ __global__ __launch_bounds__(256) void k_gemm_nt(const float *__restrict__ A, co
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
-        for (int b = 0; b < TN; ++b) {
-            const int64_t col = j0 + b * 32 + r;
-            if (col >= N) continue;
-            const float bs = bias ? bias[col] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int64_t row = i0 + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (row >= M) continue;
-                float v = acc[a][b][e] + bs;
-                if (EPI == EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-                if (EPI == EPI_ADD_ROW) v += R[row * N + col];
-                if (EPI == EPI_ADD_BCAST) v += R[(int64_t)((uint32_t)row % (uint32_t)rmod) * N + col];   // rows < 2^31 (host check)
-                C[row * N + col] = v;
-            }
-        }
+        for (int b = 0; b < TN; ++b)
+            store_block<EPI, true, true>(acc[a][b], i0 + a * 32 + 4 * h, j0 + b * 32 + r, bias, R, rmod, C, M, N);
 }
 
 // LDS-tiled variant for K % 32 == 0: block tile BM x BN, K step 32, two LDS stages (global loads of step
@@ -185,21 +165,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_lds(const float *__restrict__ A
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
-        for (int b = 0; b < TN; ++b) {
-            const int64_t col = n0 + wn + b * 32 + r;
-            if (col >= N) continue;
-            const float bsv = bias ? bias[col] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int64_t row = m0 + wm + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (row >= M) continue;
-                float v = acc[a][b][e] + bsv;
-                if (EPI == EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-                if (EPI == EPI_ADD_ROW) v += R[row * N + col];
-                if (EPI == EPI_ADD_BCAST) v += R[(int64_t)((uint32_t)row % (uint32_t)rmod) * N + col];   // rows < 2^31 (host check)
-                C[row * N + col] = v;
-            }
-        }
+        for (int b = 0; b < TN; ++b)
+            store_block<EPI, true, true>(acc[a][b], m0 + wm + a * 32 + 4 * h, n0 + wn + b * 32 + r, bias, R, rmod, C, M, N);
 }
 
 // Row-panel variant: block tile 128 x 96, 4 waves stacked along M, wave tile 32 x 96 = three independent 32 x 32
@@ -332,48 +299,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm_panel(const float *__restrict__
         }
         __syncthreads();
     }
-    if (m0 + BM <= M && n0 + BN <= N) {
-        // interior tile: no bounds checks, so all residual loads of an accumulator are in flight together
-        // (the guarded form below waits for each load before it issues the next)
-        const int64_t row0 = m0 + wv * 32 + 4 * h;
+    const int64_t row0 = m0 + wv * 32 + 4 * h, col0 = n0 + r;
+    if (m0 + BM <= M && n0 + BN <= N) {   // interior tile: the unguarded epilogue
 #pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            const int64_t col = n0 + b * 32 + r;
-            const float bsv = bias ? bias[col] : 0.f;
-            float res[16];
+        for (int b = 0; b < 3; ++b) store_block<EPI, false, true>(acc[b], row0, col0 + b * 32, bias, R, rmod, C, M, N);
+    } else {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int64_t row = row0 + (e & 3) + 8 * (e >> 2);
-                if (EPI == EPI_ADD_ROW) res[e] = R[row * N + col];
-                else if (EPI == EPI_ADD_BCAST) res[e] = R[(int64_t)((uint32_t)row % (uint32_t)rmod) * N + col];
-                else res[e] = 0.f;
-            }
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int64_t row = row0 + (e & 3) + 8 * (e >> 2);
-                float v = acc[b][e] + bsv;
-                if (EPI == EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-                if (EPI == EPI_ADD_ROW || EPI == EPI_ADD_BCAST) v += res[e];
-                C[row * N + col] = v;
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        const int64_t col = n0 + b * 32 + r;
-        if (col >= N) continue;
-        const float bsv = bias ? bias[col] : 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int64_t row = m0 + wv * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (row >= M) continue;
-            float v = acc[b][e] + bsv;
-            if (EPI == EPI_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-            if (EPI == EPI_ADD_ROW) v += R[row * N + col];
-            if (EPI == EPI_ADD_BCAST) v += R[(int64_t)((uint32_t)row % (uint32_t)rmod) * N + col];   // rows < 2^31 (host check)
-            C[row * N + col] = v;
-        }
+        for (int b = 0; b < 3; ++b) store_block<EPI, true, true>(acc[b], row0, col0 + b * 32, bias, R, rmod, C, M, N);
     }
 }
 
@@ -733,6 +665,14 @@ __global__ __launch_bounds__(256) void k_hash_tail_mfma(const float *__restrict_
         reinterpret_cast<uint32_t *>(packed_out)[((size_t)(b0 + lane) * words + (n >> 1)) * 2 + 1] = 0u;
 }
 
+template <int TM, int TN, int EPI>
+static void launch_gemm_nt(const float *A, const float *W, const float *bias, const float *R, int rmod, float *C,
+                           int M, int N, int K, hipStream_t st)
+{
+    dim3 grid((unsigned)ceil_div(N, 64 * TN), (unsigned)ceil_div(M, 64 * TM));
+    hipLaunchKernelGGL((k_gemm_nt<TM, TN, EPI>), grid, dim3(256), 0, st, A, W, bias, R, rmod, C, M, N, K);
+}
+
 template <int BM, int BN, int EPI>
 static void launch_gemm_lds(const float *A, const float *W, const float *bias, const float *R, int rmod, float *C,
                             int M, int N, int K, hipStream_t st)
@@ -747,7 +687,7 @@ static void launch_gemm_lds(const float *A, const float *W, const float *bias, c
 
 template <int BK, int EPI>
 static void launch_gemm_panel(const float *A, const float *W, const float *bias, const float *R, int rmod, float *C,
-                              int M, int N, int K, hipStream_t st, int ksplit = 1)
+                              int M, int N, int K, int ksplit, hipStream_t st)
 {
     constexpr size_t lds = (size_t)2 * (128 + 96) * (BK + 4) * sizeof(float);
     auto kern = k_gemm_panel<BK, EPI>;
@@ -757,133 +697,42 @@ static void launch_gemm_panel(const float *A, const float *W, const float *bias,
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, A, W, bias, R, rmod, C, M, N, K, K / ksplit);
 }
 
-// Slices the read-out product would be cut into (1 = no split): short-M products leave most CUs without a
-// panel, so K is cut until about every CU has one.  C must then hold that many [M][N] partials.
-static int readout_ksplit(int M, int N, int K)
-{
-    if (::wv::tune("WV_GEMM") || K % 64 || N % 96 || M < 128) return 1;
-    const int64_t panels = ceil_div(M, 128) * ceil_div(N, 96);
-    for (int ks = 8; ks >= 2; ks >>= 1)
-        if (K % (ks * 64) == 0 && K / ks >= 128 && panels * ks <= 384) return ks;
-    return 1;
-}
-
-template <int EPI>
-static void launch_gemm(const float *A, const float *W, const float *bias, const float *R, int rmod,
-                        float *C, int M, int N, int K, hipStream_t st)
-{
-    const char *force = ::wv::tune("WV_GEMM");   // "stream" / "lds" / "panel32" / "panel64" pin a kernel (tests / tuning)
-    const int64_t panels = ceil_div(M, 128) * ceil_div(N, 96);
-    const bool panel_ok = K % 64 == 0 && N % 96 == 0 && M >= 128;
-    if (panel_ok && force && !strcmp(force, "panel32")) return launch_gemm_panel<32, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
-    if (panel_ok && force && !strcmp(force, "panel64")) return launch_gemm_panel<64, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
-    if (panel_ok && !force && panels >= 256) {
-        // one workgroup per CU: nothing else hides the stage hand-over, so take the long K step
-        if (panels < 512) return launch_gemm_panel<64, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
-        return launch_gemm_panel<32, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
+// the fp32 precision of head_run_stages: the kernel head_plan chose for the product, nothing decided here
+struct PathF32 {
+    using Hidden = float;
+    template <int EPI>
+    static void gemm(GemmPlan g, const float *A, const float *W, const float *bias, const float *R, int rmod, float *C, int M,
+                     int N, int K, hipStream_t st)
+    {
+        switch (g.kernel) {
+        case Gemm::nt64: return launch_gemm_nt<1, 1, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
+        case Gemm::nt128: return launch_gemm_nt<2, 2, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
+        case Gemm::lds64: return launch_gemm_lds<64, 64, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
+        case Gemm::lds128x64: return launch_gemm_lds<128, 64, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
+        case Gemm::lds128: return launch_gemm_lds<128, 128, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
+        case Gemm::panel32: return launch_gemm_panel<32, EPI>(A, W, bias, R, rmod, C, M, N, K, g.ksplit, st);
+        case Gemm::panel64: return launch_gemm_panel<64, EPI>(A, W, bias, R, rmod, C, M, N, K, g.ksplit, st);
+        default: return;   // a bf16 kernel: head_plan(HeadPrec::f32) never answers one
+        }
     }
-    // measured on MI355X at the head's shapes: short-K, wide-N products (mlp.0: K=384, N=1536) run faster on
-    // the LDS-free kernel (118 vs 142 us); everything else on the LDS-tiled one
-    const bool prefer_stream = ((K <= 512 && N >= 1024) && !(force && !strcmp(force, "lds"))) || (force && !strcmp(force, "stream"));
-    if (K % 32 == 0 && M >= 64 && !prefer_stream) {
-        // largest tile that still gives every CU about two workgroups
-        if (ceil_div(M, 128) * ceil_div(N, 128) >= 512) return launch_gemm_lds<128, 128, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
-        if (ceil_div(M, 128) * ceil_div(N, 64) >= 384) return launch_gemm_lds<128, 64, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
-        return launch_gemm_lds<64, 64, EPI>(A, W, bias, R, rmod, C, M, N, K, st);
-    }
-    // big tile when it still yields >= 256 workgroups, else the small one
-    const int64_t big = ceil_div(M, 128) * ceil_div(N, 128);
-    if (big >= 256) {
-        dim3 grid((unsigned)ceil_div(N, 128), (unsigned)ceil_div(M, 128));
-        hipLaunchKernelGGL((k_gemm_nt<2, 2, EPI>), grid, dim3(256), 0, st, A, W, bias, R, rmod, C, M, N, K);
-    } else {
-        dim3 grid((unsigned)ceil_div(N, 64), (unsigned)ceil_div(M, 64));
-        hipLaunchKernelGGL((k_gemm_nt<1, 1, EPI>), grid, dim3(256), 0, st, A, W, bias, R, rmod, C, M, N, K);
-    }
-}
-
-struct HeadWs {
-    float *Qp, *KV, *ctx, *x1, *x1n, *hid, *x2, *pooled, *pre;
-    size_t bytes;
 };
 
-static HeadWs carve(const wv_head_params *p, int B, void *base)
-{
-    const size_t E = p->embed_dim, Nq = p->num_queries, S = p->num_tokens;
-    const size_t rows = (size_t)B * Nq;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        float *r = base ? (float *)((char *)base + off) : nullptr;
-        off += align_up((int64_t)(n * sizeof(float)), 256);
-        return r;
-    };
-    HeadWs w;
-    w.Qp = take(Nq * E);
-    w.KV = take(S * B * 2 * E);
-    w.ctx = take(rows * E);
-    w.x1 = take(rows * E);
-    w.x1n = take(rows * E);
-    w.hid = take(rows * 4 * E);
-    w.x2 = take(rows * E);
-    w.pooled = take((size_t)B * E);
-    w.pre = take((size_t)B * E * 8);   // up to 8 split-K partials of the read-out product
-    w.bytes = off;
-    return w;
-}
-
-// head_front.hip: the fused front (band features -> x2 in one launch) and its prepared weight stream
-size_t head_front_prepared_bytes(const wv_head_params *p);
-int head_front_prepare(const wv_head_params *p, void *prepared, hipStream_t st);
-int head_front_launch(const wv_head_params *p, const float *feats, int B, float *x2, int mode, hipStream_t st);
-
-}  // namespace wv
-
-using namespace wv;
-
-static int check_head(const wv_head_params *p, int B)
-{
-    WV_REQUIRE(p, "band_attn_pool: null params");
-    WV_REQUIRE(B >= 0, "band_attn_pool: B=%d", B);
-    WV_REQUIRE(p->embed_dim >= 8 && p->embed_dim % 8 == 0, "band_attn_pool: embed_dim=%d must be a multiple of 8",
-               p->embed_dim);
-    WV_REQUIRE(p->num_heads >= 1 && p->embed_dim % p->num_heads == 0,
-               "band_attn_pool: embed_dim %d not divisible by num_heads %d", p->embed_dim, p->num_heads);
-    WV_REQUIRE(p->num_queries >= 1 && p->num_queries <= 64, "band_attn_pool: num_queries=%d", p->num_queries);
-    WV_REQUIRE(p->num_tokens >= 1 && p->num_tokens <= 64, "band_attn_pool: num_tokens=%d", p->num_tokens);
-    WV_REQUIRE(p->q_eff && p->in_proj_w && p->in_proj_b && p->attn_out_w && p->attn_out_b && p->norm1_w &&
-                   p->norm1_b && p->mlp0_w && p->mlp0_b && p->mlp2_w && p->mlp2_b && p->out_w && p->out_b &&
-                   p->norm2_w && p->norm2_b,
-               "band_attn_pool: null weight pointer");
-    return WV_OK;
-}
-
-// head_bf16.hip runs the stages that stay fp32 in either precision through these
-namespace wv {
-
-int head_check_params(const wv_head_params *p, int B) { return check_head(p, B); }
-
-void head_launch_qproj(const wv_head_params *p, float *Qp, hipStream_t st)
+void launch_qproj(const wv_head_params *p, float *Qp, hipStream_t st)
 {
     hipLaunchKernelGGL(k_qproj, dim3((unsigned)ceil_div(p->num_queries * p->embed_dim, 4)), dim3(256), 0, st, p->q_eff,
                        p->in_proj_w, p->in_proj_b, Qp, p->num_queries, p->embed_dim);
 }
 
-size_t head_attn_core_lds(const wv_head_params *p)
+void launch_attn_core(const wv_head_params *p, const HeadPlan &pl, const float *Qp, const float *KV, float *ctx, int B, hipStream_t st)
 {
-    const size_t E = p->embed_dim, Nq = p->num_queries, S = p->num_tokens;
-    return (S * (2 * E + 4) + Nq * E + Nq * p->num_heads * S) * sizeof(float);
+    if (pl.attn_lds > 64 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_attn_core), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)pl.attn_lds);
+    hipLaunchKernelGGL(k_attn_core, dim3(B), dim3(256), pl.attn_lds, st, Qp, KV, ctx, B, p->embed_dim, p->num_heads,
+                       p->num_queries, p->num_tokens);
 }
 
-void head_launch_attn_core(const wv_head_params *p, const float *Qp, const float *KV, float *ctx, int B, hipStream_t st)
-{
-    const size_t sm = head_attn_core_lds(p);
-    if (sm > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_attn_core), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    hipLaunchKernelGGL(k_attn_core, dim3(B), dim3(256), sm, st, Qp, KV, ctx, B, p->embed_dim, p->num_heads, p->num_queries,
-                       p->num_tokens);
-}
-
-void head_launch_mean_rows(const float *x, float *y, int64_t groups, int n, int E, hipStream_t st)
+void launch_mean_rows(const float *x, float *y, int64_t groups, int n, int E, hipStream_t st)
 {
     hipLaunchKernelGGL(k_mean_rows, dim3((unsigned)std::min<int64_t>(ceil_div(groups * E, 256), 4096)), dim3(256), 0, st, x, y,
                        groups, n, E);
@@ -891,91 +740,65 @@ void head_launch_mean_rows(const float *x, float *y, int64_t groups, int n, int 
 
 }  // namespace wv
 
+using namespace wv;
+
 extern "C" size_t wv_band_attn_pool_workspace_bytes(const wv_head_params *p, int B)
 {
-    if (!p || B <= 0) return 0;
-    return carve(p, B, nullptr).bytes;
+    return head_plan(p, B, HeadPrec::f32).ws.bytes;
 }
 
 extern "C" int wv_band_attn_qproj(const wv_head_params *p, float *q_proj_out, void *stream)
 {
-    int rc = check_head(p, 1);
-    if (rc) return rc;
+    HeadPlan pl{};
+    if (!head_check_params(p, 1, pl)) WV_FAIL(pl.rc, "%s", pl.why);
     WV_REQUIRE(q_proj_out, "band_attn_qproj: null buffer");
-    hipLaunchKernelGGL(k_qproj, dim3((unsigned)ceil_div(p->num_queries * p->embed_dim, 4)), dim3(256), 0, (hipStream_t)stream,
-                       p->q_eff, p->in_proj_w, p->in_proj_b, q_proj_out, p->num_queries, p->embed_dim);
+    launch_qproj(p, q_proj_out, (hipStream_t)stream);
     WV_CHECK_LAUNCH("k_qproj");
     return WV_OK;
 }
 
 extern "C" size_t wv_band_attn_prepared_bytes(const wv_head_params *p)
 {
-    if (!p || check_head(p, 1)) return 0;
+    if (!p) return 0;
+    const HeadPlan pl = head_plan(p, 1, HeadPrec::f32);
+    if (pl.rc) {
+        set_error("%s", pl.why);
+        return 0;
+    }
     return head_front_prepared_bytes(p);
 }
 
 extern "C" int wv_band_attn_prepare(const wv_head_params *p, void *prepared_out, void *stream)
 {
-    int rc = check_head(p, 1);
-    if (rc) return rc;
+    HeadPlan pl{};
+    if (!head_check_params(p, 1, pl)) WV_FAIL(pl.rc, "%s", pl.why);
     WV_REQUIRE(prepared_out, "band_attn_prepare: null buffer");
+    if (!head_front_has_kernel(p))
+        WV_FAIL(WV_ENOTSUP, "band_attn_prepare: no fused kernel for E=%d S=%d Nq=%d heads=%d", p->embed_dim, p->num_tokens,
+                p->num_queries, p->num_heads);
     return head_front_prepare(p, prepared_out, (hipStream_t)stream);
 }
 
 extern "C" int wv_band_attn_pool(const wv_head_params *p, const float *feats, int B, float *out,
                                  void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = check_head(p, B);
-    if (rc) return rc;
+    const HeadPlan pl = head_plan(p, B, HeadPrec::f32);
+    if (pl.rc) WV_FAIL(pl.rc, "%s", pl.why);
     WV_REQUIRE(feats && out, "band_attn_pool: null buffer");
     WV_REQUIRE((int64_t)B * std::max(p->num_queries, p->num_tokens) < (1ll << 31), "band_attn_pool: B=%d too large", B);
     if (B == 0) return WV_OK;
-    const size_t need = carve(p, B, nullptr).bytes;
-    if (!workspace || workspace_bytes < need)
-        WV_FAIL(WV_ENOMEM, "band_attn_pool: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (!workspace || workspace_bytes < pl.ws.bytes)
+        WV_FAIL(WV_ENOMEM, "band_attn_pool: workspace %zu < %zu bytes", workspace_bytes, pl.ws.bytes);
     hipStream_t st = (hipStream_t)stream;
-    const int E = p->embed_dim, Nq = p->num_queries, S = p->num_tokens, rows = B * Nq;
-    HeadWs w = carve(p, B, workspace);
-
-    // prepared weights: everything up to x2 in one launch when the batch fills the chip (WV_HEAD_FRONT=0 / 1 pins
-    // the separate launches / the one-launch front for tests and A/B runs)
-    const char *pin = ::wv::tune("WV_HEAD_FRONT");
-    const int mode = pin && !strcmp(pin, "0") ? 0 : pin && !strcmp(pin, "1") ? 1 : -1;
-    const bool fused = p->prepared && head_front_launch(p, feats, B, w.x2, mode, st);
-    if (!fused) {
-        // Q projection (batch-invariant): Qp = q_eff @ Wq^T + bq -- taken from the caller when it was made ahead of time
-        const float *Qp = p->q_proj ? p->q_proj : reinterpret_cast<const float *>(p->prepared);   // the blob starts with it
-        if (!Qp) {
-            hipLaunchKernelGGL(k_qproj, dim3((unsigned)ceil_div(Nq * E, 4)), dim3(256), 0, st, p->q_eff, p->in_proj_w,
-                               p->in_proj_b, w.Qp, Nq, E);
-            Qp = w.Qp;
-        }
-        // K | V projection of all S*B tokens: rows E..3E of in_proj_weight
-        launch_gemm<EPI_NONE>(feats, p->in_proj_w + (size_t)E * E, p->in_proj_b + E, nullptr, 1, w.KV, S * B, 2 * E, E, st);
-        const size_t sm = ((size_t)S * (2 * E + 4) + (size_t)Nq * E + (size_t)Nq * p->num_heads * S) * sizeof(float);
-        if (sm > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_attn_core), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-        hipLaunchKernelGGL(k_attn_core, dim3(B), dim3(256), sm, st, Qp, w.KV, w.ctx, B, E, p->num_heads, Nq, S);
-        // x1 = q_eff + ctx @ Wo^T + bo ; x1n = LN1(x1)
-        launch_gemm<EPI_ADD_BCAST>(w.ctx, p->attn_out_w, p->attn_out_b, p->q_eff, Nq, w.x1, rows, E, E, st);
-        launch_layernorm(w.x1, p->norm1_w, p->norm1_b, w.x1n, (int64_t)rows, E, p->ln_eps, 1, st);
-        // x2 = x1n + GELU(x1n @ W0^T + b0) @ W2^T + b2
-        launch_gemm<EPI_GELU>(w.x1n, p->mlp0_w, p->mlp0_b, nullptr, 1, w.hid, rows, 4 * E, E, st);
-        launch_gemm<EPI_ADD_ROW>(w.hid, p->mlp2_w, p->mlp2_b, w.x1n, 1, w.x2, rows, E, 4 * E, st);
+    // Q projection (batch-invariant): Qp = q_eff @ Wq^T + bq -- taken from the caller when it was made ahead of time
+    const float *Qp = p->q_proj ? p->q_proj : reinterpret_cast<const float *>(p->prepared);   // the blob starts with it
+    if (!Qp && !pl.front) {
+        launch_qproj(p, ws_at<float>(workspace, pl.ws.Qp), st);
+        Qp = ws_at<float>(workspace, pl.ws.Qp);
     }
-    // read-out: concat (a [B][Nq*E] view of x2) or mean over the queries, then Linear + LN2
-    const float *ro_in = w.x2;
-    int ro_k = Nq * E;
-    if (p->pool_mean) {
-        hipLaunchKernelGGL(k_mean_rows, dim3((unsigned)std::min<int64_t>(ceil_div((int64_t)B * E, 256), 4096)),
-                           dim3(256), 0, st, w.x2, w.pooled, (int64_t)B, Nq, E);
-        ro_in = w.pooled;
-        ro_k = E;
-    }
-    const int ks = readout_ksplit(B, E, ro_k);
-    if (ks > 1) launch_gemm_panel<64, EPI_NONE>(ro_in, p->out_w, p->out_b, nullptr, 1, w.pre, B, E, ro_k, st, ks);
-    else launch_gemm<EPI_NONE>(ro_in, p->out_w, p->out_b, nullptr, 1, w.pre, B, E, ro_k, st);
-    launch_layernorm(w.pre, p->norm2_w, p->norm2_b, out, (int64_t)B, E, p->ln_eps, ks, st);
+    const size_t E = p->embed_dim;
+    const HeadWeights<float> w{p->in_proj_w + E * E, p->attn_out_w, p->mlp0_w, p->mlp2_w, p->out_w};
+    head_run_stages<PathF32>(p, pl, w, Qp, feats, B, out, workspace, st);
     WV_CHECK_LAUNCH("band_attn_pool");
     return WV_OK;
 }
@@ -992,7 +815,7 @@ extern "C" int wv_hash_tail(const float *fused, int B, int E, const float *hash_
     if (B == 0) return WV_OK;
     const size_t lds16 = ((size_t)4 * E * 4 + (size_t)E * 65) * sizeof(float);
     const char *pin = ::wv::tune("WV_HASH_TAIL");                   // "simple" / "valu16" / "mfma" pin a kernel (tests, A/B runs)
-    const bool simple = ::wv::tune("WV_HASH_TAIL_SIMPLE") || (pin && !strcmp(pin, "simple"));
+    const bool simple = pin && !strcmp(pin, "simple");
     if (!simple && !(pin && !strcmp(pin, "valu16")) && E % 32 == 0 && (B >= 32 || (pin && !strcmp(pin, "mfma")))) {
         const dim3 grid((unsigned)ceil_div(B, 32), (unsigned)ceil_div(nbits, 32));
         hipLaunchKernelGGL(k_hash_tail_mfma, grid, dim3(256), 0, (hipStream_t)stream, fused, B, E, hash_w, hash_b, bn_w, bn_b,

@@ -12,24 +12,11 @@
 // as rounding it when it is read.  The attention core, LayerNorm and mean-pool kernels are head.hip's (fp32 in/out).
 // Weights are converted once (wv_band_attn_bf16_prepare), activations where they are staged as an operand; band
 // features are taken as fp32 or bf16 and never copied.
-#include "common.hpp"
+#include "head.hpp"
 
 namespace wv {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_ADD_ROW = 2, EPI_ADD_BCAST = 3 };
-
-// head.hip: the stages both precisions share
-int head_check_params(const wv_head_params *p, int B);
-void head_launch_qproj(const wv_head_params *p, float *Qp, hipStream_t st);
-size_t head_attn_core_lds(const wv_head_params *p);
-void head_launch_attn_core(const wv_head_params *p, const float *Qp, const float *KV, float *ctx, int B, hipStream_t st);
-void head_launch_mean_rows(const float *x, float *y, int64_t groups, int n, int E, hipStream_t st);
-void launch_layernorm(const float *x, const float *w, const float *b, float *y, int64_t rows, int E, float eps, int nparts,
-                      hipStream_t st);
 
 // eight consecutive operand elements on their way global -> registers -> LDS: fp32 sources are rounded when they are
 // written to LDS, bf16 sources pass through
@@ -58,44 +45,7 @@ template <> struct Raw8<__bf16> {
     __device__ __forceinline__ bf16x8 packed() const { return v; }
 };
 
-// Epilogue of one 32 x 32 accumulator block: element e of this lane is row row0 + (e & 3) + 8 (e >> 2), column col.
-// GUARD = false (interior tiles): no bounds checks, so the 16 residual loads are in flight together; the guarded form
-// waits for each load before it issues the next.
-template <int EPI, bool GUARD, typename TC>
-__device__ __forceinline__ void store_block(const f32x16 &acc, int64_t row0, int64_t col, const float *__restrict__ bias,
-                                            const float *__restrict__ R, int rmod, TC *__restrict__ C, int M, int N)
-{
-    if (GUARD && col >= N) return;
-    const float bsv = bias ? bias[col] : 0.f;
-    float res[16];
-    if (EPI == EPI_ADD_BCAST) {
-        // R row = output row mod rmod, carried along the lane's rows (steps of 1, 1, 1, 5) instead of 16 divisions
-        const uint32_t m = (uint32_t)rmod, d1 = 1u % m, d5 = 5u % m;   // rows < 2^31 (host check)
-        uint32_t q = (uint32_t)row0 % m;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            res[e] = GUARD && row0 + (e & 3) + 8 * (e >> 2) >= M ? 0.f : R[(int64_t)q * N + col];
-            q += (e & 3) == 3 ? d5 : d1;
-            q -= q >= m ? m : 0u;
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int64_t row = row0 + (e & 3) + 8 * (e >> 2);
-            res[e] = EPI == EPI_ADD_ROW && !(GUARD && row >= M) ? R[row * N + col] : 0.f;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int64_t row = row0 + (e & 3) + 8 * (e >> 2);
-        float v = acc[e] + bsv;
-        if (EPI == EPI_GELU) v = gelu_erf(v);
-        if (EPI == EPI_ADD_ROW || EPI == EPI_ADD_BCAST) v += res[e];
-        if (!GUARD || row < M) C[row * N + col] = (TC)v;
-    }
-}
-
-// C[M][N] = epi(A[M][K] . W[N][K]^T + bias[N]), A fp32 or bf16, W bf16, C fp32 or bf16; epilogues as k_gemm_nt.
+// C[M][N] = epi(A[M][K] . W[N][K]^T + bias[N]), A fp32 or bf16, W bf16, C fp32 or bf16; epilogues: head.hpp (store_block, GELU through gelu_erf()).
 // Block tile BM x BN (64 x 64 or 128 x 128), 4 waves as 2 x 2, wave tile in 32 x 32 blocks of v_mfma_f32_32x32x16_bf16:
 // lane (r, h) feeds row r with k in [16 s + 8 h, 16 s + 8 h + 8) of MFMA s of a BK-wide K step (BK = 32 or 64) -- one
 // 16-byte LDS read per fragment.  Two LDS stages; rows are padded by 8 bf16 (pitch 80 or 144 bytes): 16 lanes = 16 rows
@@ -226,12 +176,12 @@ __global__ __launch_bounds__(256) void k_gemm_bf16(const TA *__restrict__ A, con
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
-            for (int b = 0; b < TN; ++b) store_block<EPI, false>(acc[a][b], row0 + a * 32, col0 + b * 32, bias, R, rmod, C, M, N);
+            for (int b = 0; b < TN; ++b) store_block<EPI, false, false>(acc[a][b], row0 + a * 32, col0 + b * 32, bias, R, rmod, C, M, N);
     } else {
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
-            for (int b = 0; b < TN; ++b) store_block<EPI, true>(acc[a][b], row0 + a * 32, col0 + b * 32, bias, R, rmod, C, M, N);
+            for (int b = 0; b < TN; ++b) store_block<EPI, true, false>(acc[a][b], row0 + a * 32, col0 + b * 32, bias, R, rmod, C, M, N);
     }
 }
 
@@ -257,33 +207,22 @@ static void launch_tile(const TA *A, const __bf16 *W, const float *bias, const f
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, A, W, bias, R, rmod, C, M, N, K, K / ksplit);
 }
 
-// ksplit > 1: C receives that many [M][N] partial products (see k_gemm_bf16); K / ksplit must be a multiple of 64
-template <int EPI, typename TA, typename TC>
-static void launch_gemm_bf16(const TA *A, const __bf16 *W, const float *bias, const float *R, int rmod, TC *C, int M, int N,
-                             int K, hipStream_t st, int ksplit = 1)
-{
-    // 128 x 128 tiles when they still give every CU one; the 64-wide K step whenever K allows it.  WV_HEAD_BF16=tile64 /
-    // tile128 and WV_HEAD_BF16_BK=32 pin a variant (tests, A/B runs)
-    const char *pin = ::wv::tune("WV_HEAD_BF16"), *pin_bk = ::wv::tune("WV_HEAD_BF16_BK");
-    bool big = ceil_div(M, 128) * ceil_div(N, 128) >= 256;
-    if (pin && !strcmp(pin, "tile64")) big = false;
-    if (pin && !strcmp(pin, "tile128")) big = true;
-    const bool bk64 = (K / ksplit) % 64 == 0 && !(pin_bk && !strcmp(pin_bk, "32"));
-    if (big) launch_tile<128, 128, 32, EPI>(A, W, bias, R, rmod, C, M, N, K, ksplit, st);   // the 64-wide step costs it a workgroup per CU
-    else if (bk64) launch_tile<64, 64, 64, EPI>(A, W, bias, R, rmod, C, M, N, K, ksplit, st);
-    else launch_tile<64, 64, 32, EPI>(A, W, bias, R, rmod, C, M, N, K, ksplit, st);
-}
-
-// Slices the read-out product is cut into (1 = no split): M = B rows give few tiles, so K is cut until about every CU has
-// a few workgroups.  C must then hold that many [M][N] partials.
-static int readout_ksplit_bf16(int M, int N, int K)
-{
-    if (ceil_div(M, 128) * ceil_div(N, 128) >= 256) return 1;
-    const int64_t tiles = ceil_div(M, 64) * ceil_div(N, 64);
-    for (int ks = 8; ks >= 2; ks >>= 1)
-        if (K % (ks * 64) == 0 && K / ks >= 128 && tiles * ks <= 1024) return ks;
-    return 1;
-}
+// the bf16 precision of head_run_stages: the tile head_plan chose for the product, nothing decided here.
+// ksplit > 1: C receives that many [M][N] partial products (see k_gemm_bf16); K / ksplit is then a multiple of 64
+struct PathBf16 {
+    using Hidden = __bf16;
+    template <int EPI, typename TA, typename TC>
+    static void gemm(GemmPlan g, const TA *A, const __bf16 *W, const float *bias, const float *R, int rmod, TC *C, int M, int N,
+                     int K, hipStream_t st)
+    {
+        switch (g.kernel) {
+        case Gemm::bf128k32: return launch_tile<128, 128, 32, EPI>(A, W, bias, R, rmod, C, M, N, K, g.ksplit, st);
+        case Gemm::bf64k64: return launch_tile<64, 64, 64, EPI>(A, W, bias, R, rmod, C, M, N, K, g.ksplit, st);
+        case Gemm::bf64k32: return launch_tile<64, 64, 32, EPI>(A, W, bias, R, rmod, C, M, N, K, g.ksplit, st);
+        default: return;   // an fp32 kernel: head_plan(HeadPrec::bf16) never answers one
+        }
+    }
+};
 
 // prepared blob: [Qp fp32 Nq*E | in_proj rows E..3E | attn_out | mlp.0 | mlp.2 | out_proj], weights bf16, 256-byte aligned
 struct Bf16Blob {
@@ -312,65 +251,30 @@ static Bf16Blob carve_blob(const wv_head_params *p, void *base)
     return b;
 }
 
-struct Bf16Ws {
-    float *KV, *ctx, *x1, *x1n, *x2, *pooled, *pre;
-    __bf16 *hid;
-    size_t bytes;
-};
-
-static Bf16Ws carve_ws(const wv_head_params *p, int B, void *base)
-{
-    const size_t E = p->embed_dim, Nq = p->num_queries, S = p->num_tokens;
-    const size_t rows = (size_t)B * Nq;
-    size_t off = 0;
-    auto take = [&](size_t nbytes) {
-        void *r = base ? (char *)base + off : nullptr;
-        off += align_up((int64_t)nbytes, 256);
-        return r;
-    };
-    Bf16Ws w;
-    w.KV = (float *)take(S * B * 2 * E * sizeof(float));
-    w.ctx = (float *)take(rows * E * sizeof(float));
-    w.x1 = (float *)take(rows * E * sizeof(float));
-    w.x1n = (float *)take(rows * E * sizeof(float));
-    w.hid = (__bf16 *)take(rows * 4 * E * 2);
-    w.x2 = (float *)take(rows * E * sizeof(float));
-    w.pooled = (float *)take((size_t)B * E * sizeof(float));
-    w.pre = (float *)take((size_t)B * E * 8 * sizeof(float));   // up to 8 split-K partials of the read-out product
-    w.bytes = off;
-    return w;
-}
-
 }  // namespace wv
 
 using namespace wv;
 
-static int check_head_bf16(const wv_head_params *p, int B)
-{
-    int rc = head_check_params(p, B);
-    if (rc) return rc;
-    WV_REQUIRE(p->embed_dim % 32 == 0, "band_attn_pool_bf16: embed_dim=%d must be a multiple of 32", p->embed_dim);
-    if (head_attn_core_lds(p) > (size_t)kMaxLdsBytes)
-        WV_FAIL(WV_ENOTSUP, "band_attn_pool_bf16: %d tokens x %d queries at embed_dim=%d do not fit the attention kernel's LDS",
-                p->num_tokens, p->num_queries, p->embed_dim);
-    return WV_OK;
-}
-
 extern "C" size_t wv_band_attn_bf16_prepared_bytes(const wv_head_params *p)
 {
-    if (!p || check_head_bf16(p, 1)) return 0;
+    if (!p) return 0;
+    const HeadPlan pl = head_plan(p, 1, HeadPrec::bf16);
+    if (pl.rc) {
+        set_error("%s", pl.why);
+        return 0;
+    }
     return carve_blob(p, nullptr).bytes;
 }
 
 extern "C" int wv_band_attn_bf16_prepare(const wv_head_params *p, void *prepared_out, void *stream)
 {
-    int rc = check_head_bf16(p, 1);
-    if (rc) return rc;
+    const HeadPlan pl = head_plan(p, 1, HeadPrec::bf16);
+    if (pl.rc) WV_FAIL(pl.rc, "%s", pl.why);
     WV_REQUIRE(prepared_out, "band_attn_bf16_prepare: null buffer");
     hipStream_t st = (hipStream_t)stream;
     const size_t E = p->embed_dim, Nq = p->num_queries;
     const Bf16Blob b = carve_blob(p, prepared_out);
-    head_launch_qproj(p, b.Qp, st);
+    launch_qproj(p, b.Qp, st);
     const struct { const float *src; __bf16 *dst; size_t n; } mats[] = {
         {p->in_proj_w + E * E, b.wkv, 2 * E * E}, {p->attn_out_w, b.wo, E * E},           {p->mlp0_w, b.w0, 4 * E * E},
         {p->mlp2_w, b.w2, 4 * E * E},             {p->out_w, b.wout, E * (p->pool_mean ? E : Nq * E)},
@@ -385,55 +289,28 @@ extern "C" int wv_band_attn_bf16_prepare(const wv_head_params *p, void *prepared
 
 extern "C" size_t wv_band_attn_pool_bf16_workspace_bytes(const wv_head_params *p, int B)
 {
-    if (!p || B <= 0) return 0;
-    return carve_ws(p, B, nullptr).bytes;
-}
-
-template <typename TF>
-static void run_head_bf16(const wv_head_params *p, const Bf16Blob &w, const TF *feats, int B, float *out, const Bf16Ws &ws,
-                          hipStream_t st)
-{
-    const int E = p->embed_dim, Nq = p->num_queries, S = p->num_tokens, rows = B * Nq;
-    // K | V projection of all S*B tokens
-    launch_gemm_bf16<EPI_NONE>(feats, w.wkv, p->in_proj_b + E, (const float *)nullptr, 1, ws.KV, S * B, 2 * E, E, st);
-    head_launch_attn_core(p, w.Qp, ws.KV, ws.ctx, B, st);
-    // x1 = q_eff + ctx @ Wo^T + bo ; x1n = LN1(x1)
-    launch_gemm_bf16<EPI_ADD_BCAST>(ws.ctx, w.wo, p->attn_out_b, p->q_eff, Nq, ws.x1, rows, E, E, st);
-    launch_layernorm(ws.x1, p->norm1_w, p->norm1_b, ws.x1n, (int64_t)rows, E, p->ln_eps, 1, st);
-    // x2 = x1n + GELU(x1n @ W0^T + b0) @ W2^T + b2; the hidden layer is an operand only: kept as bf16
-    launch_gemm_bf16<EPI_GELU>(ws.x1n, w.w0, p->mlp0_b, (const float *)nullptr, 1, ws.hid, rows, 4 * E, E, st);
-    launch_gemm_bf16<EPI_ADD_ROW>(ws.hid, w.w2, p->mlp2_b, ws.x1n, 1, ws.x2, rows, E, 4 * E, st);
-    // read-out: concat (a [B][Nq*E] view of x2) or mean over the queries, then Linear + LN2
-    const float *ro_in = ws.x2;
-    int ro_k = Nq * E;
-    if (p->pool_mean) {
-        head_launch_mean_rows(ws.x2, ws.pooled, (int64_t)B, Nq, E, st);
-        ro_in = ws.pooled;
-        ro_k = E;
-    }
-    const int ks = readout_ksplit_bf16(B, E, ro_k);
-    launch_gemm_bf16<EPI_NONE>(ro_in, w.wout, p->out_b, (const float *)nullptr, 1, ws.pre, B, E, ro_k, st, ks);
-    launch_layernorm(ws.pre, p->norm2_w, p->norm2_b, out, (int64_t)B, E, p->ln_eps, ks, st);
+    return head_plan(p, B, HeadPrec::bf16).ws.bytes;
 }
 
 extern "C" int wv_band_attn_pool_bf16(const wv_head_params *p, const void *prepared_bf16, const void *feats, int feat_dtype,
                                       int B, float *out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = check_head_bf16(p, B);
-    if (rc) return rc;
+    const HeadPlan pl = head_plan(p, B, HeadPrec::bf16);
+    if (pl.rc) WV_FAIL(pl.rc, "%s", pl.why);
     WV_REQUIRE(prepared_bf16, "band_attn_pool_bf16: null prepared blob (wv_band_attn_bf16_prepare makes it)");
     WV_REQUIRE(feat_dtype == WV_DT_F32 || feat_dtype == WV_DT_BF16,
                "band_attn_pool_bf16: feat_dtype=%d (WV_DT_F32 or WV_DT_BF16)", feat_dtype);
     WV_REQUIRE(feats && out, "band_attn_pool_bf16: null buffer");
     WV_REQUIRE((int64_t)B * std::max(p->num_queries, p->num_tokens) < (1ll << 31), "band_attn_pool_bf16: B=%d too large", B);
     if (B == 0) return WV_OK;
-    const size_t need = carve_ws(p, B, nullptr).bytes;
-    if (!workspace || workspace_bytes < need)
-        WV_FAIL(WV_ENOMEM, "band_attn_pool_bf16: workspace %zu < %zu bytes", workspace_bytes, need);
-    const Bf16Blob w = carve_blob(p, const_cast<void *>(prepared_bf16));
-    const Bf16Ws ws = carve_ws(p, B, workspace);
-    if (feat_dtype == WV_DT_BF16) run_head_bf16(p, w, reinterpret_cast<const __bf16 *>(feats), B, out, ws, (hipStream_t)stream);
-    else run_head_bf16(p, w, reinterpret_cast<const float *>(feats), B, out, ws, (hipStream_t)stream);
+    if (!workspace || workspace_bytes < pl.ws.bytes)
+        WV_FAIL(WV_ENOMEM, "band_attn_pool_bf16: workspace %zu < %zu bytes", workspace_bytes, pl.ws.bytes);
+    const Bf16Blob b = carve_blob(p, const_cast<void *>(prepared_bf16));
+    const HeadWeights<__bf16> w{b.wkv, b.wo, b.w0, b.w2, b.wout};
+    hipStream_t st = (hipStream_t)stream;
+    if (feat_dtype == WV_DT_BF16)
+        head_run_stages<PathBf16>(p, pl, w, b.Qp, reinterpret_cast<const __bf16 *>(feats), B, out, workspace, st);
+    else head_run_stages<PathBf16>(p, pl, w, b.Qp, reinterpret_cast<const float *>(feats), B, out, workspace, st);
     WV_CHECK_LAUNCH("band_attn_pool_bf16");
     return WV_OK;
 }

@@ -24,12 +24,9 @@
 //     (x2 accumulators stay in registers across the slices), so the 32 x 1536 hidden tile never exists.
 // MFMA work per wave: 5,760 + 48 v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate).  Measured structure ceiling
 // (tools/stream_mfma_test.hip): 124-126 TFLOP/s = 0.92 of a bare MFMA loop at one wave per SIMD.
-#include "common.hpp"
+#include "head.hpp"
 
 namespace wv {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int HF_E = 384;            // embed dim the fused kernel is built for
 constexpr int HF_LDA = HF_E + 4;     // LDS row pitch (floats)
@@ -69,6 +66,7 @@ static HeadFrontPlan head_front_plan(const wv_head_params *p)
     return g;
 }
 
+bool head_front_has_kernel(const wv_head_params *p) { return head_front_plan(p).ok; }
 size_t head_front_prepared_bytes(const wv_head_params *p) { return head_front_plan(p).bytes; }
 
 // ------------------------------------------------------------------------------------------------ prepare
@@ -478,12 +476,10 @@ __global__ __launch_bounds__(256, 1) void k_head_front(const float *__restrict__
 // ------------------------------------------------------------------------------------------------ host side
 int head_front_prepare(const wv_head_params *p, void *prepared, hipStream_t st)
 {
-    const HeadFrontPlan g = head_front_plan(p);
-    if (!g.ok) WV_FAIL(WV_ENOTSUP, "band_attn_prepare: no fused kernel for E=%d S=%d Nq=%d heads=%d", p->embed_dim,
-                       p->num_tokens, p->num_queries, p->num_heads);
+    const HeadFrontPlan g = head_front_plan(p);   // has a kernel: the caller asked head_front_has_kernel()
     float *Qp = reinterpret_cast<float *>(prepared);
-    int rc = wv_band_attn_qproj(p, Qp, st);
-    if (rc) return rc;
+    launch_qproj(p, Qp, st);
+    WV_CHECK_LAUNCH("k_qproj");
     f32x4 *stream = reinterpret_cast<f32x4 *>(reinterpret_cast<char *>(prepared) + g.qp_bytes);
     const size_t total = 4 * g.wave_stride4;
     hipLaunchKernelGGL(k_head_pack, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, st, p->in_proj_w, Qp,
@@ -505,24 +501,17 @@ static void launch_front(const HeadFrontPlan &g, const wv_head_params *p, const 
                        p->num_heads, p->ln_eps);
 }
 
-// 1 = launched (x2 [B*Nq][E] will hold the MLP output), 0 = separate launches are the better (or only) choice.
-// A workgroup runs its 32 rows through all 5,808 MFMAs of a wave whatever the batch: ~215 us even for one sample.  The
-// separate launches spread a small batch over the whole chip instead; measured crossover on MI355X (Nq = 4: B = 1024
-// -> 241 vs 217 us, B = 1536 -> 252 vs 317 us): from about 9/16 of the 256 CUs on, the one-launch front wins.
-// mode: 0 = never, 1 = whenever the configuration has a kernel, -1 = by that rule.
-int head_front_launch(const wv_head_params *p, const float *feats, int B, float *x2, int mode, hipStream_t st)
+// x2 [B*Nq][E] will hold the MLP output.  For a configuration with a kernel and a prepared stream (head_plan decides
+// when the one launch is the better choice).
+void head_front_launch(const wv_head_params *p, const float *feats, int B, float *x2, hipStream_t st)
 {
     const HeadFrontPlan g = head_front_plan(p);
-    if (!g.ok || !p->prepared || mode == 0) return 0;
-    if (mode < 0 && ceil_div(B, 32 / g.nq) < 144) return 0;
     if (g.nq == 4 && g.nsc == 1) launch_front<4, 1>(g, p, feats, B, x2, st);
     else if (g.nq == 4 && g.nsc == 2) launch_front<4, 2>(g, p, feats, B, x2, st);
     else if (g.nq == 4 && g.nsc == 4) launch_front<4, 4>(g, p, feats, B, x2, st);
     else if (g.nq == 8 && g.nsc == 1) launch_front<8, 1>(g, p, feats, B, x2, st);
     else if (g.nq == 8 && g.nsc == 2) launch_front<8, 2>(g, p, feats, B, x2, st);
     else if (g.nq == 8 && g.nsc == 4) launch_front<8, 4>(g, p, feats, B, x2, st);
-    else return 0;
-    return 1;
 }
 
 }  // namespace wv

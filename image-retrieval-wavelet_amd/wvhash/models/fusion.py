@@ -46,6 +46,23 @@ def resolve_matrix_dtype(value, device_type="cuda"):
     raise ValueError(f"matrix_dtype must be None, torch.bfloat16 / 'bf16' or 'auto', got {value!r}")
 
 
+def _head_params(S, E, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mean):
+    """_lib.HeadParams of the module's parameters (no projected queries, no prepared blob), and the fp32 contiguous
+    tensors its pointers refer to: the caller keeps them alive for the call."""
+    keep = [t.detach().float().contiguous() for t in
+            (q_eff, attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, attn.out_proj.bias, norm1.weight, norm1.bias,
+             mlp0.weight, mlp0.bias, mlp2.weight, mlp2.bias, out_proj.weight, out_proj.bias, norm2.weight, norm2.bias)]
+    p = _lib.HeadParams()
+    p.embed_dim, p.num_heads, p.num_queries, p.num_tokens = E, attn.num_heads, q_eff.shape[0], S
+    p.pool_mean = 1 if pool_mean else 0
+    (p.q_eff, p.in_proj_w, p.in_proj_b, p.attn_out_w, p.attn_out_b, p.norm1_w, p.norm1_b, p.mlp0_w, p.mlp0_b,
+     p.mlp2_w, p.mlp2_b, p.out_w, p.out_b, p.norm2_w, p.norm2_b) = [t.data_ptr() for t in keep]
+    p.ln_eps = float(norm1.eps)
+    p.q_proj = None
+    p.prepared = None
+    return p, keep
+
+
 def band_attn_pool(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mean=False,
                    workspace=None, qproj_cache=None, qproj_key=None, matrix_dtype=None, bf16_cache=None):
     """HIP forward of the attention-pooling core.  features_list: S x [B, E] CUDA fp32.
@@ -63,24 +80,13 @@ def band_attn_pool(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, out_pro
     S, B, E = feats.shape
     q_src = q_eff
     q_eff = q_eff.detach().float().reshape(-1, E).contiguous()
-    tensors = [q_eff, attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, attn.out_proj.bias,
-               norm1.weight, norm1.bias, mlp0.weight, mlp0.bias, mlp2.weight, mlp2.bias,
-               out_proj.weight, out_proj.bias, norm2.weight, norm2.bias]
-    keep = [t.detach().float().contiguous() for t in tensors]
+    p, keep = _head_params(S, E, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mean)
     for t in keep:
         if not t.is_cuda:
             raise ValueError("band_attn_pool: module parameters must live on the GPU")
-    p = _lib.HeadParams()
-    p.embed_dim, p.num_heads, p.num_queries, p.num_tokens = E, attn.num_heads, q_eff.shape[0], S
-    p.pool_mean = 1 if pool_mean else 0
-    (p.q_eff, p.in_proj_w, p.in_proj_b, p.attn_out_w, p.attn_out_b, p.norm1_w, p.norm1_b, p.mlp0_w, p.mlp0_b,
-     p.mlp2_w, p.mlp2_b, p.out_w, p.out_b, p.norm2_w, p.norm2_b) = [t.data_ptr() for t in keep]
-    p.ln_eps = float(norm1.eps)
-    p.q_proj = None
     out = torch.empty((B, E), dtype=torch.float32, device=feats.device)
     if B == 0:
         return out
-    p.prepared = None
     if use_bf16:
         return _band_attn_pool_bf16(lib, p, feats, out, workspace, bf16_cache, qproj_key, q_src, attn, mlp0, mlp2, out_proj)
     if qproj_cache is not None:
@@ -156,19 +162,9 @@ def band_attn_pool_host(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, ou
     feats = torch.stack([f.detach().to(fdt) for f in features_list], dim=0).contiguous()        # [S, B, E]
     S, B, E = feats.shape
     q_eff = q_eff.detach().float().reshape(-1, E).contiguous()
-    keep = [t.detach().float().contiguous() for t in
-            (q_eff, attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, attn.out_proj.bias, norm1.weight, norm1.bias,
-             mlp0.weight, mlp0.bias, mlp2.weight, mlp2.bias, out_proj.weight, out_proj.bias, norm2.weight, norm2.bias)]
+    p, keep = _head_params(S, E, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mean)
     if any(t.is_cuda for t in keep) or feats.is_cuda:
         raise ValueError("band_attn_pool_host takes host tensors (features and parameters)")
-    p = _lib.HeadParams()
-    p.embed_dim, p.num_heads, p.num_queries, p.num_tokens = E, attn.num_heads, q_eff.shape[0], S
-    p.pool_mean = 1 if pool_mean else 0
-    (p.q_eff, p.in_proj_w, p.in_proj_b, p.attn_out_w, p.attn_out_b, p.norm1_w, p.norm1_b, p.mlp0_w, p.mlp0_b,
-     p.mlp2_w, p.mlp2_b, p.out_w, p.out_b, p.norm2_w, p.norm2_b) = [t.data_ptr() for t in keep]
-    p.ln_eps = float(norm1.eps)
-    p.q_proj = None
-    p.prepared = None
     out = torch.empty((B, E), dtype=torch.float32)
     if use_bf16:
         dt = _lib.WV_DT_BF16 if fdt == torch.bfloat16 else _lib.WV_DT_F32

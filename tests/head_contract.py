@@ -32,10 +32,10 @@ RMS_BOUND, MAX_BOUND = 0.25, 1.0
 FP32_ORACLE_WORST = (0.115, 0.35)
 
 # (E, heads, Nq, read-out).  Products per call: K|V [4B x 2E, K = E], out-projection [B Nq x E, K = E], mlp.0 [B Nq x 4E,
-# K = E], mlp.2 [B Nq x E, K = 4E], read-out [B x E, K = Nq E or E].  launch_gemm_bf16: 128 x 128 tiles (K step 32) when
-# ceil(M/128) ceil(N/128) >= 256, else 64 x 64 tiles with the 64-wide K step when K (per slice) % 64 == 0, else the 32-wide
-# one; nk = K steps.  readout_ksplit_bf16: the largest ks in 8, 4, 2 with K % (64 ks) == 0, K / ks >= 128 and
-# ceil(B/64) ceil(E/64) ks <= 1024.
+# K = E], mlp.2 [B Nq x E, K = 4E], read-out [B x E, K = Nq E or E].  The plan (head_plan, csrc/head.hpp) -- gemm_bf16: 128 x 128
+# tiles (K step 32) when ceil(M/128) ceil(N/128) >= 256, else 64 x 64 tiles with the 64-wide K step when K (per slice) % 64
+# == 0, else the 32-wide one; nk = K steps.  readout_ksplit_bf16: the largest ks in 8, 4, 2 with K % (64 ks) == 0,
+# K / ks >= 128 and ceil(B/64) ceil(E/64) ks <= 1024.
 CONFIGS = {
     "e32_h4_q3_concat": (32, 4, 3, "concat"),     # K = 32: 32-wide step, nk = 1; N = 32 < 64: column guard, clamped W rows;
                                                   # mlp.2 K = 128: 64-wide, nk = 2; read-out K = 96: 32-wide, nk = 3, no split

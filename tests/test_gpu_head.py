@@ -105,6 +105,41 @@ def test_shape_sweep_against_the_fp64_oracle(config, B, diag):
         assert err < ATOL, (config, B, front)
 
 
+GEMM_PINS = ("nt64", "nt128", "lds64", "lds128x64", "lds128", "panel32", "panel64")
+
+
+@pytest.mark.parametrize("B", [17, 65, 129])
+@pytest.mark.parametrize("config", ["e384_h8_q4_concat", "e96_h8_q5_concat"])
+def test_every_fp32_gemm_variant_pinned(config, B, diag):
+    """The separate launches (WV_HEAD_FRONT=0) with each fp32 GEMM kernel pinned by name (WV_GEMM, csrc/head.hpp) and once by
+    dispatch.  A pin is honoured by every product that meets the kernel's requirement and left to the dispatch by the others:
+    nt64 / nt128 take all five products of every point; lds64 / lds128x64 / lds128 need K % 32 == 0 (E = 96 and 384 both) and
+    M >= 64: K|V (M = 4B = 68, 260, 516) and the three B Nq-row products (M = 68 ... 645) at every point, the read-out (M = B)
+    from B = 65 on; panel32 / panel64 need K % 64 == 0, N % 96 == 0 and M >= 128: nothing at E = 96 (K = 96; 480 for the
+    read-out), at E = 384 K|V and the three B Nq-row products (M = 260, 516) from B = 65 on and the read-out at B = 129.  Row
+    counts fall on both sides of the 64 and 128 tile edges; E = 96 has a partial column tile under every tile width.
+    Every output within ATOL of the fp64 oracle; the pinned outputs of a point bit-equal to one another: the read-out is not
+    split under any pin and all three kernels walk k in the same order (k_gemm_lds: "same k <-> (step, lane half) bijection")."""
+    ys = hc.yardstick(config, B)
+    head = hc.module(config).cuda()
+    dev = [f.cuda() for f in ys.feats]
+    diag.setenv("WV_HEAD_FRONT", "0")
+    outs = {}
+    with torch.no_grad():
+        for pin in GEMM_PINS + (None,):
+            if pin:
+                diag.setenv("WV_GEMM", pin)
+            else:
+                diag.delenv("WV_GEMM")
+            outs[pin] = head(dev).cpu()
+    for pin, y in outs.items():
+        err = (y.double() - ys.plain64).abs().max().item()
+        print(f"{config} B={B} WV_GEMM={pin}: max |y - fp64 oracle| = {err:.2e}")
+        assert err < ATOL, (config, B, pin)
+    for pin in GEMM_PINS[1:]:
+        assert torch.equal(outs[pin], outs[GEMM_PINS[0]]), (config, B, pin)
+
+
 @pytest.mark.parametrize("config,B", [("e96_h8_q5_concat", 65), ("e384_h8_q4_concat", 65), ("e384_h8_q4_concat", 120)])
 def test_a_row_does_not_depend_on_its_position(config, B, diag):
     """Same B, same dispatch: permuting the samples permutes the output rows bit for bit, on the separate launches and on

@@ -7,7 +7,7 @@ is asserted (run with -s to see them).
 
 That yardstick is mostly the bf16 effect itself and catches only a gross error.  The sharp one is the numerical contract
 (tests/head_contract.py: within 0.25 eff_rms / 1.0 eff_max of the fp64 evaluation of the bf16 oracle), held over a shape
-sweep that reaches every dispatch decision of launch_gemm_bf16 / readout_ksplit_bf16, plus properties that hold bit for bit:
+sweep that reaches every dispatch decision of gemm_bf16 / readout_ksplit_bf16 (head_plan, csrc/head.hpp), plus properties that hold bit for bit:
 a row does not depend on where it sits, the rounding is torch's round to nearest even, the caller's buffers are written only
 where the kernels own them, and the three tile variants give the same bits."""
 import ctypes

@@ -161,6 +161,21 @@ def test_device_entry_point_refuses_what_it_does_not_cover():
     assert rc == _lib.WV_ENOTSUP and b"LDS" in lib.wv_last_error()
 
 
+def test_fp32_entry_point_refuses_an_attention_core_that_does_not_fit_the_lds():
+    """The plan checks the attention core's LDS for either precision, before any device call: 64 tokens at E = 384, Nq = 4,
+    8 heads need (64 x 772 + 4 x 384 + 4 x 8 x 64) x 4 = 211,968 bytes against the CU's 163,840; 4 tokens fit, and the call
+    goes on to its next check (the workspace)."""
+    lib = _lib.load()
+    p = _params()
+    one = ctypes.c_void_p(16)
+    p.num_tokens = 64
+    rc = lib.wv_band_attn_pool(ctypes.byref(p), one, 1, one, one, ctypes.c_size_t(1 << 40), None)
+    assert rc == _lib.WV_ENOTSUP and b"LDS" in lib.wv_last_error() and b"band_attn_pool:" in lib.wv_last_error()
+    p.num_tokens = 4
+    assert lib.wv_band_attn_pool(ctypes.byref(p), one, 1, one, one, ctypes.c_size_t(64), None) == -12
+    assert b"workspace" in lib.wv_last_error()
+
+
 def test_module_switch_on_host_tensors():
     gold = np.load(GOLD)
     head, feats = build("adv_e384_nq4", gold)

@@ -66,7 +66,8 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    heads = {nq: make_head(nq) for nq in (4, 8)}
+    shapes = [tuple(int(v) for v in sh.split("x")) for sh in args.shapes.split(",")]
+    heads = {nq: make_head(nq) for nq in sorted({4, 8} | {nq for _, nq in shapes})}
     with torch.no_grad():
         warm = [f.cuda() for f in synth.band_features(2048, E, seed=1)]
         for _ in range(args.clock_calls):
@@ -75,7 +76,7 @@ def main():
         emit(f"# {torch.cuda.get_device_name(0)}; E={E} heads={HEADS} tokens={S}; {args.rounds} alternating rounds of {args.calls} calls, "
              f"us per call: median [min, max]")
         emit(f"{'B':>5} {'Nq':>2} {'feats':>5} | {'fp32 head':>24} | {'bf16 head':>24} | {'fp32/bf16':>9} | {'bf16 TFLOP/s':>12} {'of peak':>7}")
-        for B, nq in (tuple(int(v) for v in sh.split("x")) for sh in args.shapes.split(",")):
+        for B, nq in shapes:
             if True:
                 base = synth.band_features(B, E, seed=B)
                 for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
