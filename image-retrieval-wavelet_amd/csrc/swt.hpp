@@ -47,6 +47,46 @@ struct Cascade {
     }
 };
 
+// The same cascade for a line cut into runs of R outputs, one run per lane, when every lane of the wave runs it together.
+// The stencil is one-sided -- level l output i reads inputs i .. i + (L-1)*2^(l-1) -- so a run OWNS outputs 0 .. R-1 of
+// every level below the last and takes the (L-1)*2^l values the next level reads past them from the run to its right
+// (ds_bpermute through `right`, a lane byte address): every level value is computed once per line instead of once per
+// run that reads it.  w[] holds R + L-1 inputs on entry; lower() leaves the R + (L-1)*2^(NLEV-1) inputs of the last
+// level.  Each output keeps the taps and their order of Cascade, so it keeps its bits.
+template <int L, int NLEV, int R>
+struct RunCascade {
+    static constexpr int NPIX = R + (L - 1);
+    static constexpr int NW = R + (L - 1) * (1 << (NLEV - 1));
+    static_assert((L - 1) * (1 << (NLEV - 1)) < R, "a level's halo must come from one neighbouring run");
+
+    template <int LEV>
+    static __device__ __forceinline__ void lower(float (&w)[NW], const float (&lo)[L], int right)
+    {
+        if constexpr (LEV < NLEV) {
+            constexpr int S = 1 << (LEV - 1);
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                float a = lo[0] * w[i + S * (L - 1)];
+#pragma unroll
+                for (int m = 1; m < L; ++m) a = fmaf(lo[m], w[i + S * (L - 1 - m)], a);
+                w[i] = a;
+            }
+#pragma unroll
+            for (int i = 0; i < 2 * S * (L - 1); ++i)
+                w[R + i] = __int_as_float(__builtin_amdgcn_ds_bpermute(right, __float_as_int(w[i])));
+            lower<LEV + 1>(w, lo, right);
+        }
+    }
+    static __device__ __forceinline__ float last(const float (&w)[NW], const float (&f)[L], int i)
+    {
+        constexpr int S = 1 << (NLEV - 1);
+        float a = f[0] * w[i + S * (L - 1)];
+#pragma unroll
+        for (int m = 1; m < L; ++m) a = fmaf(f[m], w[i + S * (L - 1 - m)], a);
+        return a;
+    }
+};
+
 // v mod n for any v
 __device__ __forceinline__ int wrap(int v, int n)
 {

@@ -223,13 +223,6 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
     const int nq = g.B > xcd ? (g.B - xcd + g.nxcd - 1) / g.nxcd * g.C : 0;   // planes this XCD owns
     const bool is_h = threadIdx.x >= NH;                  // wave-uniform role
     const int t = is_h ? threadIdx.x - NH : threadIdx.x;
-    // Two statements below change no result: the row pass takes its last-level taps from the copies hlo / hhi, and
-    // the column role evaluates (and drops) the slot index of the retired planar LDS layout.  Both keep the compiler's
-    // instruction order, and with it the machine code of the kernel as measured; dropping either
-    // re-schedules it.
-    float hlo[L], hhi[L];
-#pragma unroll
-    for (int m = 0; m < L; ++m) { hlo[m] = taps.lo[m]; hhi[m] = taps.hi[m]; }
     if (is_h) {
         // ------------------------------------------------------------------ producer: pass H
         // (row, run) of this producer thread.  Coalesced mode (planar uint8, W % 16 == 0) keeps the runs of one row
@@ -238,11 +231,12 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
         // (the strided form touches each cache line of its 40-pixel window ten times).
         int rr = t / g.nrun, j = t - rr * g.nrun;
         bool active = t < TH * g.nrun;
-        int lane_left = 0, lane_right = 0, rr_ld = 0;
+        int lane_left = 0, lane_right = 0, rr_ld = 0, wrow0 = 0;
         if (g.coal) {
             const int l = t & 63, rpw = 64 / g.nrun, lr = l / g.nrun;
             j = l - lr * g.nrun;
-            rr = (t >> 6) * rpw + lr;
+            wrow0 = (t >> 6) * rpw;                                              // first row of this wave
+            rr = wrow0 + lr;
             active = lr < rpw && rr < TH;
             rr_ld = min(rr, TH - 1);                                             // spare lanes load a valid row too
             lane_left = (lr * g.nrun + (j == 0 ? g.nrun - 1 : j - 1)) * 4;       // byte addresses for ds_bpermute
@@ -273,60 +267,108 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
                 own[0] = v4.x; own[1] = v4.y; own[2] = v4.z; own[3] = v4.w;
             };
             const bool coal = CAN_COAL && g.coal;   // uniform
-            if (coal) issue_row(0);
-            else if (active) fetch(0);
-            for (int k = 0; k < nchunks; ++k) {
-                WV_STAMP(st0);
-                if constexpr (CAN_COAL) {
-                    if (coal) {
-                        // window of run j = pixels [16j - HBa, 16j - HBa + 4 NG): left neighbour | own | right neighbour
-#pragma unroll
-                        for (int kk = 0; kk < NG; ++kk) {
-                            const int gpx = 4 * kk - HBa;                      // compile-time after unrolling
-                            if (gpx < 0)
-                                raw[kk].d[0] = (uint32_t)__builtin_amdgcn_ds_bpermute(lane_left, (int)own[(gpx + 16) / 4]);
-                            else if (gpx < 16)
-                                raw[kk].d[0] = own[gpx / 4];
-                            else
-                                raw[kk].d[0] = (uint32_t)__builtin_amdgcn_ds_bpermute(lane_right, (int)own[(gpx - 16) / 4]);
-                        }
-                        if (k + 1 < nchunks) issue_row(k + 1);                 // flies during this chunk's arithmetic
-                    }
-                }
-                if (active) {
-                    float v[NG * 4];
-#pragma unroll
-                    for (int q = 0; q < NG; ++q) {
-                        const float4 p4 = s_convert4<InT, LAYOUT>(raw[q], c);
-                        v[4 * q + 0] = p4.x; v[4 * q + 1] = p4.y; v[4 * q + 2] = p4.z; v[4 * q + 3] = p4.w;
-                    }
-                    WV_STAMP(st1);
-                    if (k + 1 < nchunks && !coal) fetch(k + 1);     // next chunk's pixels fly during the arithmetic
-                    WV_STAMP(st4);
-                    // in-place cascade on v[off ..): element i of the run lives at v[i + off]
-                    constexpr int off = HBa - HB;
-                    float w[CH::NIN];
-#pragma unroll
-                    for (int i = 0; i < CH::NIN; ++i) w[i] = v[i + off];
-                    CH::template lower<1>(w, taps.lo);
-                    WV_STAMP(st5);
-                    // LDS row layout is permuted and the planes interleaved so that consecutive lanes (= consecutive
-                    // runs j) write consecutive 16-byte slots: column x = j*R + 2*q2 + e holds (lo, hi) at floats
-                    // q2*(4*nrun) + 4*j + 2*e of its row
-                    float *prow = ring + (k & 1) * buf_sz + rr * (2 * P) + 4 * j;
-                    const int qstride = 4 * g.nrun;
-#pragma unroll
-                    for (int q2 = 0; q2 < R / 2; ++q2) {
-                        float4 v4;
-                        v4.x = CH::last(w, hlo, 2 * q2 + 0); v4.y = CH::last(w, hhi, 2 * q2 + 0);
-                        v4.z = CH::last(w, hlo, 2 * q2 + 1); v4.w = CH::last(w, hhi, 2 * q2 + 1);
-                        *reinterpret_cast<float4 *>(prow + q2 * qstride) = v4;
-                    }
-                }
+            // end of a chunk: buffer k & 1 is full; buffer (k+1) & 1 was drained before this barrier
+            auto hand_over = [&]() {
                 WV_STAMP(st2);
-                __syncthreads();   // buffer k & 1 is full; buffer (k+1) & 1 was drained before this barrier
+                __syncthreads();
                 WV_STAMP(st3);
                 if constexpr (STAMP) { acc_a += st1 - st0; acc_b += st2 - st5; acc_c += st3 - st2; acc_d += st4 - st1; acc_e += st5 - st4; }
+            };
+            // The two fetch modes have a chunk loop each: neither holds the other's addresses in registers, and the wait
+            // for the strided loads in front of the conversion does not also wait for the coalesced row just issued.
+            if (coal) {
+                if constexpr (CAN_COAL) {
+                    issue_row(0);
+                    for (int k = 0; k < nchunks; ++k) {
+                        WV_STAMP(st0);
+                        // Every pixel is converted once and every level value computed once per row: run j owns
+                        // outputs 0 .. R-1 of each level and its right neighbour hands over the rest (RunCascade).
+                        // All of it feeds ds_bpermute, so it runs in every lane of the wave -- spare lanes hold a
+                        // valid row -- and only the LDS write is per lane.  A wave whose rows all lie past the
+                        // TH rows of the chunk or past the H + HALO rows the column cascade consumes skips the chunk.
+                        using RC = RunCascade<L, NLEV, R>;
+                        constexpr int NGC = (HBa - HB + RC::NPIX + 3) / 4;     // 4-pixel groups level 1 reads
+                        static_assert(HBa <= 16 && 4 * NGC - HBa <= 32, "the pixel window must end in the neighbouring runs");
+                        const int wrow = __builtin_amdgcn_readfirstlane(wrow0);             // wave-uniform
+                        const bool live = wrow < TH && k * TH + wrow < H + HALO;
+                        if (live) {
+                            float w[RC::NW];
+                            // pixels [16j - HBa, 16j - HBa + 4 NGC): left neighbour | own | right neighbour
+                            float v[NGC * 4];
+#pragma unroll
+                            for (int kk = 0; kk < NGC; ++kk) {
+                                const int gpx = 4 * kk - HBa;                  // compile-time after unrolling
+                                uint32_t d;
+                                if (gpx < 0)
+                                    d = (uint32_t)__builtin_amdgcn_ds_bpermute(lane_left, (int)own[(gpx + 16) / 4]);
+                                else if (gpx < 16)
+                                    d = own[gpx / 4];
+                                else
+                                    d = (uint32_t)__builtin_amdgcn_ds_bpermute(lane_right, (int)own[(gpx - 16) / 4]);
+                                const float4 p4 = u8x4_to_unit(d);
+                                v[4 * kk + 0] = p4.x; v[4 * kk + 1] = p4.y; v[4 * kk + 2] = p4.z; v[4 * kk + 3] = p4.w;
+                            }
+#pragma unroll
+                            for (int i = 0; i < RC::NPIX; ++i) w[i] = v[i + HBa - HB];
+                            WV_STAMP(st1);
+                            if (k + 1 < nchunks) issue_row(k + 1);             // flies during this chunk's arithmetic
+                            WV_STAMP(st4);
+                            RC::template lower<1>(w, taps.lo, lane_right);
+                            WV_STAMP(st5);
+                            if (active && k * TH + rr < H + HALO) {
+                                float *prow = ring + (k & 1) * buf_sz + rr * (2 * P) + 4 * j;   // row layout: see the strided loop
+                                const int qstride = 4 * g.nrun;
+#pragma unroll
+                                for (int q2 = 0; q2 < R / 2; ++q2) {
+                                    float4 v4;
+                                    v4.x = RC::last(w, taps.lo, 2 * q2 + 0); v4.y = RC::last(w, taps.hi, 2 * q2 + 0);
+                                    v4.z = RC::last(w, taps.lo, 2 * q2 + 1); v4.w = RC::last(w, taps.hi, 2 * q2 + 1);
+                                    *reinterpret_cast<float4 *>(prow + q2 * qstride) = v4;
+                                }
+                            }
+                        } else {
+                            if (k + 1 < nchunks) issue_row(k + 1);
+                            if constexpr (STAMP) st1 = st4 = st5 = st0;
+                        }
+                        hand_over();
+                    }
+                }
+            } else {
+                if (active) fetch(0);
+                for (int k = 0; k < nchunks; ++k) {
+                    WV_STAMP(st0);
+                    if (active) {
+                        float v[NG * 4];
+#pragma unroll
+                        for (int q = 0; q < NG; ++q) {
+                            const float4 p4 = s_convert4<InT, LAYOUT>(raw[q], c);
+                            v[4 * q + 0] = p4.x; v[4 * q + 1] = p4.y; v[4 * q + 2] = p4.z; v[4 * q + 3] = p4.w;
+                        }
+                        WV_STAMP(st1);
+                        if (k + 1 < nchunks) fetch(k + 1);              // next chunk's pixels fly during the arithmetic
+                        WV_STAMP(st4);
+                        // in-place cascade on v[off ..): element i of the run lives at v[i + off]
+                        constexpr int off = HBa - HB;
+                        float w[CH::NIN];
+#pragma unroll
+                        for (int i = 0; i < CH::NIN; ++i) w[i] = v[i + off];
+                        CH::template lower<1>(w, taps.lo);
+                        WV_STAMP(st5);
+                        // LDS row layout is permuted and the planes interleaved so that consecutive lanes (= consecutive
+                        // runs j) write consecutive 16-byte slots: column x = j*R + 2*q2 + e holds (lo, hi) at floats
+                        // q2*(4*nrun) + 4*j + 2*e of its row
+                        float *prow = ring + (k & 1) * buf_sz + rr * (2 * P) + 4 * j;
+                        const int qstride = 4 * g.nrun;
+#pragma unroll
+                        for (int q2 = 0; q2 < R / 2; ++q2) {
+                            float4 v4;
+                            v4.x = CH::last(w, taps.lo, 2 * q2 + 0); v4.y = CH::last(w, taps.hi, 2 * q2 + 0);
+                            v4.z = CH::last(w, taps.lo, 2 * q2 + 1); v4.w = CH::last(w, taps.hi, 2 * q2 + 1);
+                            *reinterpret_cast<float4 *>(prow + q2 * qstride) = v4;
+                        }
+                    }
+                    hand_over();
+                }
             }
             __syncthreads();       // pairs with the consumer's last barrier of the plane
         }
@@ -334,7 +376,6 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
         // ------------------------------------------------------------------ consumer: pass V
         const bool active = t < W;
         __builtin_amdgcn_s_setprio(kConsumerPrio);   // the critical role issues first
-        (void)(((t % R) / 4) * (4 * g.nrun) + (t / R) * 4 + (t & 3));   // see the note at the top
         // this column's (lo, hi) slot in the permuted LDS row (see pass H)
         const int tp = ((t % R) / 2) * (4 * g.nrun) + (t / R) * 4 + 2 * (t & 1);
         using VS = VStep<L, NLEV, TH>;
