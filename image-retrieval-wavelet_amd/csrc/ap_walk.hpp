@@ -77,4 +77,90 @@ __device__ __forceinline__ void ap_final(const ApState &st, double *wsum, int t,
     }
 }
 
+// ---- several cut-offs from one walk (wv_hamming_map_at_ks, wv_merge_relbits_map_ks, wv_map_at_ks).
+// List position p = round * TPQ + t does not depend on k, a thread adds its quotients in increasing position, and the list
+// for the largest cut-off has the list for every smaller one as a prefix (the order distance, then row is total): AP@c is
+// a snapshot of the walk to k_max, taken in the round that holds position c - 1, with the bits of a walk to c.
+constexpr int kMaxCutoffs = 16;              // = WV_MAX_CUTOFFS (wvhash.h)
+
+struct ApCuts {                              // travels by value in the kernel arguments: no device copy, no sync
+    int n;                                   // 1 .. kMaxCutoffs
+    int k[kMaxCutoffs];                      // strictly ascending, k[0] >= 1; the walk is k[n - 1] positions long
+};
+
+// dwords of LDS scratch of the multi-cut walk: the single-cut walk's + the waves' hit counts below a cut
+template <int TPQ>
+__host__ __device__ constexpr int ap_cuts_scratch_dwords() { return ap_scratch_dwords<TPQ>() + TPQ / 64; }
+
+// ap_accum for a chunk of the walk to cuts.k[cuts.n - 1], writing ap_out[i] / nrel_out[i] (or NULL) for every cut i whose
+// last position lies in the chunk.  `next`: the first cut not written yet (0 before the first chunk); after the last chunk
+// every cut is written, ap_final is not called.  In the round of a cut c a thread with p < c contributes
+// st.acc + its own quotient, every other thread st.acc alone; the hits of the round with p < c come from a masked ballot
+// (cnt holds whole rounds).  Each snapshot takes ap_final's way: wave butterfly, waves in index order.
+// wsum: NW doubles (8-byte aligned), wcut: NW dwords, both free LDS.  Control flow is uniform over the TPQ threads.
+template <int TPQ, typename SYNC>
+__device__ __forceinline__ void ap_accum_cuts(uint32_t relbits, const uint32_t *cnt, int Rc, int r_base, int t, ApState &st,
+                                              const ApCuts &cuts, int &next, double *wsum, uint32_t *wcut,
+                                              float *__restrict__ ap_out, int32_t *__restrict__ nrel_out, SYNC group_barrier)
+{
+    constexpr int NW = TPQ / 64, CH = 8;
+    const int lane = t & 63, wv = t >> 6;
+    // the next cut-off in a register: read from the kernel arguments when it changes, not in every round
+    int64_t cut = next < cuts.n ? cuts.k[next] : INT64_MAX;
+    for (int r0 = 0; r0 < Rc; r0 += CH) {
+        uint32_t c[CH][NW];
+#pragma unroll
+        for (int u = 0; u < CH; ++u)
+#pragma unroll
+            for (int w2 = 0; w2 < NW; ++w2) c[u][w2] = cnt[min(r0 + u, Rc - 1) * NW + w2];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) {
+            const int r = r0 + u;
+            if (r < Rc) {                                         // uniform
+                uint32_t before = st.running, tot = 0;
+#pragma unroll
+                for (int w2 = 0; w2 < NW; ++w2) {
+                    before += w2 < wv ? c[u][w2] : 0u;
+                    tot += c[u][w2];
+                }
+                const bool rel = (relbits >> r) & 1u;
+                const uint64_t m = __ballot(rel);
+                const int p = (r_base + r) * TPQ + t;
+                double own = 0.0;                                 // this thread's quotient of the round
+                if (rel) {
+                    const uint32_t j = before + (uint32_t)mbcnt(m) + 1;
+                    own = (double)((float)j / (float)(p + 1));
+                }
+                // cuts whose last position c - 1 lies in this round (uniform; several may share a round)
+                while (cut <= (int64_t)(r_base + r + 1) * TPQ) {
+                    const bool in = rel && p < cut;
+                    const uint64_t mc = __ballot(in);
+                    const double acc = wave_sum_f64(in ? st.acc + own : st.acc);
+                    if (lane == 0) {
+                        wsum[wv] = acc;
+                        wcut[wv] = (uint32_t)__popcll(mc);
+                    }
+                    group_barrier();
+                    if (t == 0) {
+                        double s = wsum[0];
+                        uint32_t running = st.running + wcut[0];
+#pragma unroll
+                        for (int w2 = 1; w2 < NW; ++w2) {
+                            s += wsum[w2];
+                            running += wcut[w2];
+                        }
+                        ap_out[next] = running ? (float)(s / (double)running) : 0.0f;
+                        if (nrel_out) nrel_out[next] = (int32_t)running;
+                    }
+                    group_barrier();                              // wsum / wcut are free for the next cut
+                    ++next;
+                    cut = next < cuts.n ? cuts.k[next] : INT64_MAX;
+                }
+                if (rel) st.acc += own;
+                st.running += tot;
+            }
+        }
+    }
+}
+
 }  // namespace wv

@@ -69,6 +69,23 @@ inline bool relevant(const uint64_t *ql, const uint64_t *dl, int lwords)
     return any != 0;
 }
 
+// the 256 threads' sums in the kernels' order: the lanes of a wave in wave_sum_f64's butterfly, the four waves in index order
+inline double sum_in_kernel_order(const double (&acc)[256])
+{
+    double wave[4];
+    for (int w = 0; w < 4; ++w) {                                           // wave_sum_f64: v += shfl_xor(v, d), d = 32 .. 1
+        double s[64];
+        for (int l = 0; l < 64; ++l) s[l] = acc[64 * w + l];
+        for (int dd = 32; dd > 0; dd >>= 1) {
+            double n2[64];
+            for (int l = 0; l < 64; ++l) n2[l] = s[l] + s[l ^ dd];
+            for (int l = 0; l < 64; ++l) s[l] = n2[l];
+        }
+        wave[w] = s[0];
+    }
+    return wave[0] + wave[1] + wave[2] + wave[3];
+}
+
 }  // namespace
 
 extern "C" int wv_pack_bits_cpu(const float *src, int64_t ld_src, uint64_t *packed, int64_t rows, int nbits, int mode,
@@ -170,20 +187,46 @@ extern "C" int wv_map_at_k_cpu(const int32_t *idx, int64_t ld, int Q, int k, con
                 acc[p & 255] += (double)((float)hits / (float)(p + 1));    // fp32 quotient like the reference
             }
         }
-        double wave[4];
-        for (int w = 0; w < 4; ++w) {                                       // wave_sum_f64: v += shfl_xor(v, d), d = 32 .. 1
-            double s[64];
-            for (int l = 0; l < 64; ++l) s[l] = acc[64 * w + l];
-            for (int dd = 32; dd > 0; dd >>= 1) {
-                double n2[64];
-                for (int l = 0; l < 64; ++l) n2[l] = s[l] + s[l ^ dd];
-                for (int l = 0; l < 64; ++l) s[l] = n2[l];
-            }
-            wave[w] = s[0];
-        }
-        const double total = wave[0] + wave[1] + wave[2] + wave[3];
+        const double total = sum_in_kernel_order(acc);
         ap[qi] = hits ? (float)(total / (double)hits) : 0.0f;
         if (nrel) nrel[qi] = (int32_t)hits;
+    }
+    return WV_OK;
+}
+
+// The same at several cut-offs from one walk (twin of wv_map_at_ks): a thread's quotients are added in increasing position,
+// so the state after position c - 1 is the state of a walk to c; each cut-off takes the reduction above.
+extern "C" int wv_map_at_ks_cpu(const int32_t *idx, int64_t ld, int Q, const int *ks, int nk, const uint64_t *qlab,
+                                const uint64_t *dblab, int lwords, float *ap, int32_t *nrel)
+{
+    HR_REQUIRE(idx && qlab && dblab && ap, "map_at_ks_cpu: null buffer");
+    HR_REQUIRE(Q >= 0 && ld >= 1 && lwords >= 1, "map_at_ks_cpu: bad shape Q=%d ld=%lld lwords=%d", Q, (long long)ld, lwords);
+    HR_REQUIRE(ks, "map_at_ks_cpu: null cut-off list");
+    HR_REQUIRE(nk >= 1 && nk <= WV_MAX_CUTOFFS, "map_at_ks_cpu: %d cut-offs (supported: 1..%d)", nk, WV_MAX_CUTOFFS);
+    HR_REQUIRE(ks[0] >= 1, "map_at_ks_cpu: cut-off %d must be >= 1", ks[0]);
+    for (int i = 1; i < nk; ++i)
+        HR_REQUIRE(ks[i] > ks[i - 1], "map_at_ks_cpu: cut-offs must be strictly ascending (ks[%d]=%d after %d)", i, ks[i], ks[i - 1]);
+    HR_REQUIRE(ks[nk - 1] <= ld, "map_at_ks_cpu: largest cut-off %d must be <= ld=%lld", ks[nk - 1], (long long)ld);
+    for (int qi = 0; qi < Q; ++qi) {
+        const int32_t *list = idx + (int64_t)qi * ld;
+        const uint64_t *ql = qlab + (int64_t)qi * lwords;
+        double acc[256];
+        for (int t = 0; t < 256; ++t) acc[t] = 0.0;
+        uint32_t hits = 0;
+        int next = 0;
+        for (int p = 0; p < ks[nk - 1]; ++p) {
+            const int32_t id = list[p];
+            if (id >= 0 && relevant(ql, dblab + (int64_t)id * lwords, lwords)) {
+                ++hits;
+                acc[p & 255] += (double)((float)hits / (float)(p + 1));
+            }
+            if (p + 1 == ks[next]) {
+                const double total = sum_in_kernel_order(acc);
+                ap[(int64_t)qi * nk + next] = hits ? (float)(total / (double)hits) : 0.0f;
+                if (nrel) nrel[(int64_t)qi * nk + next] = (int32_t)hits;
+                ++next;
+            }
+        }
     }
     return WV_OK;
 }

@@ -6,6 +6,8 @@
 
 namespace wv {
 
+struct ApCuts;                               // ap_walk.hpp
+
 constexpr int kTopkThreads = 256;            // threads per workgroup of every ranking kernel
 constexpr int kMaxBins = 130;                // nbits <= 128 (+1 bin for the padding value of ragged shard lists)
 constexpr int kWinBins = 32;                 // windowed kernel: distance bins per window
@@ -168,8 +170,9 @@ struct Rank2Ap {
 
 // Launches the windowed kernel of `plan` (window256 / window64) on its image `img`.  idx (int32 global indices) or rows16
 // (16-bit local row numbers) receives the list; k == 0: histogram only; apx: RankMode::ap / relbits, NULL otherwise.
+// cuts (RankMode::ap only): average precision at several cut-offs, k = the largest, apx->ap / nrel are [Q][cuts->n].
 int rank2_launch(const RankPlan &plan, const uint64_t *q, const void *img, int32_t *idx, uint16_t *rows16, uint8_t *dist,
                  uint32_t *cum, int Q, int64_t N, int nbits, int k, int64_t idx_offset, hipStream_t st,
-                 const Rank2Ap *apx = nullptr);
+                 const Rank2Ap *apx = nullptr, const ApCuts *cuts = nullptr);
 
 }  // namespace wv

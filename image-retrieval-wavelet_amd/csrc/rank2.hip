@@ -305,6 +305,44 @@ __device__ __forceinline__ void rank2_ap(const uint16_t *stage, const uint32_t *
     if (relbits_out) return;
     ap_final<TPQ>(st, wsum, t, ap_out, nrel_out, [] { group_sync<TPQ>(); });
 }
+// The same walk for several cut-offs (wv_hamming_map_at_ks): k = cuts.k[cuts.n - 1], ap_out / nrel_out are the query's rows
+// of cuts.n entries.  scratch: free LDS, ap_cuts_scratch_dwords<TPQ>() dwords.
+template <int TPQ>
+__device__ __forceinline__ void rank2_ap_cuts(const uint16_t *stage, const uint32_t *bitmap, uint32_t *scratch, int k, int t,
+                                              float *__restrict__ ap_out, int32_t *__restrict__ nrel_out, const ApCuts &cuts)
+{
+    constexpr int NW = TPQ / 64, CH = 8;
+    const int lane = t & 63, wv = t >> 6;
+    const int R = (k + TPQ - 1) / TPQ;
+    uint32_t *cnt = scratch;
+    double *wsum = reinterpret_cast<double *>(scratch + kApRounds * NW + (kApRounds * NW & 1));
+    uint32_t *wcut = reinterpret_cast<uint32_t *>(wsum + NW);
+    ApState st;
+    int next = 0;
+    for (int c0 = 0; c0 < R; c0 += kApRounds) {
+        const int Rc = min(kApRounds, R - c0);
+        uint32_t relbits = 0;
+        for (int r0 = c0; r0 < c0 + Rc; r0 += CH) {              // as rank2_ap: a batch's LDS reads before their first use
+            uint32_t it[CH], wd[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) it[u] = stage[min((r0 + u) * TPQ + t, k - 1)];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) wd[u] = bitmap[it[u] >> 5];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const int r = r0 + u;
+                const bool rel = r < c0 + Rc && r * TPQ + t < k && ((wd[u] >> (it[u] & 31)) & 1u);
+                relbits |= (rel ? 1u : 0u) << ((r - c0) & 31);
+                const uint64_t m = __ballot(rel);
+                if (lane == 0 && r < c0 + Rc) cnt[(r - c0) * NW + wv] = (uint32_t)__popcll(m);
+            }
+        }
+        group_sync<TPQ>();                                       // the chunk's hit counts are published
+        ap_accum_cuts<TPQ>(relbits, cnt, Rc, c0, t, st, cuts, next, wsum, wcut, ap_out, nrel_out, [] { group_sync<TPQ>(); });
+        group_sync<TPQ>();                                       // ... and read: the next chunk may overwrite them
+    }
+}
+
 template <int TPQ>
 __device__ __forceinline__ Rank2Lds rank2_lds(uint8_t *lds_raw, int k)
 {
@@ -412,12 +450,13 @@ __device__ __forceinline__ void rank2_dist_row(const Rank2Lds &L, int nbins, int
 // Expects the count table zeroed (rank2_zero_table + a group barrier before the first LDS add: the caller's -- the
 // zeroing overlaps the distance pass).  Ends with a group barrier.
 // NC = distance-cache words (4 items each): items per thread C <= 4 * NC
-template <int TPQ, int NC, bool AP = false>
+// AP: 0 = the list, 1 = average precision / relevance string of the list, 2 = average precision at the cut-offs `cuts`
+template <int TPQ, int NC, int AP = 0>
 __device__ __forceinline__ void rank2_rank(const uint32_t (&dc)[NC], uint32_t dmin, int64_t N, int C, int nbins, int k,
                                            uint32_t *__restrict__ cum_out, uint8_t *__restrict__ dist_out, uint8_t *lds_raw, int t,
                                            const uint32_t *__restrict__ cls = nullptr, uint64_t qlabel = 0, uint64_t qlabel_hi = 0,
                                            float *__restrict__ ap_out = nullptr, int32_t *__restrict__ nrel_out = nullptr,
-                                           uint64_t *__restrict__ relbits_out = nullptr)
+                                           uint64_t *__restrict__ relbits_out = nullptr, const ApCuts *cuts = nullptr)
 {
     constexpr int ROWB = TPQ * 2;                                // bytes per table row
     const Rank2Lds L = rank2_lds<TPQ>(lds_raw, k);
@@ -594,7 +633,8 @@ __device__ __forceinline__ void rank2_rank(const uint32_t (&dc)[NC], uint32_t dm
     if (dist_out) rank2_dist_row<TPQ>(L, nbins, k, dist_out, t);
     R2_STAMP(4);
     if constexpr (AP) {
-        rank2_ap<TPQ>(L.stage, bitmap, L.table, k, t, ap_out, nrel_out, relbits_out);   // the count table is free by now
+        if constexpr (AP == 2) rank2_ap_cuts<TPQ>(L.stage, bitmap, L.table, k, t, ap_out, nrel_out, *cuts);
+        else rank2_ap<TPQ>(L.stage, bitmap, L.table, k, t, ap_out, nrel_out, relbits_out);   // the count table is free by now
         R2_STAMP(7);
         group_sync<TPQ>();                                        // the table (AP scratch) and the bitmap are free again
     }
@@ -702,7 +742,7 @@ __global__ __launch_bounds__(256, rank2_min_waves(NC)) void k_rank_window(const 
                                 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lw);
             const uint64_t ql2 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lw2 >> 32)) << 32) |
                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lw2);
-            rank2_rank<TPQ, NC, true>(dc, dmin, N, C, nbins, k,
+            rank2_rank<TPQ, NC, 1>(dc, dmin, N, C, nbins, k,
                                       cum ? cum + (int64_t)qi * (apx.cum_ld ? apx.cum_ld : nbins + 1) : nullptr, nullptr, lds, t,
                                       apx.cls, ql, ql2, apx.ap ? apx.ap + qi : nullptr, apx.nrel ? apx.nrel + qi : nullptr,
                                       apx.relbits ? apx.relbits + (int64_t)qi * (apx.relbits_ld ? apx.relbits_ld : (k + 63) / 64)
@@ -714,6 +754,42 @@ __global__ __launch_bounds__(256, rank2_min_waves(NC)) void k_rank_window(const 
                                  rows16 ? rows16 + (int64_t)qi * k : nullptr, t);
         }
     }
+}
+
+// The multi-cut instantiation behind wv_hamming_map_at_ks: k_rank_window's AP pass with k = the largest cut-off, AP at every
+// cut-off (apx.ap / apx.nrel: [Q][cuts.n]).  Its own kernels: the single-k ones keep their arguments and registers.
+// (Up to 8 cache words the walk's snapshots need a few registers more than the 72 that seven waves per SIMD leave: six there.)
+constexpr int rank2_cuts_min_waves(int nc) { return nc <= 8 ? 6 : rank2_min_waves(nc); }
+
+template <int WORDS, int TPQ, int NC>
+__global__ __launch_bounds__(256, rank2_cuts_min_waves(NC)) void k_rank_window_cuts(const uint64_t *__restrict__ q, const uint4 *__restrict__ img,
+                                                                               int Q, int64_t N, int C, int nbins, int lds_per_group,
+                                                                               Rank2Ap apx, ApCuts cuts)
+{
+    extern __shared__ uint4 lds4[];
+    constexpr int GPW = 256 / TPQ;
+    const int g = threadIdx.x / TPQ, t = threadIdx.x % TPQ;
+    const int qi = blockIdx.x * GPW + g;
+    if (qi >= Q) return;                                         // whole waves only (TPQ == 64): no barrier is skipped
+    uint8_t *lds = reinterpret_cast<uint8_t *>(lds4) + (size_t)g * lds_per_group;
+    QCode<WORDS> qc;
+#pragma unroll
+    for (int w = 0; w < WORDS; ++w) {
+        const uint64_t v = q[(int64_t)qi * WORDS + w];
+        qc.w[w] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    }
+    rank2_zero_table<TPQ>(lds, t);
+    uint32_t dc[NC], dmin;
+    rank2_distances<WORDS, TPQ, NC>(img, qc, N, C, t, dc, dmin);
+    group_sync<TPQ>();                                           // the count table is zero
+    const uint64_t lw = apx.qlab[(int64_t)qi * apx.lwords], lw2 = apx.lwords > 1 ? apx.qlab[(int64_t)qi * apx.lwords + 1] : 0;
+    const uint64_t ql = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lw >> 32)) << 32) |
+                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lw);
+    const uint64_t ql2 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lw2 >> 32)) << 32) |
+                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lw2);
+    rank2_rank<TPQ, NC, 2>(dc, dmin, N, C, nbins, cuts.k[cuts.n - 1], nullptr, nullptr, lds, t, apx.cls, ql, ql2,
+                           apx.ap + (int64_t)qi * cuts.n, apx.nrel ? apx.nrel + (int64_t)qi * cuts.n : nullptr, nullptr, &cuts);
 }
 
 // ------------------------------------------------------------------------------------------ host side
@@ -746,12 +822,24 @@ struct WindowArgs {
     hipStream_t st;
     bool fused;
     Rank2Ap apx;
+    const ApCuts *cuts;      // fused, several cut-offs: k = the largest
 };
 
 template <int WORDS, int TPQ, int NC>
 int launch_window(const RankPlan &plan, const WindowArgs &a)
 {
     constexpr int GPW = 256 / TPQ;
+    if (a.cuts) {
+        auto kc = k_rank_window_cuts<WORDS, TPQ, NC>;
+        if (plan.lds > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds);
+            if (e != hipSuccess) WV_FAIL(WV_EHIP, "rank_window_cuts: hipFuncSetAttribute(%zu): %s", plan.lds, hipGetErrorString(e));
+        }
+        hipLaunchKernelGGL(kc, dim3((unsigned)ceil_div(a.Q, GPW)), dim3(256), plan.lds, a.st, a.q, (const uint4 *)a.img, a.Q, a.N, plan.C,
+                           a.nbins, (int)(plan.lds / GPW), a.apx, *a.cuts);
+        WV_CHECK_LAUNCH("k_rank_window_cuts");
+        return WV_OK;
+    }
     auto kern = a.fused ? k_rank_window<WORDS, TPQ, NC, true> : k_rank_window<WORDS, TPQ, NC, false>;
     if (plan.lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds);
@@ -778,9 +866,10 @@ int launch_window_nc(const RankPlan &plan, const WindowArgs &a)
 }  // namespace
 
 int rank2_launch(const RankPlan &plan, const uint64_t *q, const void *img, int32_t *idx, uint16_t *rows16, uint8_t *dist,
-                 uint32_t *cum, int Q, int64_t N, int nbits, int k, int64_t idx_offset, hipStream_t st, const Rank2Ap *apx)
+                 uint32_t *cum, int Q, int64_t N, int nbits, int k, int64_t idx_offset, hipStream_t st, const Rank2Ap *apx,
+                 const ApCuts *cuts)
 {
-    const WindowArgs a{q, img, idx, rows16, dist, cum, Q, N, nbits + 1, k, idx_offset, st, apx != nullptr, apx ? *apx : Rank2Ap{}};
+    const WindowArgs a{q, img, idx, rows16, dist, cum, Q, N, nbits + 1, k, idx_offset, st, apx != nullptr, apx ? *apx : Rank2Ap{}, cuts};
     const bool wave = plan.kernel == RankKernel::window64;
     if (nbits <= 64) return wave ? launch_window_nc<1, 64>(plan, a) : launch_window_nc<1, 256>(plan, a);
     return wave ? launch_window_nc<2, 64>(plan, a) : launch_window_nc<2, 256>(plan, a);

@@ -814,17 +814,17 @@ namespace wv {
 // merged relevance string is the concatenation, bin by bin and shard by shard, of runs of the shards' strings; it is
 // assembled in LDS (k bits) with shifted 32-bit copies and walked exactly as k_map_at_k walks a list (ap_walk.hpp).
 // need_out: as in k_merge_cum.
-__global__ __launch_bounds__(256) void k_merge_relbits_ap(const uint32_t *__restrict__ relbits, const uint32_t *__restrict__ cum,
-                                                          int G, int Q, int kin, int w32, int k, int nbins,
-                                                          float *__restrict__ ap, int32_t *__restrict__ nrel,
-                                                          int32_t *__restrict__ need_out, int64_t rb_ld32, int64_t cum_ld)
+// Assembles the merged string of query blockIdx.x in LDS (layout above); ends with a workgroup barrier.  M: the string,
+// scratch: free LDS behind it (8-byte aligned).
+__device__ __forceinline__ void merge_relbits_string(uint4 *lds4, const uint32_t *__restrict__ relbits, const uint32_t *__restrict__ cum,
+                                                     int G, int Q, int kin, int w32, int k, int nbins, int32_t *__restrict__ need_out,
+                                                     int64_t rb_ld32, int64_t cum_ld, uint32_t *&M, uint32_t *&scratch)
 {
-    extern __shared__ uint4 lds4[];
     int32_t *start = reinterpret_cast<int32_t *>(lds4);           // [G][nbins + 1]: first position with dist >= b
     uint32_t *base = reinterpret_cast<uint32_t *>(start + G * (nbins + 1));   // [nbins + 1]
-    uint32_t *M = base + nbins + 1;                               // merged relevance string, k bits (+ spill word)
+    M = base + nbins + 1;                                         // merged relevance string, k bits (+ spill word)
     const int mwords = (k + 31) / 32 + 1;
-    uint32_t *scratch = M + mwords + (mwords & 1);                // ap_final's doubles: 8-byte aligned
+    scratch = M + mwords + (mwords & 1);                          // ap_final's doubles: 8-byte aligned
     const int qi = blockIdx.x, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
     merge_starts_from_cum(cum, cum_ld, G, Q, qi, kin, nbins, start, tid);
     for (int u = tid; u < mwords; u += 256) M[u] = 0;
@@ -853,6 +853,17 @@ __global__ __launch_bounds__(256) void k_merge_relbits_ap(const uint32_t *__rest
         }
     }
     __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_merge_relbits_ap(const uint32_t *__restrict__ relbits, const uint32_t *__restrict__ cum,
+                                                          int G, int Q, int kin, int w32, int k, int nbins,
+                                                          float *__restrict__ ap, int32_t *__restrict__ nrel,
+                                                          int32_t *__restrict__ need_out, int64_t rb_ld32, int64_t cum_ld)
+{
+    extern __shared__ uint4 lds4[];
+    uint32_t *M, *scratch;
+    merge_relbits_string(lds4, relbits, cum, G, Q, kin, w32, k, nbins, need_out, rb_ld32, cum_ld, M, scratch);
+    const int qi = blockIdx.x, tid = threadIdx.x, lane = lane_id(), wv = wave_id();
     const int R = (k + 255) / 256;
     double *wsum = reinterpret_cast<double *>(scratch + kApRounds * 4 + (kApRounds * 4 & 1));
     ApState st;
@@ -871,6 +882,88 @@ __global__ __launch_bounds__(256) void k_merge_relbits_ap(const uint32_t *__rest
         __syncthreads();
     }
     ap_final<256>(st, wsum, tid, ap + qi, nrel ? nrel + qi : nullptr, [] { __syncthreads(); });
+}
+
+// One chunk of relevance bits -> the walk at several cut-offs: what the merge and the list kernel below share.  rel_at(p) =
+// relevance of list position p < k (free of side effects: the last position is asked again for the padding of the last
+// round); ap / nrel: the query's rows of cuts.n entries.
+template <typename REL>
+__device__ __forceinline__ void walk_cuts_256(REL rel_at, int k, uint32_t *scratch, const ApCuts &cuts, float *__restrict__ ap,
+                                              int32_t *__restrict__ nrel)
+{
+    constexpr int CH = 8;
+    const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
+    const int R = (k + 255) / 256;
+    double *wsum = reinterpret_cast<double *>(scratch + kApRounds * 4 + (kApRounds * 4 & 1));
+    uint32_t *wcut = reinterpret_cast<uint32_t *>(wsum + 4);
+    ApState st;
+    int next = 0;
+    for (int c0 = 0; c0 < R; c0 += kApRounds) {
+        const int Rc = min(kApRounds, R - c0);
+        uint32_t mine = 0;
+        for (int r0 = 0; r0 < Rc; r0 += CH) {                     // a batch's reads are issued before the first is used
+            bool rv[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) rv[u] = rel_at(min((c0 + r0 + u) * 256 + tid, k - 1));
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const int r = r0 + u;
+                const bool rel = r < Rc && (c0 + r) * 256 + tid < k && rv[u];
+                mine |= (rel ? 1u : 0u) << (r & 31);
+                const uint64_t m = __ballot(rel);
+                if (lane == 0 && r < Rc) scratch[r * 4 + wv] = (uint32_t)__popcll(m);
+            }
+        }
+        __syncthreads();
+        ap_accum_cuts<256>(mine, scratch, Rc, c0, tid, st, cuts, next, wsum, wcut, ap, nrel, [] { __syncthreads(); });
+        __syncthreads();
+    }
+}
+
+// k_merge_relbits_ap at several cut-offs: the string is assembled for k = the largest, ap / nrel are [Q][cuts.n].
+__global__ __launch_bounds__(256) void k_merge_relbits_ap_cuts(const uint32_t *__restrict__ relbits, const uint32_t *__restrict__ cum,
+                                                               int G, int Q, int kin, int w32, int nbins, float *__restrict__ ap,
+                                                               int32_t *__restrict__ nrel, int32_t *__restrict__ need_out,
+                                                               int64_t rb_ld32, int64_t cum_ld, ApCuts cuts)
+{
+    extern __shared__ uint4 lds4[];
+    const int k = cuts.k[cuts.n - 1], qi = blockIdx.x;
+    uint32_t *M, *scratch;
+    merge_relbits_string(lds4, relbits, cum, G, Q, kin, w32, k, nbins, need_out, rb_ld32, cum_ld, M, scratch);
+    walk_cuts_256([M](int p) { return ((M[p >> 5] >> (p & 31)) & 1u) != 0; }, k, scratch, cuts, ap + (int64_t)qi * cuts.n,
+                  nrel ? nrel + (int64_t)qi * cuts.n : nullptr);
+}
+
+// k_map_at_k at several cut-offs: the list is read and the labels are gathered once, ap / nrel are [Q][cuts.n].  The walk is
+// ap_walk.hpp's, whose order is k_map_at_k's: every column has the bits of a k_map_at_k launch with that k.
+template <int LW>
+__global__ __launch_bounds__(256) void k_map_at_ks(const int32_t *__restrict__ idx, int64_t ld, const uint64_t *__restrict__ qlab,
+                                                   const uint64_t *__restrict__ dblab, int lwords, float *__restrict__ ap,
+                                                   int32_t *__restrict__ nrel, ApCuts cuts)
+{
+    __shared__ __attribute__((aligned(8))) uint32_t scratch[ap_cuts_scratch_dwords<256>()];
+    const int qi = blockIdx.x, k = cuts.k[cuts.n - 1];
+    const int32_t *list = idx + (int64_t)qi * ld;
+    const int lw = LW > 0 ? LW : lwords;
+    const uint64_t *ql = qlab + (int64_t)qi * lw;
+    uint64_t qreg[LW > 0 ? LW : 1];
+    if constexpr (LW > 0) {
+#pragma unroll
+        for (int w = 0; w < LW; ++w) qreg[w] = ql[w];
+    }
+    auto rel_at = [&](int p) {
+        const int32_t id = list[p];
+        const uint64_t *dl = dblab + (int64_t)max(id, 0) * lw;   // an absent entry (< 0) reads row 0 and counts as no hit
+        uint64_t any = 0;
+        if constexpr (LW > 0) {
+#pragma unroll
+            for (int w = 0; w < LW; ++w) any |= dl[w] & qreg[w];
+        } else {
+            for (int w = 0; w < lw; ++w) any |= dl[w] & ql[w];
+        }
+        return id >= 0 && any != 0;
+    };
+    walk_cuts_256(rel_at, k, scratch, cuts, ap + (int64_t)qi * cuts.n, nrel ? nrel + (int64_t)qi * cuts.n : nullptr);
 }
 }  // namespace wv
 
@@ -1065,6 +1158,94 @@ extern "C" int wv_merge_relbits_map(const uint64_t *relbits, int64_t relbits_ld,
                        cum, G, Q, kin, w32, k, nbins, ap, nrel, need_out, relbits_ld ? 2 * relbits_ld : (int64_t)w32,
                        cum_ld ? cum_ld : (int64_t)(nbins + 1));
     WV_CHECK_LAUNCH("k_merge_relbits_ap");
+    return WV_OK;
+}
+
+// ---------------------------------------------------------------------------------- average precision at several cut-offs
+// The cut-offs of a call (HOST pointer): 1 .. WV_MAX_CUTOFFS of them, strictly ascending, inside [1, limit].
+static int validate_cuts(const char *what, const int *ks, int nk, int64_t limit, const char *limit_name, ApCuts &cuts)
+{
+    static_assert(kMaxCutoffs == WV_MAX_CUTOFFS, "ap_walk.hpp and wvhash.h disagree");
+    WV_REQUIRE(ks, "%s: null cut-off list", what);
+    WV_REQUIRE(nk >= 1 && nk <= kMaxCutoffs, "%s: %d cut-offs (supported: 1..%d)", what, nk, kMaxCutoffs);
+    cuts.n = nk;
+    for (int i = 0; i < kMaxCutoffs; ++i) cuts.k[i] = i < nk ? ks[i] : 0;
+    WV_REQUIRE(ks[0] >= 1, "%s: cut-off %d must be >= 1", what, ks[0]);
+    for (int i = 1; i < nk; ++i)
+        WV_REQUIRE(ks[i] > ks[i - 1], "%s: cut-offs must be strictly ascending (ks[%d]=%d after %d)", what, i, ks[i], ks[i - 1]);
+    WV_REQUIRE(ks[nk - 1] <= limit, "%s: largest cut-off %d must be <= %s=%lld", what, ks[nk - 1], limit_name, (long long)limit);
+    return WV_OK;
+}
+
+extern "C" int wv_hamming_map_at_ks(const uint64_t *q, const void *prepared, const void *prepared_labels, const uint64_t *qlab,
+                                    int lwords, int Q, int64_t N, int nbits, const int *ks, int nk, float *ap, int32_t *nrel,
+                                    void *stream)
+{
+    WV_REQUIRE(lwords >= 1, "hamming_map_at_ks: lwords=%d", lwords);
+    if (lwords > 2) WV_FAIL(WV_ENOTSUP, "hamming_map_at_ks: %d label words (more than 128 classes): wv_hamming_topk + wv_map_at_ks", lwords);
+    if (int rc = validate_rank_shape("hamming_map_at_ks", q && prepared && prepared_labels && qlab && ap, Q, N, nbits)) return rc;
+    ApCuts cuts;
+    if (int rc = validate_cuts("hamming_map_at_ks", ks, nk, N, "N", cuts)) return rc;
+    if (Q == 0) return WV_OK;
+    const int kmax = cuts.k[nk - 1];
+    const RankPlan plan = rank_plan(Q, N, nbits, kmax, RankMode::ap);    // list, window, LDS and bitmap: sized by the largest cut-off
+    if (plan.kernel == RankKernel::none)
+        WV_FAIL(WV_ENOTSUP, "hamming_map_at_ks: %lld rows / largest cut-off %d %s; call wv_hamming_topk + wv_map_at_ks instead",
+                (long long)N, kmax, plan.why);
+    const Rank2Ap apx{(const uint32_t *)prepared_labels, qlab, lwords, ap, nrel, nullptr, 0, 0};
+    return rank2_launch(plan, q, blob_image(prepared, N, (nbits + 63) / 64, plan.kernel), nullptr, nullptr, nullptr, nullptr, Q, N, nbits,
+                        kmax, 0, (hipStream_t)stream, &apx, &cuts);
+}
+
+// dynamic LDS of k_merge_relbits_ap_cuts: run boundaries [G][nbins + 1], bin bases, the kmax-bit merged string, the walk's scratch
+extern "C" size_t wv_merge_relbits_map_ks_lds_bytes(int G, int kmax, int nbits)
+{
+    if (G < 1 || kmax < 1 || nbits < 1 || nbits > 128) return 0;
+    const int nbins = nbits + 1;
+    const size_t mwords = (size_t)(kmax + 31) / 32 + 1;
+    return ((size_t)G * (nbins + 1) + nbins + 1 + ap_cuts_scratch_dwords<256>() + 4) * 4 + (mwords + (mwords & 1)) * 4;
+}
+
+extern "C" int wv_merge_relbits_map_ks(const uint64_t *relbits, int64_t relbits_ld, const uint32_t *cum, int64_t cum_ld, int G, int Q,
+                                       int kin, const int *ks, int nk, int nbits, float *ap, int32_t *nrel, int32_t *need_out,
+                                       void *stream)
+{
+    WV_REQUIRE((relbits_ld == 0 || relbits_ld >= (kin + 63) / 64) && (cum_ld == 0 || cum_ld >= nbits + 2),
+               "merge_relbits_map_ks: row pitches %lld / %lld too small", (long long)relbits_ld, (long long)cum_ld);
+    WV_REQUIRE(relbits && cum && ap, "merge_relbits_map_ks: null buffer");
+    WV_REQUIRE(G >= 1 && Q >= 0 && kin >= 1, "merge_relbits_map_ks: bad shape G=%d Q=%d kin=%d", G, Q, kin);
+    if (int rc = require_nbits("merge_relbits_map_ks", nbits)) return rc;
+    ApCuts cuts;
+    if (int rc = validate_cuts("merge_relbits_map_ks", ks, nk, 0x7fffffff, "INT_MAX", cuts)) return rc;
+    if (Q == 0) return WV_OK;
+    const int kmax = cuts.k[nk - 1], nbins = nbits + 1, w32 = 2 * (int)ceil_div(kin, 64);
+    const size_t lds = wv_merge_relbits_map_ks_lds_bytes(G, kmax, nbits), limit = WV_MERGE_RELBITS_LDS_LIMIT;
+    if (lds > limit)
+        WV_FAIL(WV_ENOTSUP, "merge_relbits_map_ks: the merged string of the largest cut-off %d does not fit LDS beside the run boundaries "
+                "of G=%d shards (%zu bytes needed, %zu available)", kmax, G, lds, limit);
+    hipLaunchKernelGGL(k_merge_relbits_ap_cuts, dim3(Q), dim3(256), lds, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(relbits),
+                       cum, G, Q, kin, w32, nbins, ap, nrel, need_out, relbits_ld ? 2 * relbits_ld : (int64_t)w32,
+                       cum_ld ? cum_ld : (int64_t)(nbins + 1), cuts);
+    WV_CHECK_LAUNCH("k_merge_relbits_ap_cuts");
+    return WV_OK;
+}
+
+extern "C" int wv_map_at_ks(const int32_t *idx, int64_t ld, int Q, const int *ks, int nk, const uint64_t *qlab, const uint64_t *dblab,
+                            int lwords, float *ap, int32_t *nrel, void *stream)
+{
+    WV_REQUIRE(idx && qlab && dblab && ap, "map_at_ks: null buffer");
+    WV_REQUIRE(Q >= 0 && lwords >= 1 && ld >= 1, "map_at_ks: bad shape Q=%d ld=%lld lwords=%d", Q, (long long)ld, lwords);
+    ApCuts cuts;
+    if (int rc = validate_cuts("map_at_ks", ks, nk, ld, "ld", cuts)) return rc;
+    if (Q == 0) return WV_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (lwords == 1)
+        hipLaunchKernelGGL((k_map_at_ks<1>), dim3(Q), dim3(256), 0, st, idx, ld, qlab, dblab, lwords, ap, nrel, cuts);
+    else if (lwords == 2)
+        hipLaunchKernelGGL((k_map_at_ks<2>), dim3(Q), dim3(256), 0, st, idx, ld, qlab, dblab, lwords, ap, nrel, cuts);
+    else
+        hipLaunchKernelGGL((k_map_at_ks<0>), dim3(Q), dim3(256), 0, st, idx, ld, qlab, dblab, lwords, ap, nrel, cuts);
+    WV_CHECK_LAUNCH("k_map_at_ks");
     return WV_OK;
 }
 

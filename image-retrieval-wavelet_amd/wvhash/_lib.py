@@ -97,6 +97,11 @@ SIGNATURES = {
     "wv_rank_from_dist": (_i, [_vp, _i64, _i, _i64, _i, _vp, _vp, _i, _vp]),
     "wv_map_at_k": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "wv_map_at_k_ld": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "wv_hamming_map_at_ks": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _i, _vp, _vp, _vp]),
+    "wv_merge_relbits_map_ks": (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "wv_merge_relbits_map_ks_lds_bytes": (_sz, [_i, _i, _i]),
+    "wv_map_at_ks": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "wv_map_at_ks_cpu": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "wv_topk_merge_cum": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i, _i, _vp]),
     "wv_topk_merge_cum_need": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i, _i, _vp, _vp]),
     "wv_hit_prefix": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),

@@ -8,6 +8,7 @@ reference's own configuration, main/engine/evaluate.py:76-81; BASELINE config c0
 of the same entry points (csrc/host_rank.cpp; same integers, same AP bits) -- and routes the arithmetic through libwvhash:
   calc_hamming_dist       -> wv_hamming_dist        (:183-186)
   calculate_maphashing    -> wv_hamming_topk + wv_map_at_k   (:203-231, the reported metric)
+  calculate_maphashing_at -> wv_hamming_map_at_ks / wv_map_at_ks: the same at several cut-offs from one ranking pass
   calculate_bit_balance / calculate_worst_bit_balance -> wv_bit_counts   (:188-200)
   calculate_map           -> get_knn + wv_map_at_k  (:156-167, torchmetrics RetrievalMAP)
   calculate_rpr / calculate_pr / calculate_pr_rc / calculate_pr_rc_hashing -> wv_hit_prefix (:131-181, :235-273)
@@ -25,6 +26,7 @@ from .get_knn import get_knn, _to_gpu, _is_pm1
 LOGGER = logging.getLogger("RETRIEVAL")
 
 _RECALL_KS = (1, 2, 4, 8, 10, 16, 20, 30, 32, 100, 1000)
+_NOT_METRICS = ("calculate_maphashing_at",)     # calculate_* methods that take cut-offs of their own: not get_accuracy columns
 
 
 class RankCache(object):
@@ -33,9 +35,10 @@ class RankCache(object):
     reads a prefix (the reference re-runs its whole per-query loop for every k, main/engine/evaluate.py:226-243).
     Entries are keyed by tensor identity (storage pointer, shape, version counter): new embeddings invalidate them."""
 
-    def __init__(self, kmax_hint=0):
-        self.kmax_hint = int(kmax_hint)
-        self._codes, self._labels, self._lists = {}, {}, None
+    def __init__(self, kmax_hint=0, ks=()):
+        self.ks = sorted({int(k) for k in ks if isinstance(k, int) and not isinstance(k, bool) and k > 0})   # the run's cut-offs
+        self.kmax_hint = max([int(kmax_hint)] + self.ks)
+        self._codes, self._labels, self._lists, self._aps, self._prep = {}, {}, None, None, None
 
     @staticmethod
     def _key(t):
@@ -62,6 +65,40 @@ class RankCache(object):
             idx, dist = H.hamming_topk(self.packed_codes(query), self.packed_codes(reference), reference.shape[1], kk)
             self._lists = (key, idx, dist)
         return self._lists[1]
+
+    def maphashing(self, query, query_labels, reference, reference_labels, topk, also=()):
+        """Average precision per query at `topk` (float32 [Q]).  The first call for an embedding pair answers ALL the run's
+        cut-offs (and those in `also`: further cut-offs the caller will ask for next) from one pass and keeps the columns: from the cached lists (wv_map_at_ks) when a k-NN metric already made
+        them, otherwise from the fused ranking + AP pass (wv_hamming_map_at_ks), so that no [Q, k_max] list exists."""
+        num_ref, nbits = reference.shape
+        topk = min(int(topk), num_ref)
+        key = (self._key(query), self._key(reference), self._key(query_labels), self._key(reference_labels))
+        if self._aps is None or self._aps[0] != key:
+            self._aps = (key, {})
+        done = self._aps[1]
+        if topk not in done:
+            want = sorted({min(int(k), num_ref) for k in (*self.ks, *also)} | {topk})
+            qlp, rlp = self.packed_labels(query_labels, reference_labels)
+            for s in range(0, len(want), H.MAX_CUTOFFS):
+                ks = want[s:s + H.MAX_CUTOFFS]
+                ap = None
+                have = self._lists is not None and self._lists[0] == key[:2] and self._lists[1].shape[1] >= ks[-1]
+                if not have and nbits <= 128 and rlp.shape[1] <= 2:
+                    prepared = self._prepared(reference, rlp)
+                    got = H.hamming_map_at_ks(self.packed_codes(query), prepared[0], prepared[1], qlp, nbits, ks)
+                    ap = got[0] if got is not None else None
+                if ap is None:
+                    ap = H.map_at_ks(self.lists(query, reference, ks[-1]), qlp, rlp, ks)[0]
+                for i, k in enumerate(ks):
+                    done[k] = ap[:, i]
+        return done[topk]
+
+    def _prepared(self, reference, rlp):
+        """(PreparedDB, PreparedLabels) of the reference set, laid out once per embedding pair."""
+        key = (self._key(reference), rlp.data_ptr())
+        if self._prep is None or self._prep[0] != key:
+            self._prep = (key, (H.PreparedDB(self.packed_codes(reference), reference.shape[1]), H.PreparedLabels(rlp)))
+        return self._prep[1]
 
     def knn(self, reference, query, num_k, same_source):
         """get_knn(..., distance_metric='hamming') from the cached ranking: (indices int64, inner products fp32)."""
@@ -100,7 +137,7 @@ class CustomCalculator(object):
         if self.host and self.rank_cache is not None:
             raise ValueError("a shared RankCache holds GPU lists: not available with device='cpu'")
         self.original_function_dict = {name[len("calculate_"):]: getattr(self, name)
-                                       for name in dir(self) if name.startswith("calculate_")}
+                                       for name in dir(self) if name.startswith("calculate_") and name not in _NOT_METRICS}
         self.check_primary_metrics(include, exclude)
         self.original_function_dict = self.get_function_dict(include, exclude)
         self.curr_function_dict = self.get_function_dict()
@@ -244,6 +281,8 @@ class CustomCalculator(object):
                 else:                                    # outside the fused kernel: rank with the database already prepared
                     idx = H.hamming_topk(H.pack_codes(query), prepared, nbits, topk, want_dist=False)[0]
                     ap, _ = H.map_at_k(idx, qlp, rlp, k=topk)
+        if ap is None and self.rank_cache is not None:
+            ap = self.rank_cache.maphashing(query, query_labels, reference, reference_labels, topk)   # all the run's k at once
         if ap is None:
             idx = self._ranked_lists(query, reference, topk)
             ap, _ = self._average_precisions(idx, query_labels, reference_labels, k=topk)
@@ -251,6 +290,38 @@ class CustomCalculator(object):
         if return_per_query:
             return result, ap
         return result
+
+    def calculate_maphashing_at(self, query, query_labels, reference, reference_labels, ks, ref_includes_query=False,
+                                return_per_query=False, **kwargs):
+        """calculate_maphashing at several cut-offs from ONE ranking pass -> {k: value} (return_per_query: {k: (value, ap
+        float32 [Q])}), each value what calculate_maphashing returns for topk = k.  ks: positive ints in any order, repeats
+        allowed; a cut-off beyond the reference set clips at its size like gnd[0:topk]."""
+        ks = list(ks)
+        if not ks or not all(isinstance(k, int) and not isinstance(k, bool) and k > 0 for k in ks):
+            raise ValueError("calculate_maphashing_at: ks must be a non-empty sequence of positive ints")
+        query, reference = self._dev(query), self._dev(reference)
+        query_labels, reference_labels = self._dev(query_labels), self._dev(reference_labels)
+        num_query, (num_ref, nbits) = query.shape[0], reference.shape
+        if num_query == 0:
+            raise ZeroDivisionError("calculate_maphashing_at: no queries")
+        eff = [min(k, num_ref) for k in ks]
+        cols = {}
+        if self.host:
+            qlp, rlp = self._packed_labels(query_labels, reference_labels, HH)
+            uniq = sorted(set(eff))
+            idx = HH.hamming_topk(HH.pack_codes(query), HH.pack_codes(reference), nbits, uniq[-1], want_dist=False)[0]
+            for s in range(0, len(uniq), HH.MAX_CUTOFFS):
+                ap = HH.map_at_ks(idx, qlp, rlp, uniq[s:s + HH.MAX_CUTOFFS])[0]
+                cols.update({k: ap[:, i] for i, k in enumerate(uniq[s:s + HH.MAX_CUTOFFS])})
+        else:
+            cache = self.rank_cache if self.rank_cache is not None else RankCache()
+            for k in eff:
+                cols[k] = cache.maphashing(query, query_labels, reference, reference_labels, k, also=eff)
+        out = {}
+        for k, ke in zip(ks, eff):
+            value = cols[ke].double().sum().item() / num_query
+            out[k] = (value, cols[ke]) if return_per_query else value
+        return out
 
     # ------------------------------------------------------------------ knn metrics
     def calculate_map(self, query_labels, knn_indices, reference_labels, not_lone_query_mask, **kwargs):

@@ -214,9 +214,11 @@ def evaluate(net, train_dataset=None, val_dataset=None, test_dataset=None, epoch
 @_preserve_rng
 def evaluate_multi_k(net, train_dataset=None, val_dataset=None, test_dataset=None, epoch=None, custom_eval=None,
                      k_list=(5000,), **kwargs):
-    """Embeds once and ranks once: the calculators of all k share a RankCache -- packed codes, packed labels and the
-    ranked lists at the largest k; every smaller k is a prefix.  Returns {k: {split: {metric: value}}} like the
-    reference, which re-runs the whole ranking per k (main/engine/evaluate.py:226-243)."""
+    """Embeds once and ranks once: the calculators of all k share a RankCache -- packed codes, packed labels and, when a k-NN
+    metric is computed, the ranked lists at the largest k (every smaller k is a prefix).  maphashing is answered for all the
+    integer cut-offs at once: from those lists, or -- no k-NN metric -- from one fused ranking + AP pass that writes no list.
+    Returns {k: {split: {metric: value}}} like the reference, which re-runs the whole ranking per k
+    (main/engine/evaluate.py:226-243)."""
     from .accuracy_calculator import RankCache
     dataset_dict, splits_to_eval = _build_dataset_dict_and_splits(train_dataset, val_dataset, test_dataset, custom_eval)
     k_list = list(k_list)
@@ -226,7 +228,7 @@ def evaluate_multi_k(net, train_dataset=None, val_dataset=None, test_dataset=Non
     LOGGER.info(f"Computing embeddings once, reused for k in {k_list}")
     emb = tester.get_all_embeddings_for_all_splits(dataset_dict, net, None, needed)
     ints = [k for k in k_list if isinstance(k, int)]
-    cache = RankCache(kmax_hint=max(ints) if ints else 0)
+    cache = RankCache(kmax_hint=max(ints) if ints else 0, ks=ints)     # maphashing: every cut-off from one pass
     results_by_k = {}
     for k in k_list:
         tester.accuracy_calculator = get_tester(k=k, rank_cache=cache, **kwargs).accuracy_calculator
@@ -259,6 +261,9 @@ def evaluate_sharded(net, test_dataset, k=5000, epoch=None, batch_size=64, num_w
       most 32,768 rows: MIRFLICKR and COCO at k = 5000; otherwise lists are exchanged, the packed database labels
       all-gathered (8 bytes per row and label word) and AP computed from the merged lists: the same numbers;
     * the AP sums and the per-bit counts are all-reduced.
+    ``k`` may be a sequence of cut-offs (evaluate_all_checkpoints.py --k 5000,117218): still one ranking pass per shard, one
+    all_gather and one all_to_all, sized by the largest; the result is then ``{k: {"test": {...}}}``.  More than 16 different
+    cut-offs are answered from exchanged lists, 16 per pass over them.
     Returns ``{"test": {"epoch", "maphashing_level0", "map_level0", "bit_balance_level0", "worst_bit_balance_level0"}}`` -- the
     four columns evaluate_all_checkpoints.py:173-174 reads into its CSVs --, the same
     numbers as evaluate() on one GPU (lists are identical for every world size; AP sums differ by fp64 rounding only).
@@ -271,7 +276,12 @@ def evaluate_sharded(net, test_dataset, k=5000, epoch=None, batch_size=64, num_w
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     if not (isinstance(test_dataset, dict) and "gallery" in test_dataset and "test" in test_dataset):
         raise ValueError("evaluate_sharded expects {'test': query dataset, 'gallery': database dataset}")
-    tester = get_tester(batch_size=batch_size, num_workers=num_workers, k=k, **kwargs)
+    # k: one cut-off, or a sequence of them -- answered from ONE ranking pass and ONE exchange sized by the largest
+    multi = isinstance(k, (tuple, list))
+    k_list = list(k) if multi else [k]
+    if multi and not k_list:
+        raise ValueError("evaluate_sharded: empty k sequence")
+    tester = get_tester(batch_size=batch_size, num_workers=num_workers, k=k_list[0], **kwargs)   # embeds; the metrics are below
     net.eval()
     n_db, n_q = len(test_dataset["gallery"]), len(test_dataset["test"])
     lo, hi, _ = _even_slice(n_db, world, rank)
@@ -310,12 +320,14 @@ def evaluate_sharded(net, test_dataset, k=5000, epoch=None, batch_size=64, num_w
     rlp_local = torch.zeros((per_db, lw), dtype=torch.int64, device=dev)
     if r_codes is not None:
         rlp_local[:hi - lo] = H.pack_labels(r_lab.float())
-    k_eff = min(int(k), n_db) if k is not None else n_db
+    k_effs = [min(int(kk), n_db) if kk is not None else n_db for kk in k_list]
+    k_max = max(k_effs)
+    k_arg = k_effs if multi else k_effs[0]
     ap = None
-    if world > 1 and lw in (1, 2) and nbits <= 128 and min(k_eff, per_db) <= H.RANK_K_MAX and per_db <= H.SHARD_ROWS_MAX:
+    if world > 1 and lw in (1, 2) and nbits <= 128 and min(k_max, per_db) <= H.RANK_K_MAX and per_db <= H.SHARD_ROWS_MAX:
         # mAP from relevance strings: no list and no database label leaves its GPU (decided from values every rank shares)
         shard_labels = H.PreparedLabels(rlp_local[:hi - lo].contiguous()) if hi > lo else None
-        got = sharded_hamming_map_at_k(qp, qlp, H.PreparedDB(rp, nbits), shard_labels, nbits, k_eff, n_db, None, group=group)
+        got = sharded_hamming_map_at_k(qp, qlp, H.PreparedDB(rp, nbits), shard_labels, nbits, k_arg, n_db, None, group=group)
         ap = got[0] if got is not None else None
     if ap is None:
         if world > 1:
@@ -323,10 +335,19 @@ def evaluate_sharded(net, test_dataset, k=5000, epoch=None, batch_size=64, num_w
             _all_gather(rlp_all, rlp_local, group)
         else:
             rlp_all = rlp_local
-        idx, _ = sharded_hamming_topk(qp, rp, nbits, k_eff, n_db, group=group, want_dist=False)
+        idx, _ = sharded_hamming_topk(qp, rp, nbits, k_max, n_db, group=group, want_dist=False)
         # global row g of shard s sits at row s * per_db + (g - lo_s) of the gathered label table = g (shards are contiguous
         # slices of equal length per_db, the last one shorter): the gathered table is indexed by the global row directly
-        ap, _ = H.map_at_k(idx, qlp, rlp_all)
+        if multi:                                                # wv_map_at_ks takes MAX_CUTOFFS different cut-offs per pass
+            uniq = sorted(set(k_effs))
+            cols = {}
+            for s in range(0, len(uniq), H.MAX_CUTOFFS):
+                part = H.map_at_ks(idx, qlp, rlp_all, uniq[s:s + H.MAX_CUTOFFS])[0]
+                cols.update({kk: part[:, i] for i, kk in enumerate(uniq[s:s + H.MAX_CUTOFFS])})
+            ap = torch.stack([cols[kk] for kk in k_effs], dim=1)
+        else:
+            ap = H.map_at_k(idx, qlp, rlp_all)[0]
+    ap_cols = ap if multi else ap.unsqueeze(1)                     # [Ql, cut-offs]
     # map_level0 (calculate_map, accuracy_calculator.py:156-167): the same average precisions, averaged over the queries
     # that are not "lone" -- at least one database row anywhere shares a label with them (a lone query's AP is 0, so the
     # numerator is the one of maphashing).  Every rank tests all queries' label words against its shard's; MAX-reduced.
@@ -343,18 +364,26 @@ def evaluate_sharded(net, test_dataset, k=5000, epoch=None, batch_size=64, num_w
     if world > 1:
         _all_reduce(has, dist.ReduceOp.MAX, group)
     not_lone = has[rank * q_per:rank * q_per + n_local_q] if world > 1 else has[:n_local_q]
-    sums = torch.zeros(3 + nbits, dtype=torch.float64, device=dev)
-    sums[0] = ap[:n_local_q].double().sum()
-    sums[1] = float(hi - lo)
-    sums[2] = not_lone.double().sum()
+    nk = len(k_list)
+    sums = torch.zeros(2 + nk + nbits, dtype=torch.float64, device=dev)    # [rows, kept queries, AP sum per cut-off, bit counts]
+    sums[0] = float(hi - lo)
+    sums[1] = not_lone.double().sum()
+    for i in range(nk):
+        sums[2 + i] = ap_cols[:n_local_q, i].double().sum()
     if hi > lo:
-        sums[3:] = H.bit_counts(rp, nbits).double()
+        sums[2 + nk:] = H.bit_counts(rp, nbits).double()
     if world > 1:
         _all_reduce(sums, dist.ReduceOp.SUM, group)
-    frac = sums[3:] / sums[1]
+    frac = sums[2 + nk:] / sums[0]
     balance = 1.0 - 2.0 * (frac - 0.5).abs()
-    kept = float(sums[2].item())
-    return {"test": {"epoch": f"{epoch}", "maphashing_level0": float(sums[0].item()) / n_q,
-                     "map_level0": float(sums[0].item()) / kept if kept else 0.0,
-                     "bit_balance_level0": float(balance.mean().item()),
-                     "worst_bit_balance_level0": float(balance.min().item())}}
+    kept = float(sums[1].item())
+
+    def columns(i):
+        ap_sum = float(sums[2 + i].item())
+        return {"test": {"epoch": f"{epoch}", "maphashing_level0": ap_sum / n_q,
+                         "map_level0": ap_sum / kept if kept else 0.0,
+                         "bit_balance_level0": float(balance.mean().item()),
+                         "worst_bit_balance_level0": float(balance.min().item())}}
+    if multi:
+        return {kk: columns(i) for i, kk in enumerate(k_list)}
+    return columns(0)

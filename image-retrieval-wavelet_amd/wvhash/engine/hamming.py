@@ -66,6 +66,7 @@ def bit_counts(packed, nbits):
 
 
 SHARD_ROWS_MAX = 32768      # wv_hamming_hist / wv_hamming_topk_rows16 take shards up to this many rows
+MAX_CUTOFFS = 16            # WV_MAX_CUTOFFS: different cut-offs one multi-k call takes
 RANK_K_MAX = 32639          # longest list the windowed kernel builds (its 16-bit cells count list bytes: 2 (k + 128) < 65536)
 
 
@@ -336,6 +337,29 @@ def map_at_k(idx, qlab_packed, dblab_packed, k=None):
     return ap, nrel
 
 
+def map_at_ks(idx, qlab_packed, dblab_packed, ks):
+    """map_at_k for several cut-offs from ONE pass over the lists (read once, labels gathered once)
+    -> (ap float32 [Q, len(ks)], nrel int32 [Q, len(ks)]), column i = map_at_k(idx, ..., k=ks[i])."""
+    lib = _lib.require_gpu()
+    Q, kfull = idx.shape
+    uniq, c_ks, cols = _cutoffs(ks, "map_at_ks")
+    if uniq[-1] > kfull:
+        raise ValueError(f"map_at_ks: cut-off {uniq[-1]} outside the lists' length {kfull}")
+    lw = qlab_packed.shape[1]
+    if dblab_packed.shape[1] != lw:
+        raise ValueError("map_at_ks: label widths differ")
+    if idx.stride(1) != 1:
+        idx = idx.contiguous()
+    ap = torch.empty((Q, len(uniq)), dtype=torch.float32, device=idx.device)
+    nrel = torch.empty((Q, len(uniq)), dtype=torch.int32, device=idx.device)
+    if Q:
+        with torch.cuda.device(idx.device):
+            rc = lib.wv_map_at_ks(_lib.ptr(idx), idx.stride(0), Q, c_ks, len(uniq), _lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw,
+                                  _lib.ptr(ap), _lib.ptr(nrel), _lib.stream_ptr())
+            _lib.check(rc, "wv_map_at_ks")
+    return _columns(ap, nrel, cols)
+
+
 class PreparedLabels:
     """The database rows' packed label words laid out for the fused ranking + AP kernel (wv_rank_labels_prepare): one
     or two 64-bit multi-hot words per row (up to 128 classes), databases of at most 32,768 rows.  `ok` is False for anything else -- the caller then
@@ -400,6 +424,72 @@ def hamming_map_at_k(q_packed, db, labels, qlab_packed, nbits, k):
     return ap, nrel
 
 
+def _cutoffs(ks, what):
+    """The cut-offs of a multi-k call, as they arrive (any order, repeats allowed) -> (sorted unique list, C int array of
+    it, column of every requested cut-off in the sorted list)."""
+    ks = [int(k) for k in ks]
+    if not ks:
+        raise ValueError(f"{what}: no cut-offs")
+    uniq = sorted(set(ks))
+    if len(uniq) > MAX_CUTOFFS:
+        raise ValueError(f"{what}: {len(uniq)} different cut-offs (at most {MAX_CUTOFFS} per call)")
+    if uniq[0] < 1:
+        raise ValueError(f"{what}: cut-off {uniq[0]} must be >= 1")
+    return uniq, (ctypes.c_int * len(uniq))(*uniq), [uniq.index(k) for k in ks]
+
+
+def _columns(ap, nrel, cols):
+    """[Q, unique cut-offs] -> [Q, requested cut-offs]"""
+    if cols == list(range(ap.shape[1])):
+        return ap, nrel
+    sel = torch.tensor(cols, dtype=torch.long, device=ap.device)
+    return ap.index_select(1, sel), nrel.index_select(1, sel)
+
+
+def hamming_map_at_ks(q_packed, db, labels, qlab_packed, nbits, ks):
+    """hamming_map_at_k for several cut-offs from ONE ranking pass -> (ap float32 [Q, len(ks)], nrel int32 [Q, len(ks)]),
+    column i = what hamming_map_at_k returns for k = ks[i]; or None when the largest cut-off is outside the fused kernel
+    (the caller then runs hamming_topk at max(ks) + map_at_ks: the same numbers).  ks: any order, repeats allowed, at most
+    MAX_CUTOFFS different values."""
+    lib = _lib.require_gpu()
+    if not isinstance(db, PreparedDB) or not isinstance(labels, PreparedLabels):
+        raise TypeError("hamming_map_at_ks: needs a PreparedDB and PreparedLabels")
+    Q, words = q_packed.shape
+    if words != db.words or labels.N != db.N:
+        raise ValueError("hamming_map_at_ks: query / database / label shapes disagree")
+    uniq, c_ks, cols = _cutoffs(ks, "hamming_map_at_ks")
+    kmax = uniq[-1]
+    if kmax > db.N:
+        raise ValueError(f"hamming_map_at_ks: largest cut-off {kmax} must be <= N={db.N}")
+    if not labels.ok or qlab_packed.shape[1] != labels.words or nbits > 128:
+        return None
+    dev = q_packed.device
+    if db.parts or labels.parts:                         # more than 32,768 rows: virtual shards, one prefix length for max(ks)
+        if not (db.parts and labels.parts) or len(db.parts) != len(labels.parts) or not Q:
+            return None
+        cums = torch.stack([hamming_hist(q_packed, part, nbits) for part in db.parts])
+        send = max(1, min(kmax, db.per, _prefix_need(cums, kmax)))
+        if send > RANK_K_MAX:
+            return None
+        wires = torch.zeros((len(db.parts), Q, relbits_wire_words(send, nbits)), dtype=torch.int64, device=dev)
+        for g, (part, lab) in enumerate(zip(db.parts, labels.parts)):
+            if hamming_shard_relbits(q_packed, part, lab, qlab_packed, nbits, min(send, part.N), wire=wires[g], kin=send) is None:
+                return None
+        got = merge_relbits_map_ks(wires, send, uniq, nbits)
+        return None if got is None else _columns(*got, cols)
+    ap = torch.empty((Q, len(uniq)), dtype=torch.float32, device=dev)
+    nrel = torch.empty((Q, len(uniq)), dtype=torch.int32, device=dev)
+    if Q:
+        with torch.cuda.device(dev):
+            rc = lib.wv_hamming_map_at_ks(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
+                                          _lib.ptr(qlab_packed.contiguous()), labels.words, Q, db.N, nbits, c_ks, len(uniq),
+                                          _lib.ptr(ap), _lib.ptr(nrel), _lib.stream_ptr())
+            if rc == _lib.WV_ENOTSUP:
+                return None
+            _lib.check(rc, "wv_hamming_map_at_ks")
+    return _columns(ap, nrel, cols)
+
+
 def relbits_wire_words(kin, nbits):
     """int64 words per (query, shard) row of the sharded-mAP wire buffer: [histogram: nbits + 2 int32, padded to 8 bytes |
     relevance string: ceil(kin / 64) uint64]."""
@@ -458,6 +548,39 @@ def merge_relbits_map(wire, kin, k, nbits, need_out=None):
                                           _lib.stream_ptr())
             _lib.check(rc, "wv_merge_relbits_map")
     return ap, nrel
+
+
+MERGE_LDS_LIMIT = 60 * 1024  # WV_MERGE_RELBITS_LDS_LIMIT: dynamic LDS above which wv_merge_relbits_map_ks answers WV_ENOTSUP
+
+
+def merge_relbits_lds_bytes(G, k, nbits):
+    """LDS wv_merge_relbits_map_ks needs for G shards and a largest cut-off k, as the library itself computes it
+    (wv_merge_relbits_map_ks_lds_bytes; no GPU needed).  Callers that must decide a fallback before any rank exchanges
+    anything (parallel.sharded_hamming_map_at_k) hold it against MERGE_LDS_LIMIT."""
+    return int(_lib.load().wv_merge_relbits_map_ks_lds_bytes(int(G), int(k), int(nbits)))
+
+
+def merge_relbits_map_ks(wire, kin, ks, nbits, need_out=None):
+    """merge_relbits_map for several cut-offs from ONE merged string (assembled for max(ks); need_out refers to max(ks))
+    -> (ap float32 [Q, len(ks)], nrel int32 [Q, len(ks)]), or None when that string does not fit the kernel's LDS."""
+    lib = _lib.require_gpu()
+    G, Q, ld = wire.shape
+    if wire.dtype != torch.int64 or ld != relbits_wire_words(kin, nbits):
+        raise ValueError("merge_relbits_map_ks: expected the int64 [G, Q, relbits_wire_words(kin, nbits)] wire buffer")
+    uniq, c_ks, cols = _cutoffs(ks, "merge_relbits_map_ks")
+    wire = wire.contiguous()
+    ap = torch.empty((Q, len(uniq)), dtype=torch.float32, device=wire.device)
+    nrel = torch.empty((Q, len(uniq)), dtype=torch.int32, device=wire.device)
+    if Q:
+        hist_words = (nbits + 3) // 2
+        with torch.cuda.device(wire.device):
+            rc = lib.wv_merge_relbits_map_ks(wire.data_ptr() + 8 * hist_words, ld, wire.data_ptr(), 2 * ld, G, Q, kin, c_ks, len(uniq),
+                                             nbits, _lib.ptr(ap), _lib.ptr(nrel), _lib.ptr(need_out) if need_out is not None else None,
+                                             _lib.stream_ptr())
+            if rc == _lib.WV_ENOTSUP:
+                return None
+            _lib.check(rc, "wv_merge_relbits_map_ks")
+    return _columns(ap, nrel, cols)
 
 
 def wire_histograms(wire, nbits):

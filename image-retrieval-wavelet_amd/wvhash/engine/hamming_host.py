@@ -10,6 +10,7 @@ import torch
 from .. import _lib
 
 SHARD_ROWS_MAX = 1 << 62        # no windowed-kernel limit on the host
+MAX_CUTOFFS = 16                # WV_MAX_CUTOFFS
 
 
 def _words(nbits):
@@ -114,6 +115,31 @@ def map_at_k(idx, qlab_packed, dblab_packed, k=None):
     return ap, nrel
 
 
+def map_at_ks(idx, qlab_packed, dblab_packed, ks):
+    """map_at_k for several cut-offs from one walk -> (ap float32 [Q, len(ks)], nrel int32 [Q, len(ks)])."""
+    lib = _lib.load()
+    idx = _host(idx, torch.int32) if idx.stride(-1) != 1 or idx.dtype != torch.int32 or idx.is_cuda else idx
+    qlab_packed, dblab_packed = _host(qlab_packed), _host(dblab_packed)
+    Q, kfull = idx.shape
+    ks = [int(k) for k in ks]
+    uniq = sorted(set(ks))
+    if not uniq or len(uniq) > MAX_CUTOFFS:
+        raise ValueError(f"map_at_ks: {len(uniq)} different cut-offs (1..{MAX_CUTOFFS} per call)")
+    if uniq[0] < 1 or uniq[-1] > kfull:
+        raise ValueError(f"map_at_ks: cut-offs {uniq[0]}..{uniq[-1]} outside the lists' length {kfull}")
+    lw = qlab_packed.shape[1]
+    if dblab_packed.shape[1] != lw:
+        raise ValueError("map_at_ks: label widths differ")
+    ap = torch.empty((Q, len(uniq)), dtype=torch.float32)
+    nrel = torch.empty((Q, len(uniq)), dtype=torch.int32)
+    if Q:
+        _lib.check(lib.wv_map_at_ks_cpu(_lib.ptr(idx), idx.stride(0), Q, (ctypes.c_int * len(uniq))(*uniq), len(uniq),
+                                        _lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw, _lib.ptr(ap), _lib.ptr(nrel)),
+                   "wv_map_at_ks_cpu")
+    sel = torch.tensor([uniq.index(k) for k in ks], dtype=torch.long)
+    return ap.index_select(1, sel), nrel.index_select(1, sel)
+
+
 def hit_prefix(idx, qlab_packed, dblab_packed):
     lib = _lib.load()
     idx = _host(idx, torch.int32)
@@ -141,3 +167,7 @@ class PreparedDB:
 
 def hamming_map_at_k(*args, **kwargs):
     return None                   # ranking and AP are two calls on the host (same numbers)
+
+
+def hamming_map_at_ks(*args, **kwargs):
+    return None

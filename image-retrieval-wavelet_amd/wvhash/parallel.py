@@ -255,10 +255,20 @@ def sharded_hamming_map_at_k(q_local, qlab_local, db_shard, labels_shard, nbits,
     in two); db_shard PreparedDB and labels_shard PreparedLabels of this rank's rows; send_hint: the prefix length (learn it
     from an earlier batch, check the returned `need` with exchange_ok), or None for a one-off call that sizes the exchange
     exactly first: a histogram pass per shard, one SUM and one MAX all-reduce and one host read (what evaluate_sharded
-    uses) -- `need` is then <= the prefix that was sent by construction."""
+    uses) -- `need` is then <= the prefix that was sent by construction.
+    k may be a sequence of cut-offs (any order): ap and nrel are then [Ql, len(k)], column i what the call returns for k[i];
+    still one all_gather and one all_to_all, their length from max(k), and `need` refers to max(k)."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
+    ks = [int(x) for x in k] if isinstance(k, (tuple, list)) else None    # several cut-offs: ap / nrel are [Ql, len(k)]
+    if ks is not None:
+        if not ks:
+            raise ValueError("sharded_hamming_map_at_k: empty k sequence")
+        k = max(ks)                                      # ranking, prefix length and exchange are sized by the largest
     if world == 1:
-        out = H.hamming_map_at_k(q_local, db_shard, labels_shard, qlab_local, nbits, k)
+        if ks is not None:
+            out = H.hamming_map_at_ks(q_local, db_shard, labels_shard, qlab_local, nbits, ks)
+        else:
+            out = H.hamming_map_at_k(q_local, db_shard, labels_shard, qlab_local, nbits, k)
         return None if out is None else (out[0], out[1], None)
     rank = dist.get_rank(group)
     Ql, words = q_local.shape
@@ -267,6 +277,8 @@ def sharded_hamming_map_at_k(q_local, qlab_local, db_shard, labels_shard, nbits,
     lwords = qlab_local.shape[1]                         # 1 label word (<= 64 classes) or 2 (COCO's 80, NUS-WIDE's 81)
     if per > H.SHARD_ROWS_MAX or min(k, per) > H.RANK_K_MAX or lwords not in (1, 2) or nbits > 128:
         return None                                      # decided from values every rank shares: no rank goes another way
+    if ks is not None and (len(set(ks)) > H.MAX_CUTOFFS or H.merge_relbits_lds_bytes(world, k, nbits) > H.MERGE_LDS_LIMIT):
+        return None                                      # likewise: world, max(k) and nbits are the same on every rank
     dev = q_local.device
     both = torch.cat([q_local, qlab_local], dim=1).contiguous()           # codes | label words: one collective
     both_all = torch.empty((world * Ql, words + lwords), dtype=both.dtype, device=dev)
@@ -294,6 +306,11 @@ def sharded_hamming_map_at_k(q_local, qlab_local, db_shard, labels_shard, nbits,
     wire_r = torch.empty_like(wire)
     _all_to_all(wire_r, wire, group)                      # histogram + relevance string of a (query, shard) side by side
     need = torch.zeros(1, dtype=torch.int32, device=dev)
+    if ks is not None:
+        got = H.merge_relbits_map_ks(wire_r.view(world, Ql, -1), send, ks, nbits, need_out=need)
+        if got is None:
+            raise RuntimeError("sharded_hamming_map_at_k: the merged string does not fit although the shared checks passed")
+        return got[0], got[1], need
     ap, nrel = H.merge_relbits_map(wire_r.view(world, Ql, -1), send, k, nbits, need_out=need)
     return ap, nrel, need
 

@@ -49,7 +49,9 @@ const char *wv_last_error(void);
  * wv_band_attn_pool_cpu, wv_hash_tail_cpu; 4 added the host twins of the ranking side (wv_pack_bits_cpu ... wv_hit_prefix_cpu); 2 added wv_head_params.q_proj, the host twins, wv_swt2d_forward_ex, the two-step shard entry
  * points and wv_map_at_k_ld; 3 added wv_head_params.prepared / wv_band_attn_prepare (one-launch head front), the ranking + AP
  * entry points (wv_hamming_map_at_k, wv_rank_labels_prepare), wv_hamming_shard_prefix / wv_topk_merge_cum_need and the
- * relevance-string pair of the sharded mAP (wv_hamming_shard_relbits, wv_merge_relbits_map).  A struct gaining a field bumps it. */
+ * relevance-string pair of the sharded mAP (wv_hamming_shard_relbits, wv_merge_relbits_map).  The multi-cut-off entry points
+ * (wv_hamming_map_at_ks, wv_merge_relbits_map_ks[_lds_bytes], wv_map_at_ks, wv_map_at_ks_cpu) were added under 5 as well: new symbols only.
+ * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------
@@ -302,6 +304,35 @@ int wv_map_at_k(const int32_t *idx, int Q, int k, const uint64_t *qlab, const ui
  * largest k -- evaluate_multi_k (main/engine/evaluate.py:172-245) re-ranks once per k in the reference. */
 int wv_map_at_k_ld(const int32_t *idx, int64_t ld, int Q, int k, const uint64_t *qlab, const uint64_t *dblab,
                    int lwords, float *ap, int32_t *nrel, void *stream);
+
+/* Average precision at SEVERAL cut-offs from one pass (evaluate_all_checkpoints.py --k 5000,117218; evaluate_multi_k's k_list).
+ * The list for the largest cut-off has the list for every smaller one as a prefix (the order distance, then row is total) and a
+ * list position's thread does not depend on k, so AP@ks[i] is a snapshot of one walk to ks[nk - 1]: column i has the bits the
+ * single-k entry point of the same name returns for k = ks[i] (whenever both run the same kernel variant: always for
+ * wv_merge_relbits_map_ks, wv_map_at_ks and the 256-thread ranking kernel; one wave per query sums in its own order).
+ *   ks    HOST pointer, nk in [1, WV_MAX_CUTOFFS], strictly ascending, 1 <= ks[0], ks[nk - 1] <= N (lists: <= ld); anything
+ *         else is WV_EINVAL, answered on the host before any launch
+ *   ap    float32 [Q][nk], nrel int32 [Q][nk] or NULL; nothing else is written
+ * wv_hamming_map_at_ks    <- wv_hamming_map_at_k: list, window, LDS and relevance bitmap sized by ks[nk - 1]; no list is written
+ * wv_merge_relbits_map_ks <- wv_merge_relbits_map: the merged string is assembled for ks[nk - 1], need_out refers to it too;
+ *                            the shards send wv_hamming_shard_relbits' string of that prefix
+ * wv_map_at_ks            <- wv_map_at_k_ld: the list is read and the labels are gathered once for all cut-offs
+ * wv_map_at_ks_cpu        host twin of wv_map_at_ks (HOST pointers), same summation order, bit for bit
+ * WV_ENOTSUP when the largest cut-off is outside the fused kernel (wv_hamming_map_at_ks: as wv_hamming_map_at_k) or its merged
+ * string does not fit LDS (wv_merge_relbits_map_ks): the caller then runs wv_hamming_topk + wv_map_at_ks. */
+#define WV_MAX_CUTOFFS 16
+/* dynamic LDS wv_merge_relbits_map_ks needs for G shards and a largest cut-off kmax (0 for arguments it refuses); the call
+ * answers WV_ENOTSUP above WV_MERGE_RELBITS_LDS_LIMIT.  For callers that must know before they exchange anything. */
+#define WV_MERGE_RELBITS_LDS_LIMIT (60 * 1024)
+size_t wv_merge_relbits_map_ks_lds_bytes(int G, int kmax, int nbits);
+int wv_hamming_map_at_ks(const uint64_t *q, const void *prepared, const void *prepared_labels, const uint64_t *qlab, int lwords,
+                         int Q, int64_t N, int nbits, const int *ks, int nk, float *ap, int32_t *nrel, void *stream);
+int wv_merge_relbits_map_ks(const uint64_t *relbits, int64_t relbits_ld, const uint32_t *cum, int64_t cum_ld, int G, int Q, int kin,
+                            const int *ks, int nk, int nbits, float *ap, int32_t *nrel, int32_t *need_out, void *stream);
+int wv_map_at_ks(const int32_t *idx, int64_t ld, int Q, const int *ks, int nk, const uint64_t *qlab, const uint64_t *dblab,
+                 int lwords, float *ap, int32_t *nrel, void *stream);
+int wv_map_at_ks_cpu(const int32_t *idx, int64_t ld, int Q, const int *ks, int nk, const uint64_t *qlab, const uint64_t *dblab,
+                     int lwords, float *ap, int32_t *nrel);
 
 /* Running hit counts along each ranked list: hits[q][p] = relevant entries among idx[q][0..p] (uint32 [Q][k]).
  * The ratios of these counts are the secondary retrieval diagnostics of accuracy_calculator.py:131-181
