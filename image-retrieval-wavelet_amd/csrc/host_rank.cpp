@@ -248,3 +248,31 @@ extern "C" int wv_hit_prefix_cpu(const int32_t *idx, int Q, int k, const uint64_
     }
     return WV_OK;
 }
+
+// Twin of wv_hamming_radius_hist, any N: per query the cumulative distance histograms of all rows and of the rows that share
+// a label bit with it (cum[b], cumrel[b]: distance < b; nbits + 2 entries each).  Integers: identical to the kernel's.
+extern "C" int wv_hamming_radius_hist_cpu(const uint64_t *q, const uint64_t *db, const uint64_t *qlab, const uint64_t *dblab, int lwords,
+                                          int Q, int64_t N, int nbits, uint32_t *cum, uint32_t *cumrel)
+{
+    HR_REQUIRE(q && db && qlab && dblab && cum && cumrel, "hamming_radius_hist_cpu: null buffer");
+    HR_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_radius_hist_cpu: nbits=%d (supported: 1..128)", nbits);
+    HR_REQUIRE(lwords == 1 || lwords == 2, "hamming_radius_hist_cpu: lwords=%d (supported: 1, 2)", lwords);
+    HR_REQUIRE(Q >= 0 && N >= 0 && N <= 0xffffffffLL, "hamming_radius_hist_cpu: bad shape Q=%d N=%lld", Q, (long long)N);
+    const int words = (nbits + 63) / 64, ld = nbits + 2;
+    std::vector<uint8_t> d((size_t)N);
+    for (int qi = 0; qi < Q; ++qi) {
+        const uint64_t *ql = qlab + (int64_t)qi * lwords;
+        uint32_t *ca = cum + (int64_t)qi * ld, *cr = cumrel + (int64_t)qi * ld;
+        dist_row(q + (int64_t)qi * words, db, N, words, d.data());
+        for (int b = 0; b < ld; ++b) ca[b] = cr[b] = 0;
+        for (int64_t n = 0; n < N; ++n) {                                   // counts of bin d at [d + 1] ...
+            ca[d[n] + 1]++;
+            if (relevant(ql, dblab + n * lwords, lwords)) cr[d[n] + 1]++;
+        }
+        for (int b = 1; b < ld; ++b) {                                      // ... summed up: rows with distance < b
+            ca[b] += ca[b - 1];
+            cr[b] += cr[b - 1];
+        }
+    }
+    return WV_OK;
+}

@@ -28,6 +28,7 @@ enum class RankMode {
     hist,        // histograms only (k = 0): windowed kernel only
     ap,          // average precision of the list, never written (wv_hamming_map_at_k): windowed kernel only
     relbits,     // relevance string of the list (wv_hamming_shard_relbits): windowed kernel only
+    radius,      // histograms of all rows and of the relevant rows (wv_hamming_radius_hist): 256-thread windowed kernel only
 };
 
 // a database image of the windowed kernel exists for databases (shards) of at most this many rows: one wave per query
@@ -60,6 +61,16 @@ inline size_t window_lds_bytes_per_query(int tpq, int k, int bm_words = 0)
     b = (b + 15) / 16 * 16;
     const size_t hist = (size_t)(kMaxBins + 1) * 17 * 4;         // histogram-only mode: [bins + 1][16] dwords + totals
     return b > hist ? b : (hist + 15) / 16 * 16;
+}
+
+// LDS of the radius-histogram kernel (k_rank_radius, rank2.hip): count table [kMaxBins + 1][16] dwords (a dword = the cell of
+// 16 threads: all rows in the low half, relevant rows in the high half), the two rows of totals, and the relevance bitmap
+// over every ITEM number of the 256 threads (8 C words: padding items index it too) + the word a 64-bit read may touch
+constexpr int rank_radius_bitmap_words(int C) { return 8 * C + 1; }
+inline size_t radius_lds_bytes(int C)
+{
+    const size_t b = (size_t)(kMaxBins + 1) * 16 * 4 + (size_t)2 * (kMaxBins + 1) * 4 + (size_t)rank_radius_bitmap_words(C) * 4;
+    return (b + 15) / 16 * 16;
 }
 
 // LDS of the column kernel: hist[nbins][256] (u16 pairs when N < 65536), tot[kMaxBins], base[kMaxBins + 1], misc[4]
@@ -104,11 +115,14 @@ inline RankPlan rank_plan(int Q, int64_t N, int nbits, int k, RankMode mode)
     }
     // the AP walk keeps 32 list positions per thread (N <= kImg64MaxRows here: the 256-thread image exists and fits)
     if (fused && kern == RankKernel::window64 && k > 32 * 64) kern = RankKernel::window256;
+    // the radius histograms exist for 256 threads per query only (N <= kImg256MaxRows here: that image exists)
+    if (mode == RankMode::radius) kern = RankKernel::window256;
     RankPlan p{kern, 0, 0, 0, nullptr, ""};
     const int tpq = rank_threads_per_query(kern);
     p.C = (int)ceil_div(N, tpq);
     p.NC = p.C <= 16 ? 4 : (p.C <= 32 ? 8 : (p.C <= 64 ? 16 : (p.C <= 100 ? 25 : 32)));
     p.lds = window_lds_bytes_per_query(tpq, k, fused ? rank2_bitmap_words(N) : 0) * (kTopkThreads / tpq);
+    if (mode == RankMode::radius) p.lds = radius_lds_bytes(p.C);
     if (fused && p.lds > kRankLdsLimit)
         return {RankKernel::none, 0, 0, 0, "do not fit the fused kernel's LDS (list + relevance bitmap)", instead};
     return p;
@@ -174,5 +188,10 @@ struct Rank2Ap {
 int rank2_launch(const RankPlan &plan, const uint64_t *q, const void *img, int32_t *idx, uint16_t *rows16, uint8_t *dist,
                  uint32_t *cum, int Q, int64_t N, int nbits, int k, int64_t idx_offset, hipStream_t st,
                  const Rank2Ap *apx = nullptr, const ApCuts *cuts = nullptr);
+
+// Launches the radius-histogram kernel of `plan` (RankMode::radius: window256) on its image: cum / cumrel uint32 [Q][nbits + 2],
+// rows (cumrel: rows sharing a label bit with the query) with distance < b.  apx: cls, qlab, lwords are read.
+int rank2_radius_launch(const RankPlan &plan, const uint64_t *q, const void *img, const Rank2Ap &apx, uint32_t *cum, uint32_t *cumrel,
+                        int Q, int64_t N, int nbits, hipStream_t st);
 
 }  // namespace wv

@@ -792,6 +792,102 @@ __global__ __launch_bounds__(256, rank2_cuts_min_waves(NC)) void k_rank_window_c
                            apx.ap + (int64_t)qi * cuts.n, apx.nrel ? apx.nrel + (int64_t)qi * cuts.n : nullptr, nullptr, &cuts);
 }
 
+// Precision / recall by Hamming radius (wv_hamming_radius_hist): per query the cumulative distance histogram of ALL rows and
+// of the rows that share a label bit with the query -- what a hash-table lookup within radius r returns and how much of it
+// is relevant.  The distance pass and the relevance bitmap are those of the fused AP kernel, the count pass is
+// rank2_hist_only's with the relevance bit riding along: a table dword is the cell of 16 threads (bin, t & 15), its low half
+// counts every item, its high half the relevant ones (16 threads x <= 128 items = 2048 per half: no carry), so an item
+// costs ONE LDS add whatever its relevance.  Its own kernel: the ranking kernels keep their code and registers.
+// LDS (radius_lds_bytes, rank.hpp): table [kMaxBins + 1][16] dwords | totals of all rows, of the relevant rows | bitmap.
+// The bitmap is indexed by ITEM number, which runs to 256 C - 1 >= N: it covers 8 C words (+ 1: the 64-bit window read
+// below), the words behind the rows' are zero.  (Padding items also carry distance 255, i.e. the dummy row.)
+template <int TPQ, int NC>
+__device__ __forceinline__ void rank2_radius_hist(const uint32_t (&dc)[NC], int C, int nbins, const uint32_t *bitmap, uint32_t *table,
+                                                  uint32_t *tot, uint32_t *__restrict__ cum_out, uint32_t *__restrict__ cumrel_out, int t)
+{
+    const int first = t * C;
+    char *cell = reinterpret_cast<char *>(table) + (uint32_t)(t & 15) * 4u;
+#pragma unroll
+    for (int bw = 0; bw < NC; bw += 8) {                          // 32 items: one 64-bit window of the bitmap
+        if (bw * 4 < C) {                                         // uniform
+            const int p = first + bw * 4;                         // <= 256 C - 1: word (p >> 5) + 1 <= 8 C
+            const uint32_t lo = bitmap[p >> 5], hi = bitmap[(p >> 5) + 1];
+            const uint32_t rel32 = (uint32_t)((((uint64_t)hi << 32) | lo) >> (p & 31));   // bit i = item p + i
+#pragma unroll
+            for (int j = 0; j < 32; ++j) {
+                if (bw + (j >> 2) < NC) {
+                    const uint32_t d = (dc[bw + (j >> 2)] >> (8 * (j & 3))) & 0xffu;
+                    const uint32_t b = min(d, (uint32_t)nbins);   // 255 (no item) -> the dummy row
+                    const uint32_t inc = 1u + (((rel32 >> j) & 1u) << 16);
+                    __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(cell + b * 64), inc, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    group_sync<TPQ>();
+    for (int b = t; b < nbins; b += TPQ) {                        // thread b sums row b
+        const uint4 *row = reinterpret_cast<const uint4 *>(table + b * 16);
+        uint32_t all = 0, rel = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint4 v = row[i];
+            all += (v.x & 0xffffu) + (v.y & 0xffffu) + (v.z & 0xffffu) + (v.w & 0xffffu);
+            rel += (v.x >> 16) + (v.y >> 16) + (v.z >> 16) + (v.w >> 16);
+        }
+        tot[b] = all;
+        tot[kMaxBins + 1 + b] = rel;
+    }
+    group_sync<TPQ>();
+    if (t < 128) {                                                // wave 0: all rows, wave 1: relevant rows; 3 bins per lane >= 130
+        const int which = __builtin_amdgcn_readfirstlane(t >> 6), b0 = 3 * (t & 63);
+        const uint32_t *src = tot + which * (kMaxBins + 1);
+        uint32_t *dst = which ? cumrel_out : cum_out;
+        const uint32_t t0 = b0 < nbins ? src[b0] : 0u, t1 = b0 + 1 < nbins ? src[b0 + 1] : 0u, t2 = b0 + 2 < nbins ? src[b0 + 2] : 0u;
+        const uint32_t incl = wave_incl_scan_u32(t0 + t1 + t2), excl = incl - (t0 + t1 + t2);
+        if (b0 <= nbins) dst[b0] = excl;
+        if (b0 + 1 <= nbins) dst[b0 + 1] = excl + t0;
+        if (b0 + 2 <= nbins) dst[b0 + 2] = excl + t0 + t1;
+    }
+}
+
+template <int WORDS, int TPQ, int NC>
+__global__ __launch_bounds__(256, rank2_min_waves(NC)) void k_rank_radius(const uint64_t *__restrict__ q, const uint4 *__restrict__ img,
+                                                                          int Q, int64_t N, int C, int nbins, Rank2Ap apx,
+                                                                          uint32_t *__restrict__ cum, uint32_t *__restrict__ cumrel)
+{
+    static_assert(TPQ == 256, "the radius histograms are built for 256 threads per query (rank_plan never picks another)");
+    extern __shared__ uint4 lds4[];
+    const int t = threadIdx.x;
+    const int qi = blockIdx.x;                                   // one query per workgroup
+    if (qi >= Q) return;
+    uint32_t *table = reinterpret_cast<uint32_t *>(lds4);        // [kMaxBins + 1][16]
+    uint32_t *tot = table + (kMaxBins + 1) * 16;                 // [2][kMaxBins + 1]
+    uint32_t *bitmap = tot + 2 * (kMaxBins + 1);                 // [rank_radius_bitmap_words(C)]
+    QCode<WORDS> qc;
+#pragma unroll
+    for (int w = 0; w < WORDS; ++w) {
+        const uint64_t v = q[(int64_t)qi * WORDS + w];
+        qc.w[w] = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    }
+    const int nw = rank2_bitmap_words(N);                        // bitmap words that hold rows: <= 8 C
+    for (int i = t; i < (nbins + 1) * 16; i += TPQ) table[i] = 0;              // LDS stores in the shadow of the image loads
+    for (int w = nw + t; w < rank_radius_bitmap_words(C); w += TPQ) bitmap[w] = 0;
+    uint32_t dc[NC], dmin;
+    rank2_distances<WORDS, TPQ, NC>(img, qc, N, C, t, dc, dmin);
+    (void)dmin;
+    const uint64_t lw = apx.qlab[(int64_t)qi * apx.lwords], lw2 = apx.lwords > 1 ? apx.qlab[(int64_t)qi * apx.lwords + 1] : 0;
+    const uint64_t ql = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lw >> 32)) << 32) |
+                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lw);
+    const uint64_t ql2 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lw2 >> 32)) << 32) |
+                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lw2);
+    rank2_relevance_bitmap<TPQ>(apx.cls, ql, ql2, nw, t, bitmap);   // a query without classes: all words zero
+    group_sync<TPQ>();                                           // table zero, bitmap complete
+    rank2_radius_hist<TPQ, NC>(dc, C, nbins, bitmap, table, tot, cum + (int64_t)qi * (nbins + 1), cumrel + (int64_t)qi * (nbins + 1), t);
+}
+
 // ------------------------------------------------------------------------------------------ host side
 int rank2_prepare(const uint64_t *db, void *img, int64_t N, int words, RankKernel kern, hipStream_t st)
 {
@@ -873,6 +969,37 @@ int rank2_launch(const RankPlan &plan, const uint64_t *q, const void *img, int32
     const bool wave = plan.kernel == RankKernel::window64;
     if (nbits <= 64) return wave ? launch_window_nc<1, 64>(plan, a) : launch_window_nc<1, 256>(plan, a);
     return wave ? launch_window_nc<2, 64>(plan, a) : launch_window_nc<2, 256>(plan, a);
+}
+
+namespace {
+template <int WORDS, int NC>
+int launch_radius(const RankPlan &plan, const uint64_t *q, const void *img, const Rank2Ap &apx, uint32_t *cum, uint32_t *cumrel, int Q,
+                  int64_t N, int nbins, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_rank_radius<WORDS, 256, NC>), dim3((unsigned)Q), dim3(256), plan.lds, st, q, (const uint4 *)img, Q, N, plan.C,
+                       nbins, apx, cum, cumrel);
+    WV_CHECK_LAUNCH("k_rank_radius");
+    return WV_OK;
+}
+
+template <int WORDS>
+int launch_radius_nc(const RankPlan &plan, const uint64_t *q, const void *img, const Rank2Ap &apx, uint32_t *cum, uint32_t *cumrel, int Q,
+                     int64_t N, int nbins, hipStream_t st)
+{
+    if (plan.NC == 4) return launch_radius<WORDS, 4>(plan, q, img, apx, cum, cumrel, Q, N, nbins, st);
+    if (plan.NC == 8) return launch_radius<WORDS, 8>(plan, q, img, apx, cum, cumrel, Q, N, nbins, st);
+    if (plan.NC == 16) return launch_radius<WORDS, 16>(plan, q, img, apx, cum, cumrel, Q, N, nbins, st);
+    if (plan.NC == 25) return launch_radius<WORDS, 25>(plan, q, img, apx, cum, cumrel, Q, N, nbins, st);
+    return launch_radius<WORDS, 32>(plan, q, img, apx, cum, cumrel, Q, N, nbins, st);
+}
+}  // namespace
+
+int rank2_radius_launch(const RankPlan &plan, const uint64_t *q, const void *img, const Rank2Ap &apx, uint32_t *cum, uint32_t *cumrel,
+                        int Q, int64_t N, int nbits, hipStream_t st)
+{
+    if (plan.kernel != RankKernel::window256) WV_FAIL(WV_EINVAL, "rank2_radius_launch: the plan names no 256-thread kernel");
+    if (nbits <= 64) return launch_radius_nc<1>(plan, q, img, apx, cum, cumrel, Q, N, nbits + 1, st);
+    return launch_radius_nc<2>(plan, q, img, apx, cum, cumrel, Q, N, nbits + 1, st);
 }
 
 }  // namespace wv

@@ -1095,6 +1095,21 @@ extern "C" int wv_hamming_map_at_k(const uint64_t *q, const void *prepared, cons
     return fused_call("hamming_map_at_k", RankMode::ap, q, prepared, apx, nullptr, Q, N, nbits, k, stream);
 }
 
+// ---------------------------------------------------------------------------------- precision / recall by Hamming radius
+extern "C" int wv_hamming_radius_hist(const uint64_t *q, const void *prepared, const void *prepared_labels, const uint64_t *qlab,
+                                      int lwords, int Q, int64_t N, int nbits, uint32_t *cum, uint32_t *cumrel, void *stream)
+{
+    WV_REQUIRE(lwords >= 1, "hamming_radius_hist: lwords=%d", lwords);
+    if (lwords > 2) WV_FAIL(WV_ENOTSUP, "hamming_radius_hist: %d label words (more than 128 classes)", lwords);
+    if (int rc = validate_rank_shape("hamming_radius_hist", q && prepared && prepared_labels && qlab && cum && cumrel, Q, N, nbits)) return rc;
+    if (Q == 0) return WV_OK;
+    const RankPlan plan = rank_plan(Q, N, nbits, 0, RankMode::radius);
+    if (plan.kernel == RankKernel::none) return rank_refuse("hamming_radius_hist", plan, N, 0);
+    const Rank2Ap apx{(const uint32_t *)prepared_labels, qlab, lwords, nullptr, nullptr, nullptr, 0, 0};
+    return rank2_radius_launch(plan, q, blob_image(prepared, N, (nbits + 63) / 64, plan.kernel), apx, cum, cumrel, Q, N, nbits,
+                               (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------- sharded search, two steps
 // 16-bit lists and / or histograms of one shard (RankMode::rows16, hist): windowed kernel, or WV_ENOTSUP
 static int shard_call(const char *what, RankMode mode, const uint64_t *q, const uint64_t *db, const void *prepared, uint16_t *rows16,

@@ -12,6 +12,8 @@ of the same entry points (csrc/host_rank.cpp; same integers, same AP bits) -- an
   calculate_bit_balance / calculate_worst_bit_balance -> wv_bit_counts   (:188-200)
   calculate_map           -> get_knn + wv_map_at_k  (:156-167, torchmetrics RetrievalMAP)
   calculate_rpr / calculate_pr / calculate_pr_rc / calculate_pr_rc_hashing -> wv_hit_prefix (:131-181, :235-273)
+  calculate_precision_hamming_radius / calculate_pr_curve_hamming (opt-in: computed only when named in `include`)
+                          -> wv_hamming_radius_hist (DSCH/_utils.py:469-493, 577-594: precision / recall by Hamming radius)
 Ranking ties are broken by ascending reference index (see engine/get_knn.py).
 """
 import logging
@@ -21,12 +23,14 @@ import torch
 from .. import _lib
 from . import hamming as H
 from . import hamming_host as HH
+from . import radius_metrics
 from .get_knn import get_knn, _to_gpu, _is_pm1
 
 LOGGER = logging.getLogger("RETRIEVAL")
 
 _RECALL_KS = (1, 2, 4, 8, 10, 16, 20, 30, 32, 100, 1000)
 _NOT_METRICS = ("calculate_maphashing_at",)     # calculate_* methods that take cut-offs of their own: not get_accuracy columns
+_OPT_IN = ("precision_hamming_radius", "pr_curve_hamming")   # computed only when `include` names them (construction or get_accuracy)
 
 
 class RankCache(object):
@@ -93,6 +97,12 @@ class RankCache(object):
                     done[k] = ap[:, i]
         return done[topk]
 
+    def radius_tables(self, query, query_labels, reference, reference_labels):
+        """(cum, cumrel) of hamming_radius_hist for the pair, from the cached packed codes / labels and prepared database."""
+        qlp, rlp = self.packed_labels(query_labels, reference_labels)
+        prepared = self._prepared(reference, rlp)
+        return H.hamming_radius_hist(self.packed_codes(query), prepared[0], prepared[1], qlp, reference.shape[1])
+
     def _prepared(self, reference, rlp):
         """(PreparedDB, PreparedLabels) of the reference set, laid out once per embedding pair."""
         key = (self._key(reference), rlp.data_ptr())
@@ -126,6 +136,8 @@ class CustomCalculator(object):
         self.num_top_k = k
         self.with_faiss = with_faiss
         self.pr_rc_path, self.last_pr_rc = kwargs.pop("pr_rc_path", "pr_rc.csv"), None
+        self.hamming_radius = kwargs.pop("hamming_radius", 2)
+        self.pr_curve_hamming_path, self.last_pr_curve_hamming = kwargs.pop("pr_curve_hamming_path", None), None
         self.distance_metric = distance_metric
         self.rank_cache = kwargs.pop("rank_cache", None)          # shared by the calculators of evaluate_multi_k
         # device=None / 'cuda': the ranking stage lives on the GPU.  device='cpu' (what the reference pins its calculator
@@ -139,7 +151,11 @@ class CustomCalculator(object):
         self.original_function_dict = {name[len("calculate_"):]: getattr(self, name)
                                        for name in dir(self) if name.startswith("calculate_") and name not in _NOT_METRICS}
         self.check_primary_metrics(include, exclude)
+        every = self.original_function_dict
+        self._opted_in = tuple(m for m in _OPT_IN if m in include and m not in exclude)
         self.original_function_dict = self.get_function_dict(include, exclude)
+        # the opt-in metrics stay nameable in get_accuracy(include=...); an empty include never selects them
+        self.original_function_dict.update({m: every[m] for m in _OPT_IN if m not in exclude})
         self.curr_function_dict = self.get_function_dict()
         LOGGER.info(f"Initializing CustomCalculator with with_faiss={with_faiss} and "
                     f"distance_metric={distance_metric} device: {'cpu (host twins)' if self.host else 'cuda (HIP)'}")
@@ -167,7 +183,8 @@ class CustomCalculator(object):
 
     def get_function_dict(self, include=(), exclude=()):
         if len(include) == 0:
-            include = list(self.original_function_dict.keys())
+            opted = getattr(self, "_opted_in", ())
+            include = [k for k in self.original_function_dict.keys() if k not in _OPT_IN or k in opted]
         included = [k for k in include if k not in exclude]
         return {k: v for k, v in self.original_function_dict.items() if k in included}
 
@@ -382,6 +399,47 @@ class CustomCalculator(object):
             ok &= not_lone_query_mask
         if bool(ok.any()):
             self._write_pr_rc(*self._curves(hits[ok]))
+        return 0
+
+    # ------------------------------------------------------------------ by Hamming radius (DSCH/_utils.py:469-493, 577-594)
+    def _radius_tables(self, query, query_labels, reference, reference_labels):
+        """(cum, cumrel) int32 [Q, nbits + 2] of the pair (wv_hamming_radius_hist, its host twin with device='cpu')."""
+        query, reference = self._dev(query), self._dev(reference)
+        query_labels, reference_labels = self._dev(query_labels), self._dev(reference_labels)
+        nbits = reference.shape[1]
+        if query.dim() != 2 or query.shape[1] != nbits or nbits > 128 or not (_is_pm1(query) and _is_pm1(reference)):
+            raise ValueError("Hamming-radius metrics need +-1 codes of at most 128 bits "
+                             f"(got {tuple(query.shape)} / {tuple(reference.shape)})")
+        if self.rank_cache is not None:
+            got = self.rank_cache.radius_tables(query, query_labels, reference, reference_labels)
+        else:
+            qlp, rlp = self._packed_labels(query_labels, reference_labels, self.H)
+            got = self.H.hamming_radius_hist(self.H.pack_codes(query), self.H.PreparedDB(self.H.pack_codes(reference), nbits),
+                                             self.H.PreparedLabels(rlp), qlp, nbits)
+        if got is None:
+            raise ValueError("Hamming-radius metrics need labels of at most 128 classes and a database of at most "
+                             f"{64 * H.SHARD_ROWS_MAX} rows on the GPU (got {tuple(reference_labels.shape)} labels, "
+                             f"{reference.shape[0]} rows)")
+        return got
+
+    def calculate_precision_hamming_radius(self, query, query_labels, reference, reference_labels, **kwargs):
+        """Precision of a lookup within Hamming radius `hamming_radius` (constructor kwarg, 2 = P@H<=2), mean over all
+        queries: get_precision_recall_by_Hamming_Radius (DSCH/_utils.py:577-594).  Opt-in: name it in `include`."""
+        if query.shape[0] == 0:
+            raise ZeroDivisionError("calculate_precision_hamming_radius: no queries")
+        tables = self._radius_tables(query, query_labels, reference, reference_labels)
+        return radius_metrics.precision_within_radius(*tables, radius=self.hamming_radius)
+
+    def calculate_pr_curve_hamming(self, query, query_labels, reference, reference_labels, **kwargs):
+        """Precision / recall at every Hamming radius 0..nbits (pr_curve, DSCH/_utils.py:469-493): keeps (P, R) in
+        last_pr_curve_hamming, writes pr_curve_hamming_path (columns radius, pr, rc) when one is set, returns 0 -- the
+        contract of calculate_pr_rc_hashing.  Opt-in: name it in `include`."""
+        P, R = radius_metrics.radius_curves(*self._radius_tables(query, query_labels, reference, reference_labels))
+        self.last_pr_curve_hamming = (P, R)
+        if self.pr_curve_hamming_path:
+            import pandas as pd
+            pd.DataFrame({"radius": list(range(P.shape[0])), "pr": P.cpu().numpy(), "rc": R.cpu().numpy()}) \
+                .to_csv(self.pr_curve_hamming_path, index=False)
         return 0
 
     def _knn_relevance(self, query_labels, knn_labels, k):

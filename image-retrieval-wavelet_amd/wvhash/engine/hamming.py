@@ -424,6 +424,47 @@ def hamming_map_at_k(q_packed, db, labels, qlab_packed, nbits, k):
     return ap, nrel
 
 
+def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
+    """Cumulative distance histograms of every query over ALL rows of `db` and over the rows that share a label with it
+    -> (cum, cumrel) int32 [Q, nbits + 2]: cum[q, b] = rows with distance < b (hamming_hist's numbers), cumrel[q, b] = those
+    of them relevant to query q.  What precision / recall by Hamming radius need (engine/radius_metrics.py); no [Q, N]
+    matrix and no list exists.  The tables add across row shards: more than 32,768 rows (virtual shards) are the sum of the
+    per-part calls.  None where hamming_map_at_k answers None (labels wider than 2 words, nbits > 128).
+    db: PreparedDB; labels: PreparedLabels of the same rows; qlab_packed: int64 [Q, 1 or 2]."""
+    lib = _lib.require_gpu()
+    if not isinstance(db, PreparedDB) or not isinstance(labels, PreparedLabels):
+        raise TypeError("hamming_radius_hist: needs a PreparedDB and PreparedLabels")
+    Q, words = q_packed.shape
+    if words != db.words or labels.N != db.N or words != _words(nbits):
+        raise ValueError("hamming_radius_hist: query / database / label shapes disagree")
+    if not labels.ok or qlab_packed.shape[1] != labels.words or nbits > 128:
+        return None
+    dev = q_packed.device
+    if db.parts or labels.parts:
+        if not (db.parts and labels.parts) or len(db.parts) != len(labels.parts):
+            return None
+        cum = torch.zeros((Q, nbits + 2), dtype=torch.int32, device=dev)
+        cumrel = torch.zeros_like(cum)
+        for part, lab in zip(db.parts, labels.parts):
+            got = hamming_radius_hist(q_packed, part, lab, qlab_packed, nbits)
+            if got is None:
+                return None
+            cum += got[0]
+            cumrel += got[1]
+        return cum, cumrel
+    cum = torch.empty((Q, nbits + 2), dtype=torch.int32, device=dev)
+    cumrel = torch.empty_like(cum)
+    if Q:
+        with torch.cuda.device(dev):
+            rc = lib.wv_hamming_radius_hist(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
+                                            _lib.ptr(qlab_packed.contiguous()), labels.words, Q, db.N, nbits, _lib.ptr(cum),
+                                            _lib.ptr(cumrel), _lib.stream_ptr())
+            if rc == _lib.WV_ENOTSUP:
+                return None
+            _lib.check(rc, "wv_hamming_radius_hist")
+    return cum, cumrel
+
+
 def _cutoffs(ks, what):
     """The cut-offs of a multi-k call, as they arrive (any order, repeats allowed) -> (sorted unique list, C int array of
     it, column of every requested cut-off in the sorted list)."""

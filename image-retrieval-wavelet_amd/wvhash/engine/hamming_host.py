@@ -165,6 +165,35 @@ class PreparedDB:
         self.parts = None
 
 
+class PreparedLabels:
+    """Nothing to prepare on the host either: keeps the packed label words."""
+
+    def __init__(self, dblab_packed):
+        self.packed = _host(dblab_packed)
+        self.N, self.words = self.packed.shape
+        self.parts, self.ok, self.blob = None, self.words <= 2, None
+
+
+def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
+    """hamming.hamming_radius_hist through the host twin (wv_hamming_radius_hist_cpu), any N -> (cum, cumrel) int32
+    [Q, nbits + 2], the kernel's integers.  db / labels: PreparedDB / PreparedLabels of this module or packed int64 tensors."""
+    lib = _lib.load()
+    q_packed, qlab_packed = _host(q_packed), _host(qlab_packed)
+    dbp = _host(db.packed if isinstance(db, PreparedDB) else db)
+    lab = _host(labels.packed if isinstance(labels, PreparedLabels) else labels)
+    Q, words = q_packed.shape
+    if dbp.shape[1] != words or lab.shape[0] != dbp.shape[0] or words != _words(nbits):
+        raise ValueError("hamming_radius_hist: query / database / label shapes disagree")
+    if lab.shape[1] > 2 or qlab_packed.shape[1] != lab.shape[1] or nbits > 128:
+        return None
+    cum = torch.zeros((Q, nbits + 2), dtype=torch.int32)
+    cumrel = torch.zeros_like(cum)
+    if Q and dbp.shape[0]:                           # an empty shard contributes zeros
+        _lib.check(lib.wv_hamming_radius_hist_cpu(_lib.ptr(q_packed), _lib.ptr(dbp), _lib.ptr(qlab_packed), _lib.ptr(lab), lab.shape[1],
+                                                  Q, dbp.shape[0], nbits, _lib.ptr(cum), _lib.ptr(cumrel)), "wv_hamming_radius_hist_cpu")
+    return cum, cumrel
+
+
 def hamming_map_at_k(*args, **kwargs):
     return None                   # ranking and AP are two calls on the host (same numbers)
 

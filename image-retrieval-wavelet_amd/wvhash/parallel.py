@@ -315,6 +315,39 @@ def sharded_hamming_map_at_k(q_local, qlab_local, db_shard, labels_shard, nbits,
     return ap, nrel, need
 
 
+def sharded_hamming_radius_hist(q_local, qlab_local, db_shard, labels_shard, nbits, group=None):
+    """Radius histograms (H.hamming_radius_hist) of ALL ranks' queries against the row-sharded database, the same on every
+    rank -> (cum, cumrel) int32 [world * Ql, nbits + 2], query rows in rank order.  The tables count disjoint row sets, so
+    the shards' tables simply add: one all_gather (query codes and label words in one buffer), one pass over the shard, ONE
+    SUM all_reduce of both tables -- no prefix negotiation, no merge.  Feed engine.radius_metrics with the result.
+    q_local int64 [Ql, words], qlab_local int64 [Ql, 1 or 2] (every rank the same Ql); db_shard / labels_shard: this rank's
+    rows as PreparedDB / PreparedLabels, or -- host tensors (gloo) -- packed int64 codes and label words, which take the
+    library's host twin.  A shard may be ragged or empty."""
+    from .engine import hamming_host as HH
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    Ql, words = q_local.shape
+    lwords = qlab_local.shape[1]
+    if lwords not in (1, 2) or nbits > 128:
+        raise ValueError(f"sharded_hamming_radius_hist: 1 or 2 label words and nbits <= 128 (got {lwords}, {nbits})")
+    dev = q_local.device
+    both_all = torch.cat([q_local, qlab_local], dim=1).contiguous()          # codes | label words: one collective
+    if world > 1:
+        both = both_all
+        both_all = torch.empty((world * Ql, words + lwords), dtype=both.dtype, device=dev)
+        _all_gather(both_all, both, group)
+    q_all, ql_all = both_all[:, :words].contiguous(), both_all[:, words:].contiguous()
+    tables = torch.zeros((2, world * Ql, nbits + 2), dtype=torch.int32, device=dev)
+    n_local = db_shard.N if hasattr(db_shard, "N") else db_shard.shape[0]
+    if n_local > 0 and Ql > 0:
+        got = (H if dev.type == "cuda" else HH).hamming_radius_hist(q_all, db_shard, labels_shard, ql_all, nbits)
+        if got is None:
+            raise RuntimeError("sharded_hamming_radius_hist: this shard is outside the radius histograms")
+        tables[0], tables[1] = got
+    if world > 1:
+        _all_reduce(tables, dist.ReduceOp.SUM, group)
+    return tables[0], tables[1]
+
+
 def exchange_ok(needs, send_hint, kin):
     """True when every `need` a hinted call returned fits the prefix length that was exchanged (one host read for
     the whole list; call it where the host synchronises anyway)."""

@@ -51,6 +51,7 @@ const char *wv_last_error(void);
  * entry points (wv_hamming_map_at_k, wv_rank_labels_prepare), wv_hamming_shard_prefix / wv_topk_merge_cum_need and the
  * relevance-string pair of the sharded mAP (wv_hamming_shard_relbits, wv_merge_relbits_map).  The multi-cut-off entry points
  * (wv_hamming_map_at_ks, wv_merge_relbits_map_ks[_lds_bytes], wv_map_at_ks, wv_map_at_ks_cpu) were added under 5 as well: new symbols only.
+ * So were the radius histograms (wv_hamming_radius_hist, wv_hamming_radius_hist_cpu): 71 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -283,6 +284,25 @@ int wv_hamming_shard_relbits(const uint64_t *q, const void *prepared, const void
                              int nbits, int k, void *stream);
 int wv_merge_relbits_map(const uint64_t *relbits, int64_t relbits_ld, const uint32_t *cum, int64_t cum_ld, int G, int Q, int kin,
                          int k, int nbits, float *ap, int32_t *nrel, int32_t *need_out, void *stream);
+
+/* Precision and recall by Hamming radius -- what a hash-table lookup within radius r returns -- from ONE pass over the codes,
+ * without a [Q][N] distance or relevance matrix and without lists.  Two integer tables per query, uint32 [Q][nbits + 2] each:
+ *   cum[q][b]     rows with distance < b (the numbers wv_hamming_hist returns; cum[q][nbits + 1] = N)
+ *   cumrel[q][b]  rows with distance < b that share a label bit with the query (label_comparison_fn on multi-hot words;
+ *                 cumrel[q][nbits + 1] = all relevant rows; all zero for a query without classes)
+ * Within radius r a query finds cum[q][r + 1] rows, cumrel[q][r + 1] of them relevant: the ingredients of pr_curve
+ * (precision and recall at every radius 0..nbits, DSCH/_utils.py:469-493) and of get_precision_recall_by_Hamming_Radius
+ * (P@H<=2, DSCH/_utils.py:577-594); wvhash/engine/radius_metrics.py turns the tables into those numbers.  Both tables ADD
+ * across row shards (counts of disjoint row sets): a database beyond one call's range, or one spread over several GPUs, is
+ * the plain sum of the per-shard tables -- one SUM all-reduce, no merge.
+ *   prepared / prepared_labels  wv_db_prepare's and wv_rank_labels_prepare's blobs, as for wv_hamming_map_at_k
+ *   qlab                        [Q][lwords] label words of the queries, lwords = 1 or 2; nbits <= 128
+ * wv_hamming_radius_hist      WV_ENOTSUP outside the windowed kernel (more than 32,768 rows) and for lwords > 2
+ * wv_hamming_radius_hist_cpu  host twin (HOST pointers, packed codes and label words, any N): the same integers */
+int wv_hamming_radius_hist(const uint64_t *q, const void *prepared, const void *prepared_labels, const uint64_t *qlab, int lwords,
+                           int Q, int64_t N, int nbits, uint32_t *cum, uint32_t *cumrel, void *stream);
+int wv_hamming_radius_hist_cpu(const uint64_t *q, const uint64_t *db, const uint64_t *qlab, const uint64_t *dblab, int lwords, int Q,
+                               int64_t N, int nbits, uint32_t *cum, uint32_t *cumrel);
 
 /* Ranking from a stored distance matrix row (same order as wv_hamming_topk). */
 int wv_rank_from_dist(const uint8_t *dist_matrix, int64_t ld_dist, int Q, int64_t N, int nbits,
