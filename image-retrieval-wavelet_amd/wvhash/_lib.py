@@ -104,6 +104,11 @@ SIGNATURES = {
     "wv_merge_relbits_map_ks_lds_bytes": (_sz, [_i, _i, _i]),
     "wv_map_at_ks": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "wv_map_at_ks_cpu": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "wv_label_overlap_hist": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp]),
+    "wv_label_overlap_hist_cpu": (_i, [_vp, _vp, _i, _i, _i64, _vp]),
+    "wv_ndcg_weights": (_i, [_vp, _i64]),
+    "wv_ndcg_at_ks": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "wv_ndcg_at_ks_cpu": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "wv_topk_merge_cum": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i, _i, _vp]),
     "wv_topk_merge_cum_need": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _vp, _i, _i, _vp, _vp]),
     "wv_hit_prefix": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),

@@ -14,6 +14,7 @@ of the same entry points (csrc/host_rank.cpp; same integers, same AP bits) -- an
   calculate_rpr / calculate_pr / calculate_pr_rc / calculate_pr_rc_hashing -> wv_hit_prefix (:131-181, :235-273)
   calculate_precision_hamming_radius / calculate_pr_curve_hamming (opt-in: computed only when named in `include`)
                           -> wv_hamming_radius_hist (DSCH/_utils.py:469-493, 577-594: precision / recall by Hamming radius)
+  calculate_ndcg_hamming (opt-in likewise) -> wv_label_overlap_hist + wv_ndcg_at_ks (DSCH/_utils.py:551-574: NDCG@ndcg_k)
 Ranking ties are broken by ascending reference index (see engine/get_knn.py).
 """
 import logging
@@ -23,6 +24,7 @@ import torch
 from .. import _lib
 from . import hamming as H
 from . import hamming_host as HH
+from . import ndcg as ndcg_metrics
 from . import radius_metrics
 from .get_knn import get_knn, _to_gpu, _is_pm1
 
@@ -30,7 +32,7 @@ LOGGER = logging.getLogger("RETRIEVAL")
 
 _RECALL_KS = (1, 2, 4, 8, 10, 16, 20, 30, 32, 100, 1000)
 _NOT_METRICS = ("calculate_maphashing_at",)     # calculate_* methods that take cut-offs of their own: not get_accuracy columns
-_OPT_IN = ("precision_hamming_radius", "pr_curve_hamming")   # computed only when `include` names them (construction or get_accuracy)
+_OPT_IN = ("precision_hamming_radius", "pr_curve_hamming", "ndcg_hamming")   # computed only when `include` names them (construction or get_accuracy)
 
 
 class RankCache(object):
@@ -103,6 +105,13 @@ class RankCache(object):
         prepared = self._prepared(reference, rlp)
         return H.hamming_radius_hist(self.packed_codes(query), prepared[0], prepared[1], qlp, reference.shape[1])
 
+    def ndcg_sums(self, query, query_labels, reference, reference_labels, k):
+        """(dcg, idcg) float64 [Q, 1] at cut-off k from the cached packed codes / labels and prepared database."""
+        qlp, rlp = self.packed_labels(query_labels, reference_labels)
+        qp, db, nbits = self.packed_codes(query), self._prepared(reference, rlp)[0], reference.shape[1]
+        return ndcg_metrics.ndcg_sums_packed(H, lambda lo, hi: H.hamming_topk(qp[lo:hi], db, nbits, k, want_dist=False)[0],
+                                             query.shape[0], qlp, rlp, [k])
+
     def _prepared(self, reference, rlp):
         """(PreparedDB, PreparedLabels) of the reference set, laid out once per embedding pair."""
         key = (self._key(reference), rlp.data_ptr())
@@ -137,6 +146,7 @@ class CustomCalculator(object):
         self.with_faiss = with_faiss
         self.pr_rc_path, self.last_pr_rc = kwargs.pop("pr_rc_path", "pr_rc.csv"), None
         self.hamming_radius = kwargs.pop("hamming_radius", 2)
+        self.ndcg_k = kwargs.pop("ndcg_k", 1000)                  # the reference's call: NDCG(qB, rB, qL, rL, what=1, k=1000)
         self.pr_curve_hamming_path, self.last_pr_curve_hamming = kwargs.pop("pr_curve_hamming_path", None), None
         self.distance_metric = distance_metric
         self.rank_cache = kwargs.pop("rank_cache", None)          # shared by the calculators of evaluate_multi_k
@@ -441,6 +451,28 @@ class CustomCalculator(object):
             pd.DataFrame({"radius": list(range(P.shape[0])), "pr": P.cpu().numpy(), "rc": R.cpu().numpy()}) \
                 .to_csv(self.pr_curve_hamming_path, index=False)
         return 0
+
+    # ------------------------------------------------------------------ graded relevance (DSCH/_utils.py:551-574)
+    def calculate_ndcg_hamming(self, query, query_labels, reference, reference_labels, **kwargs):
+        """NDCG@ndcg_k (constructor kwarg, 1000 = the reference's call; < 0 or beyond the reference set: all of it) of the
+        Hamming ranking with graded relevance 2^(shared classes) - 1: what ndcg.NDCG(query, reference, query_labels,
+        reference_labels, what=1, k=ndcg_k) returns for the same tensors.  Opt-in: name it in `include`."""
+        if query.shape[0] == 0:
+            raise ZeroDivisionError("calculate_ndcg_hamming: no queries")
+        query, reference = self._dev(query), self._dev(reference)
+        query_labels, reference_labels = self._dev(query_labels), self._dev(reference_labels)
+        (num_ref, nbits), k = reference.shape, int(self.ndcg_k)
+        k = num_ref if k < 0 or k > num_ref else k
+        if query.dim() != 2 or query.shape[1] != nbits or nbits > 128 or not (_is_pm1(query) and _is_pm1(reference)):
+            raise ValueError(f"ndcg_hamming needs +-1 codes of at most 128 bits (got {tuple(query.shape)} / {tuple(reference.shape)})")
+        if query_labels.dim() != 2 or reference_labels.dim() != 2 or reference_labels.shape[1] > 128 or k < 1:
+            raise ValueError("ndcg_hamming needs multi-hot labels of at most 128 classes and a cut-off >= 1 "
+                             f"(got {tuple(reference_labels.shape)} labels, ndcg_k={self.ndcg_k})")
+        if self.rank_cache is not None:
+            sums = self.rank_cache.ndcg_sums(query, query_labels, reference, reference_labels, k)
+            return ndcg_metrics.ndcg_from_sums(*sums)[0].item()
+        return ndcg_metrics.NDCG(query, reference, query_labels, reference_labels, what=1, k=k,
+                                 device="cpu" if self.host else None)
 
     def _knn_relevance(self, query_labels, knn_labels, k):
         return self.label_comparison_fn(query_labels[:, None], knn_labels[:, :k]) if query_labels.ndim > 1 \

@@ -531,6 +531,73 @@ def hamming_map_at_ks(q_packed, db, labels, qlab_packed, nbits, ks):
     return _columns(ap, nrel, cols)
 
 
+def _label_pair(qlab_packed, dblab_packed, what):
+    lw = qlab_packed.shape[1]
+    if qlab_packed.dim() != 2 or dblab_packed.dim() != 2 or dblab_packed.shape[1] != lw:
+        raise ValueError(f"{what}: label widths differ")
+    if lw not in (1, 2):
+        raise ValueError(f"{what}: {lw} label words (graded overlap takes 1 or 2: up to 128 classes)")
+    return lw
+
+
+def label_overlap_hist(qlab_packed, dblab_packed):
+    """hist int32 [Q, 64 * lwords + 1]: hist[q, r] = database rows that share exactly r classes with query q
+    (wv_label_overlap_hist: one pass over the packed label words, any N; the tables of row shards add up)."""
+    lib = _lib.require_gpu()
+    lw = _label_pair(qlab_packed, dblab_packed, "label_overlap_hist")
+    Q, N = qlab_packed.shape[0], dblab_packed.shape[0]
+    hist = torch.zeros((Q, 64 * lw + 1), dtype=torch.int32, device=qlab_packed.device)
+    if Q and N:                                      # an empty shard contributes zeros
+        with torch.cuda.device(qlab_packed.device):
+            _lib.check(lib.wv_label_overlap_hist(_lib.ptr(qlab_packed.contiguous()), _lib.ptr(dblab_packed.contiguous()), lw, Q, N,
+                                                 _lib.ptr(hist), _lib.stream_ptr()), "wv_label_overlap_hist")
+    return hist
+
+
+_NDCG_WEIGHTS = {}               # (device, entries) -> fp64 table w[p] = 1 / log2(p + 2), made on the host by the library
+
+
+def ndcg_weights(k, device=None):
+    """The discount table of wv_ndcg_at_ks, >= k entries (float64), made once per (device, rounded-up length) and kept."""
+    n = max(1024, 1 << (int(k) - 1).bit_length())
+    key = (str(device) if device is not None else "cpu", n)
+    if key not in _NDCG_WEIGHTS:
+        w = torch.empty(n, dtype=torch.float64)
+        _lib.check(_lib.load().wv_ndcg_weights(_lib.ptr(w), n), "wv_ndcg_weights")
+        _NDCG_WEIGHTS[key] = w if device is None else w.to(device)
+    return _NDCG_WEIGHTS[key]
+
+
+def ndcg_at_ks(idx, qlab_packed, dblab_packed, ks, hist=None):
+    """DCG and ideal DCG of ranked lists at several cut-offs from one walk (wv_ndcg_at_ks)
+    -> (dcg, idcg) float64 [Q, len(ks)].  idx: int32 [Q, >= max(ks)]; hist: label_overlap_hist of the WHOLE database (made
+    here when None).  Gains are 2^overlap - 1 in fp64 (beyond an overlap of 62 the reference's int64 overflows: no parity)."""
+    lib = _lib.require_gpu()
+    Q, kfull = idx.shape
+    lw = _label_pair(qlab_packed, dblab_packed, "ndcg_at_ks")
+    uniq, c_ks, cols = _cutoffs(ks, "ndcg_at_ks")
+    if uniq[-1] > kfull:
+        raise ValueError(f"ndcg_at_ks: cut-off {uniq[-1]} outside the lists' length {kfull}")
+    if idx.dtype != torch.int32:
+        raise ValueError("ndcg_at_ks: expected int32 lists")
+    if idx.stride(1) != 1:
+        idx = idx.contiguous()
+    if hist is None:
+        hist = label_overlap_hist(qlab_packed, dblab_packed)
+    if tuple(hist.shape) != (Q, 64 * lw + 1) or hist.dtype != torch.int32:
+        raise ValueError("ndcg_at_ks: hist must be the int32 [Q, 64 * lwords + 1] table of label_overlap_hist")
+    dev = idx.device
+    w = ndcg_weights(uniq[-1], dev)
+    dcg = torch.zeros((Q, len(uniq)), dtype=torch.float64, device=dev)
+    idcg = torch.zeros_like(dcg)
+    if Q:
+        with torch.cuda.device(dev):
+            _lib.check(lib.wv_ndcg_at_ks(_lib.ptr(idx), idx.stride(0), Q, c_ks, len(uniq), _lib.ptr(qlab_packed.contiguous()),
+                                         _lib.ptr(dblab_packed.contiguous()), lw, _lib.ptr(hist.contiguous()), _lib.ptr(w),
+                                         _lib.ptr(dcg), _lib.ptr(idcg), _lib.stream_ptr()), "wv_ndcg_at_ks")
+    return _columns(dcg, idcg, cols)
+
+
 def relbits_wire_words(kin, nbits):
     """int64 words per (query, shard) row of the sharded-mAP wire buffer: [histogram: nbits + 2 int32, padded to 8 bytes |
     relevance string: ceil(kin / 64) uint64]."""

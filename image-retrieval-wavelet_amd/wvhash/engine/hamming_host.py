@@ -194,6 +194,47 @@ def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
     return cum, cumrel
 
 
+def label_overlap_hist(qlab_packed, dblab_packed):
+    """hamming.label_overlap_hist through the host twin (wv_label_overlap_hist_cpu): the same integers."""
+    lib = _lib.load()
+    qlab_packed, dblab_packed = _host(qlab_packed), _host(dblab_packed)
+    lw = qlab_packed.shape[1]
+    if dblab_packed.shape[1] != lw:
+        raise ValueError("label_overlap_hist: label widths differ")
+    if lw not in (1, 2):
+        raise ValueError(f"label_overlap_hist: {lw} label words (graded overlap takes 1 or 2: up to 128 classes)")
+    Q, N = qlab_packed.shape[0], dblab_packed.shape[0]
+    hist = torch.zeros((Q, 64 * lw + 1), dtype=torch.int32)
+    if Q and N:
+        _lib.check(lib.wv_label_overlap_hist_cpu(_lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw, Q, N, _lib.ptr(hist)),
+                   "wv_label_overlap_hist_cpu")
+    return hist
+
+
+def ndcg_at_ks(idx, qlab_packed, dblab_packed, ks, hist=None):
+    """hamming.ndcg_at_ks through the host twin (wv_ndcg_at_ks_cpu): the same table w, the same summation order, the
+    kernel's bits -> (dcg, idcg) float64 [Q, len(ks)]."""
+    from .hamming import _cutoffs, _columns, ndcg_weights
+    lib = _lib.load()
+    idx = _host(idx, torch.int32) if idx.stride(-1) != 1 or idx.dtype != torch.int32 or idx.is_cuda else idx
+    qlab_packed, dblab_packed = _host(qlab_packed), _host(dblab_packed)
+    Q, kfull = idx.shape
+    lw = qlab_packed.shape[1]
+    uniq, c_ks, cols = _cutoffs(ks, "ndcg_at_ks")
+    if uniq[-1] > kfull:
+        raise ValueError(f"ndcg_at_ks: cut-off {uniq[-1]} outside the lists' length {kfull}")
+    hist = label_overlap_hist(qlab_packed, dblab_packed) if hist is None else _host(hist, torch.int32)
+    if tuple(hist.shape) != (Q, 64 * lw + 1):
+        raise ValueError("ndcg_at_ks: hist must be the int32 [Q, 64 * lwords + 1] table of label_overlap_hist")
+    w = ndcg_weights(uniq[-1])
+    dcg = torch.zeros((Q, len(uniq)), dtype=torch.float64)
+    idcg = torch.zeros_like(dcg)
+    if Q:
+        _lib.check(lib.wv_ndcg_at_ks_cpu(_lib.ptr(idx), idx.stride(0), Q, c_ks, len(uniq), _lib.ptr(qlab_packed), _lib.ptr(dblab_packed),
+                                         lw, _lib.ptr(hist), _lib.ptr(w), _lib.ptr(dcg), _lib.ptr(idcg)), "wv_ndcg_at_ks_cpu")
+    return _columns(dcg, idcg, cols)
+
+
 def hamming_map_at_k(*args, **kwargs):
     return None                   # ranking and AP are two calls on the host (same numbers)
 

@@ -52,6 +52,7 @@ const char *wv_last_error(void);
  * relevance-string pair of the sharded mAP (wv_hamming_shard_relbits, wv_merge_relbits_map).  The multi-cut-off entry points
  * (wv_hamming_map_at_ks, wv_merge_relbits_map_ks[_lds_bytes], wv_map_at_ks, wv_map_at_ks_cpu) were added under 5 as well: new symbols only.
  * So were the radius histograms (wv_hamming_radius_hist, wv_hamming_radius_hist_cpu): 71 symbols.
+ * So were the NDCG entry points (wv_label_overlap_hist[_cpu], wv_ndcg_weights, wv_ndcg_at_ks[_cpu]): 76 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -353,6 +354,42 @@ int wv_map_at_ks(const int32_t *idx, int64_t ld, int Q, const int *ks, int nk, c
                  int lwords, float *ap, int32_t *nrel, void *stream);
 int wv_map_at_ks_cpu(const int32_t *idx, int64_t ld, int Q, const int *ks, int nk, const uint64_t *qlab, const uint64_t *dblab,
                      int lwords, float *ap, int32_t *nrel);
+
+/* NDCG from GRADED relevance -- the number of classes a row shares with the query -- as DSCH/_utils.py:551-574 (NDCG) defines
+ * it, without its [Q][N] relevance matrix, its [Q][N] argsort and its per-query sort of all N gains:
+ *   rel(q, n) = popcount(qlab[q] & dblab[n]) over the lwords label words (wv_pack_bits mode 1), 0 .. 64 * lwords
+ *   gain(r)   = 2^r - 1 as an fp64 value, ldexp(1.0, r) - 1.0: exact for r <= 53 and rounded like the reference's int64 ->
+ *               float64 conversion through r = 62.  From r = 63 the reference's int64 2**Rel overflows (2^64 - 1 is -1 there);
+ *               above 62 this fp64 value IS the definition and parity with the reference is not claimed.
+ *   w[p]      = 1 / log2(p + 2), an fp64 table made once on the host by wv_ndcg_weights (w: HOST pointer, k entries); the
+ *               kernel and the twin read the table, neither evaluates a logarithm, neither divides
+ *   DCG@k(q)  = sum over p < k of gain(rel(q, idx[q][p])) * w[p]; entries idx < 0 contribute 0, as in wv_map_at_k
+ *   IDCG@k(q) = the same sum over the gains of all N rows in descending order, position by position from the histogram:
+ *               position p takes the largest r with #{rows with rel >= r} > p, positions past the last row with rel >= 1 add 0
+ *   NDCG@k    = (1 / Q) * sum over the queries with IDCG > 0 of DCG / IDCG (wvhash/engine/ndcg.py; the reference divides by
+ *               all queries)
+ * wv_label_overlap_hist  hist uint32 [Q][64 * lwords + 1], overwritten: hist[q][r] = rows of THIS call that share exactly r
+ *                        classes with query q.  One pass over the plain label words, any N >= 1 (N < 2^32): no prepared blob,
+ *                        no 32,768-row limit.  The rows of the table ADD across row shards (counts of disjoint row sets), like
+ *                        the radius tables above.  No workspace; the zeroing is enqueued on `stream`.
+ * wv_ndcg_at_ks          dcg, idcg fp64 [Q][nk] from ranked lists idx int32 [Q][ld] (as wv_hamming_topk / wv_knn_float write
+ *                        them) at the cut-offs ks -- wv_map_at_ks' rules: HOST pointer, nk in [1, WV_MAX_CUTOFFS], strictly
+ *                        ascending, 1 <= ks[0], ks[nk - 1] <= ld; anything else is WV_EINVAL, answered on the host before any
+ *                        launch; the cut-offs travel by value in the kernel arguments.  hist: the table above for the whole
+ *                        database; w: DEVICE copy of wv_ndcg_weights' table, >= ks[nk - 1] entries.
+ * lwords outside {1, 2} is WV_ENOTSUP.  No workspace, no hidden synchronisation.
+ * Summation order, the same in the kernel and in the host twin, so that dcg and idcg agree BIT FOR BIT: position p belongs to
+ * thread p % 256, a thread adds its terms in increasing position with fma(gain, w[p], acc), a cut-off c is reduced in the round
+ * that holds position c - 1 (threads with p < c contribute their fma, the others their acc): the 64 lanes of a wave in an
+ * xor-butterfly, the four waves in index order.  Column i of a multi-cut call has the bits of a call with ks = {ks[i]}.
+ * _cpu: host twins (HOST pointers, no stream). */
+int wv_label_overlap_hist(const uint64_t *qlab, const uint64_t *dblab, int lwords, int Q, int64_t N, uint32_t *hist, void *stream);
+int wv_label_overlap_hist_cpu(const uint64_t *qlab, const uint64_t *dblab, int lwords, int Q, int64_t N, uint32_t *hist);
+int wv_ndcg_weights(double *w, int64_t k);
+int wv_ndcg_at_ks(const int32_t *idx, int64_t ld, int Q, const int *ks, int nk, const uint64_t *qlab, const uint64_t *dblab,
+                  int lwords, const uint32_t *hist, const double *w, double *dcg, double *idcg, void *stream);
+int wv_ndcg_at_ks_cpu(const int32_t *idx, int64_t ld, int Q, const int *ks, int nk, const uint64_t *qlab, const uint64_t *dblab,
+                      int lwords, const uint32_t *hist, const double *w, double *dcg, double *idcg);
 
 /* Running hit counts along each ranked list: hits[q][p] = relevant entries among idx[q][0..p] (uint32 [Q][k]).
  * The ratios of these counts are the secondary retrieval diagnostics of accuracy_calculator.py:131-181
