@@ -717,6 +717,11 @@ struct PathF32 {
     }
 };
 
+void launch_gemm_f32(GemmPlan g, const float *A, const float *W, const float *bias, float *C, int M, int N, int K, hipStream_t st)
+{
+    PathF32::gemm<EPI_NONE>(g, A, W, bias, nullptr, 1, C, M, N, K, st);
+}
+
 void launch_qproj(const wv_head_params *p, float *Qp, hipStream_t st)
 {
     hipLaunchKernelGGL(k_qproj, dim3((unsigned)ceil_div(p->num_queries * p->embed_dim, 4)), dim3(256), 0, st, p->q_eff,

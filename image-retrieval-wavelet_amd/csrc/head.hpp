@@ -5,6 +5,7 @@
 // launchers run what it answers.
 #pragma once
 #include "common.hpp"
+#include "head_args.hpp"
 
 namespace wv {
 
@@ -98,6 +99,8 @@ void launch_attn_core(const wv_head_params *p, const HeadPlan &pl, const float *
 void launch_layernorm(const float *x, const float *w, const float *b, float *y, int64_t rows, int E, float eps, int nparts,
                       hipStream_t st);
 void launch_mean_rows(const float *x, float *y, int64_t groups, int n, int E, hipStream_t st);
+// C[M][N] = A[M][K] . W[N][K]^T + bias[N] on the fp32 kernel g names (no epilogue): for head_attn.hip
+void launch_gemm_f32(GemmPlan g, const float *A, const float *W, const float *bias, float *C, int M, int N, int K, hipStream_t st);
 
 // The fp32 layout keeps a leading slot for the projected queries; the bf16 one has none (they come with its prepared
 // blob) and holds the MLP hidden layer, an operand only, as bf16.
@@ -122,6 +125,21 @@ inline HeadWs head_ws_layout(const wv_head_params *p, int B, HeadPrec prec)
     w.pooled = take((size_t)B * E * sizeof(float));
     w.pre = take((size_t)B * E * 8 * sizeof(float));   // up to 8 split-K partials of the read-out product
     w.bytes = off;
+    return w;
+}
+
+// wv_band_attn_maps keeps three of them: Qp | K (| V) | ctx, sized for the call that asks for every output
+struct HeadMapsWs {
+    size_t Qp, KV, ctx, bytes;
+};
+inline HeadMapsWs head_maps_ws_layout(const wv_head_params *p, int B)
+{
+    const size_t E = p->embed_dim, Nq = p->num_queries, S = p->num_tokens;
+    HeadMapsWs w;
+    w.Qp = 0;
+    w.KV = w.Qp + align_up((int64_t)(Nq * E * sizeof(float)), 256);
+    w.ctx = w.KV + align_up((int64_t)(S * B * 2 * E * sizeof(float)), 256);
+    w.bytes = w.ctx + align_up((int64_t)((size_t)B * Nq * E * sizeof(float)), 256);
     return w;
 }
 
@@ -198,18 +216,9 @@ inline int readout_ksplit_bf16(int64_t M, int N, int K)
 // the argument check of every head entry point: false with pl.rc / pl.why set when the parameters are refused
 inline bool head_check_params(const wv_head_params *p, int B, HeadPlan &pl)
 {
-    if (!p) return WV_PLAN_REFUSE(pl, WV_EINVAL, "band_attn_pool: null params");
-    const int E = p->embed_dim;
-    if (B < 0) return WV_PLAN_REFUSE(pl, WV_EINVAL, "band_attn_pool: B=%d", B);
-    if (!(E >= 8 && E % 8 == 0)) return WV_PLAN_REFUSE(pl, WV_EINVAL, "band_attn_pool: embed_dim=%d must be a multiple of 8", E);
-    if (!(p->num_heads >= 1 && E % p->num_heads == 0))
-        return WV_PLAN_REFUSE(pl, WV_EINVAL, "band_attn_pool: embed_dim %d not divisible by num_heads %d", E, p->num_heads);
-    if (!(p->num_queries >= 1 && p->num_queries <= 64))
-        return WV_PLAN_REFUSE(pl, WV_EINVAL, "band_attn_pool: num_queries=%d", p->num_queries);
-    if (!(p->num_tokens >= 1 && p->num_tokens <= 64))
-        return WV_PLAN_REFUSE(pl, WV_EINVAL, "band_attn_pool: num_tokens=%d", p->num_tokens);
-    if (!(p->q_eff && p->in_proj_w && p->in_proj_b && p->attn_out_w && p->attn_out_b && p->norm1_w && p->norm1_b &&
-          p->mlp0_w && p->mlp0_b && p->mlp2_w && p->mlp2_b && p->out_w && p->out_b && p->norm2_w && p->norm2_b))
+    if ((pl.rc = head_attn_args_refusal(p, B, "band_attn_pool", pl.why, sizeof(pl.why))) != WV_OK) return false;
+    if (!(p->norm1_w && p->norm1_b && p->mlp0_w && p->mlp0_b && p->mlp2_w && p->mlp2_b && p->out_w && p->out_b && p->norm2_w &&
+          p->norm2_b))
         return WV_PLAN_REFUSE(pl, WV_EINVAL, "band_attn_pool: null weight pointer");
     return true;
 }
@@ -229,7 +238,7 @@ inline HeadPlan head_plan(const wv_head_params *p, int B, HeadPrec prec)
         return pl;
     }
     // k_attn_core keeps kv[S][2E + 4] | q[Nq][E] | P[Nq][heads][S] in LDS
-    pl.attn_lds = ((size_t)S * (2 * E + 4) + (size_t)Nq * E + (size_t)Nq * p->num_heads * S) * sizeof(float);
+    pl.attn_lds = head_attn_lds_bytes(p);
     if (pl.attn_lds > (size_t)kMaxLdsBytes) {
         WV_PLAN_REFUSE(pl, WV_ENOTSUP, "%s: %d tokens x %d queries at embed_dim=%d do not fit the attention kernel's LDS", what, S, Nq, E);
         return pl;

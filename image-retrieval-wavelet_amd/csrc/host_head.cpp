@@ -1,6 +1,7 @@
 // Host twins of the head entry points ("wv_band_attn_pool ... _cpu twins of each taking host pointers"):
 //   wv_band_attn_pool_cpu <- wv_band_attn_pool   CrossAttentionBottleneckHead*.forward in eval mode
 //                                                (/root/reference/main/models/multi_dino_attention.py:1111-1141; :1030, :568, :448)
+//   wv_band_attn_maps_cpu <- wv_band_attn_maps   what the head's nn.MultiheadAttention call returns (:1128), plus the scores
 //   wv_hash_tail_cpu      <- wv_hash_tail        hash_fc -> BatchNorm1d(eval) -> sign (+ bit packing)  (:829-833)
 //   wv_band_attn_pool_bf16_cpu <- wv_band_attn_pool_bf16   the same forward with both operands of the five dense weight
 //                                                products rounded to bf16 (nearest even) and nothing else changed
@@ -22,6 +23,7 @@
 #endif
 
 #include "../../include/wvhash.h"
+#include "head_args.hpp"
 
 namespace wv {
 void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
@@ -221,7 +223,74 @@ int pool_cpu(const wv_head_params *p, const void *feats_any, int feat_dtype, int
     return WV_OK;
 }
 
+// The attention call alone: scores, softmax per head, its mean over the heads, out_proj(context).  Same arithmetic and
+// summation orders as pool_cpu above and as k_attn_maps: fmaf chain over the head dimension, x scale, max-subtracted expf,
+// sum over the tokens in index order, one division; heads averaged in index order.
+int maps_cpu(const wv_head_params *p, const float *feats, int layout, int B, float *probs, float *probs_mean, float *scores,
+             float *attn_out)
+{
+    const int E = p->embed_dim, H = p->num_heads, Nq = p->num_queries, S = p->num_tokens, d = E / H;
+    const float scale = 1.f / sqrtf((float)d), inv_heads = 1.f / (float)H;
+    const int ldkv = attn_out ? 2 * E : E;                      // K alone when nothing needs V
+    std::vector<float> Qp((size_t)Nq * E), kv((size_t)S * E), KV((size_t)S * ldkv), P((size_t)H * Nq * S), ctx((size_t)Nq * E);
+    linear(p->q_eff, E, Nq, p->in_proj_w, p->in_proj_b, E, E, Qp.data(), E);
+    for (int b = 0; b < B; ++b) {
+        for (int s = 0; s < S; ++s) {
+            const size_t row = layout == WV_TOKENS_BSE ? (size_t)b * S + s : (size_t)s * B + b;
+            memcpy(kv.data() + (size_t)s * E, feats + row * E, sizeof(float) * E);
+        }
+        linear(kv.data(), E, S, p->in_proj_w + (size_t)E * E, p->in_proj_b + E, ldkv, E, KV.data(), ldkv);
+        for (int h = 0; h < H; ++h)
+            for (int nq = 0; nq < Nq; ++nq) {
+                float *pr = P.data() + ((size_t)h * Nq + nq) * S, mx = -INFINITY;
+                const float *qh = Qp.data() + (size_t)nq * E + h * d;
+                for (int s = 0; s < S; ++s) {
+                    const float *kh = KV.data() + (size_t)s * ldkv + h * d;
+                    float a = 0.f;
+                    for (int j = 0; j < d; ++j) a = fmaf(qh[j], kh[j], a);
+                    pr[s] = a * scale;
+                    mx = fmaxf(mx, pr[s]);
+                }
+                if (scores) memcpy(scores + (((size_t)b * H + h) * Nq + nq) * S, pr, sizeof(float) * S);
+                float den = 0.f;
+                for (int s = 0; s < S; ++s) { pr[s] = expf(pr[s] - mx); den += pr[s]; }
+                for (int s = 0; s < S; ++s) pr[s] = pr[s] / den;
+            }
+        if (probs) memcpy(probs + (size_t)b * H * Nq * S, P.data(), sizeof(float) * P.size());
+        if (probs_mean)
+            for (int i = 0; i < Nq * S; ++i) {
+                float a = 0.f;
+                for (int h = 0; h < H; ++h) a += P[(size_t)h * Nq * S + i];
+                probs_mean[(size_t)b * Nq * S + i] = a * inv_heads;
+            }
+        if (attn_out) {
+            for (int nq = 0; nq < Nq; ++nq)
+                for (int e = 0; e < E; ++e) {
+                    const float *pr = P.data() + ((size_t)(e / d) * Nq + nq) * S;
+                    float a = 0.f;
+                    for (int s = 0; s < S; ++s) a = fmaf(pr[s], KV[(size_t)s * ldkv + E + e], a);
+                    ctx[(size_t)nq * E + e] = a;
+                }
+            linear(ctx.data(), E, Nq, p->attn_out_w, p->attn_out_b, E, E, attn_out + (size_t)b * Nq * E, E);
+        }
+    }
+    return WV_OK;
+}
+
 }  // namespace
+
+extern "C" int wv_band_attn_maps_cpu(const wv_head_params *p, const float *feats, int layout, int B, float *probs, float *probs_mean,
+                                     float *scores, float *attn_out)
+{
+    char why[256];
+    if (const int rc = ::wv::head_attn_args_refusal(p, B, "band_attn_maps_cpu", why, sizeof(why))) HH_FAIL(rc, "%s", why);
+    HH_REQUIRE(probs || probs_mean || scores || attn_out, "band_attn_maps_cpu: no output asked for");
+    HH_REQUIRE(layout == WV_TOKENS_SBE || layout == WV_TOKENS_BSE, "band_attn_maps_cpu: layout=%d (WV_TOKENS_SBE or WV_TOKENS_BSE)",
+               layout);
+    if (B == 0) return WV_OK;
+    HH_REQUIRE(feats, "band_attn_maps_cpu: null buffer");
+    return maps_cpu(p, feats, layout, B, probs, probs_mean, scores, attn_out);
+}
 
 extern "C" int wv_band_attn_pool_cpu(const wv_head_params *p, const float *feats, int B, float *out)
 {

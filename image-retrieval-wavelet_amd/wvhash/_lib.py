@@ -22,6 +22,7 @@ WV_METRIC_IP, WV_METRIC_L2, WV_METRIC_L2_SQUARED = 0, 1, 2
 WV_RANK_DESCENDING, WV_RANK_SQRT = 1, 2
 ABI_VERSION = 5        # what include/wvhash.h documents; load() refuses a library that reports another one
 WV_BANDS_INNER, WV_BANDS_OUTER = 0, 1
+WV_TOKENS_SBE, WV_TOKENS_BSE = 0, 1      # band tokens as [S][B][E] (wv_band_attn_pool's) or [B][S][E] (torch.stack(kv_list, 1))
 WV_ENOTSUP = -95            # return code: the shape is outside the kernel asked for (callers fall back)
 
 
@@ -31,6 +32,10 @@ class WvhashUnavailable(RuntimeError):
 
 class WvhashError(RuntimeError):
     pass
+
+
+class WvhashUnsupported(WvhashError):
+    """WV_ENOTSUP from an entry point whose caller has another way to the same result."""
 
 
 class HeadParams(ctypes.Structure):
@@ -131,6 +136,9 @@ SIGNATURES = {
     "wv_band_attn_pool_bf16_workspace_bytes": (_sz, [ctypes.POINTER(HeadParams), _i]),
     "wv_band_attn_pool_bf16": (_i, [ctypes.POINTER(HeadParams), _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "wv_band_attn_pool_bf16_cpu": (_i, [ctypes.POINTER(HeadParams), _vp, _i, _i, _vp]),
+    "wv_band_attn_maps_workspace_bytes": (_sz, [ctypes.POINTER(HeadParams), _i]),
+    "wv_band_attn_maps": (_i, [ctypes.POINTER(HeadParams), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wv_band_attn_maps_cpu": (_i, [ctypes.POINTER(HeadParams), _vp, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None
@@ -208,6 +216,23 @@ def stream_ptr():
 
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def wv_band_attn_maps(p, feats, layout, B, probs=None, probs_mean=None, scores=None, attn_out=None):
+    """The attention maps of the head into the given fp32 tensors (None = not wanted): wv_band_attn_maps on the stream of
+    `feats`' GPU with a workspace of its own, or the host twin wv_band_attn_maps_cpu when `feats` is a host tensor.  Every
+    pointer of `p` must live where `feats` does."""
+    outs = [ptr(t) for t in (probs, probs_mean, scores, attn_out)]
+    if not feats.is_cuda:
+        return check(load().wv_band_attn_maps_cpu(ctypes.byref(p), ptr(feats), layout, B, *outs), "wv_band_attn_maps_cpu")
+    lib = require_gpu()
+    with torch.cuda.device(feats.device):
+        nbytes = lib.wv_band_attn_maps_workspace_bytes(ctypes.byref(p), B)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=feats.device)
+        rc = lib.wv_band_attn_maps(ctypes.byref(p), ptr(feats), layout, B, *outs, ptr(ws), ctypes.c_size_t(nbytes), stream_ptr())
+    if rc == WV_ENOTSUP:
+        raise WvhashUnsupported("wv_band_attn_maps: " + lib.wv_last_error().decode(errors="replace"))
+    check(rc, "wv_band_attn_maps")
 
 
 def host_floats(values):

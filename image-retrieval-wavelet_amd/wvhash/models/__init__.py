@@ -1,12 +1,12 @@
 from .fusion import (CrossAttentionBottleneckHead, CrossAttentionBottleneckHeadAdvanced,
                      CrossAttentionBottleneckHeadPooled, CrossAttentionBottleneckHeadDecoupled,
-                     get_fusion_head, band_attn_pool)
+                     get_fusion_head, band_attn_pool, band_attn_maps, BandMultiheadAttention)
 from .fusion_extra import (AdvancedFusionModule, AttentionFusionHead, GatedFusionHead, SemanticFusionHead, StandardFusionHead,
                            TemperatureFusionHead, TemperatureGatedFusionHead)
 from .hashing import SharedDinoHashing, MultiDinoHashing, hash_tail, load_dinov2
 
 __all__ = ["CrossAttentionBottleneckHead", "CrossAttentionBottleneckHeadAdvanced",
            "CrossAttentionBottleneckHeadPooled", "CrossAttentionBottleneckHeadDecoupled", "get_fusion_head",
-           "band_attn_pool", "SharedDinoHashing", "MultiDinoHashing", "hash_tail", "load_dinov2", "StandardFusionHead",
+           "band_attn_pool", "band_attn_maps", "BandMultiheadAttention", "SharedDinoHashing", "MultiDinoHashing", "hash_tail", "load_dinov2", "StandardFusionHead",
            "TemperatureFusionHead", "SemanticFusionHead", "GatedFusionHead", "TemperatureGatedFusionHead",
            "AttentionFusionHead", "AdvancedFusionModule"]

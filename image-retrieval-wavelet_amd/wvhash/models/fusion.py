@@ -6,7 +6,13 @@ Eval-mode forward on GPU tensors runs the HIP/MFMA kernels (wv_band_attn_pool; w
 "auto" the opt-in bf16 matrix-core path, wv_band_attn_pool_bf16).  Training-mode
 forward (dropout, autograd, ortho loss) is stock PyTorch on the GPU: training is outside the
 accelerated path.  There is no CPU execution path.
+
+The fused forward never calls `head.attn`.  A head whose `attn` carries a forward hook, a forward pre-hook or a patched
+`forward` (the reference's attention.py and studies/measure_attention_collapse.py read the head that way) makes that call
+as well, once per forward, and the module answers it from wv_band_attn_maps (BandMultiheadAttention); the head's own
+result still comes from wv_band_attn_pool, so an observer never changes a code bit.
 """
+import collections
 import ctypes
 import logging
 
@@ -174,6 +180,85 @@ def band_attn_pool_host(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, ou
     return out
 
 
+AttnMaps = collections.namedtuple("AttnMaps", "weights scores attn_output")
+_LAYOUTS = {"sbe": _lib.WV_TOKENS_SBE, "bse": _lib.WV_TOKENS_BSE}
+
+
+def band_attn_maps(kv, q_eff, attn, layout="bse", per_head=True, want=("probs", "scores", "attn_out")):
+    """What `attn(query=q_eff broadcast over the batch, key=kv, value=kv)` computes in eval mode, through wv_band_attn_maps
+    (GPU tensors) or its host twin (host tensors): AttnMaps(weights, scores, attn_output), None for what `want` leaves out.
+    kv: the band tokens, [B, S, E] (layout "bse": torch.stack(kv_list, 1)) or [S, B, E] ("sbe"); q_eff: [Nq, E] or [1, Nq, E].
+    weights ("probs"): the softmax, [B, H, Nq, S] with per_head, else its mean over the heads [B, Nq, S]; scores: what the
+    softmax is taken of, [B, H, Nq, S]; attn_output ("attn_out"): out_proj(context), [B, Nq, E].  Always fp32 arithmetic:
+    bf16 tokens are upcast, and under matrix_dtype="bf16" these are the fp32 attention of the same parameters and tokens,
+    not the bf16 path's internal values."""
+    if layout not in _LAYOUTS:
+        raise ValueError(f"band_attn_maps: layout must be 'bse' or 'sbe', got {layout!r}")
+    want = tuple(want)
+    if not want or set(want) - {"probs", "scores", "attn_out"}:
+        raise ValueError(f"band_attn_maps: want must name some of 'probs', 'scores', 'attn_out', got {want!r}")
+    if kv.dim() != 3:
+        raise ValueError(f"band_attn_maps: kv must be [B, S, E] or [S, B, E], got {tuple(kv.shape)}")
+    kv = kv.detach().float().contiguous()
+    E = kv.shape[2]
+    B, S = (kv.shape[0], kv.shape[1]) if layout == "bse" else (kv.shape[1], kv.shape[0])
+    keep = [t.detach().float().contiguous() for t in
+            (q_eff.reshape(-1, E), attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, attn.out_proj.bias)]
+    if any(t.device != kv.device for t in keep):
+        raise ValueError("band_attn_maps: the module's parameters and the query tokens must live where kv does")
+    p = _lib.HeadParams()                                    # every pointer the maps do not read stays NULL
+    p.embed_dim, p.num_heads, p.num_queries, p.num_tokens = E, attn.num_heads, keep[0].shape[0], S
+    p.q_eff, p.in_proj_w, p.in_proj_b, p.attn_out_w, p.attn_out_b = [t.data_ptr() for t in keep]
+    H, Nq = p.num_heads, p.num_queries
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=kv.device)
+    weights = (new(B, H, Nq, S) if per_head else new(B, Nq, S)) if "probs" in want else None
+    scores = new(B, H, Nq, S) if "scores" in want else None
+    attn_out = new(B, Nq, E) if "attn_out" in want else None
+    _lib.wv_band_attn_maps(p, kv, _LAYOUTS[layout], B, probs=weights if per_head else None,
+                           probs_mean=None if per_head else weights, scores=scores, attn_out=attn_out)
+    return AttnMaps(weights, scores, attn_out)
+
+
+class BandMultiheadAttention(nn.MultiheadAttention):
+    """nn.MultiheadAttention -- same parameters, same state_dict keys -- whose eval-mode forward answers the heads' call
+    (batch-broadcast queries attending over a few band tokens, key is value, no masks, fp32) from the library:
+    wv_band_attn_maps on the GPU, its host twin on the host.  Every other call (training mode, masks, distinct key and
+    value, per-sample queries, other dtypes, tensors that need autograd, shapes outside the kernel) is stock PyTorch."""
+
+    def _library_takes(self, query, key, value, key_padding_mask, attn_mask, is_causal):
+        if (self.training or not self.batch_first or not self._qkv_same_embed_dim or self.in_proj_bias is None
+                or self.bias_k is not None or self.add_zero_attn):
+            return False
+        if key_padding_mask is not None or attn_mask is not None or is_causal or key is not value:
+            return False
+        if query.dim() != 3 or key.dim() != 3 or query.shape[0] != key.shape[0] or query.shape[0] == 0:
+            return False
+        if not (query.stride(0) == 0 or query.shape[0] == 1):                 # one set of queries for the whole batch
+            return False
+        E = self.embed_dim
+        if query.shape[2] != E or key.shape[2] != E or E % 8 or not (1 <= query.shape[1] <= 64 and 1 <= key.shape[1] <= 64):
+            return False
+        if query.dtype != torch.float32 or key.dtype != torch.float32:
+            return False
+        if not (query.device == key.device == self.in_proj_weight.device) or key.device.type not in ("cuda", "cpu"):
+            return False
+        return not (torch.is_grad_enabled() and (query.requires_grad or key.requires_grad))
+
+    def forward(self, query, key, value, key_padding_mask=None, need_weights=True, attn_mask=None,
+                average_attn_weights=True, is_causal=False):
+        if self._library_takes(query, key, value, key_padding_mask, attn_mask, is_causal):
+            try:
+                maps = band_attn_maps(key, query[0], self, "bse", per_head=not average_attn_weights,
+                                      want=("probs", "attn_out") if need_weights else ("attn_out",))
+                return maps.attn_output, maps.weights
+            except _lib.WvhashUnsupported:                                     # WV_ENOTSUP: more tokens than fit the kernel's LDS
+                pass
+        return super().forward(query, key, value, key_padding_mask=key_padding_mask, need_weights=need_weights,
+                               attn_mask=attn_mask, average_attn_weights=average_attn_weights, is_causal=is_causal)
+
+
 class CrossAttentionBottleneckHeadAdvanced(nn.Module):
     _pool = "concat"
 
@@ -190,7 +275,7 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
         ])
         self.query_tokens = nn.Parameter(torch.randn(1, num_queries, embed_dim))
         nn.init.trunc_normal_(self.query_tokens, std=0.02)
-        self.attn = nn.MultiheadAttention(embed_dim, num_heads, dropout=dropout, batch_first=True)
+        self.attn = BandMultiheadAttention(embed_dim, num_heads, dropout=dropout, batch_first=True)
         self.norm1 = nn.LayerNorm(embed_dim)
         self.norm2 = nn.LayerNorm(embed_dim)
         self.mlp = nn.Sequential(
@@ -240,6 +325,39 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
             return False
         return not (torch.is_grad_enabled() and any(t.requires_grad for t in kv_list))
 
+    def _attn_observed(self):
+        """Someone reads this head through its `attn` submodule: a forward hook, a forward pre-hook or an instance-level
+        `forward` (module-global hooks, nn.modules.module.register_module_forward_hook, are not looked at)."""
+        a = self.attn
+        if a._forward_hooks or a._forward_pre_hooks:
+            return True
+        # a patch that was "restored" with setattr leaves the class's own bound method in the instance: no override
+        f = vars(a).get("forward")
+        return f is not None and not (getattr(f, "__self__", None) is a and getattr(f, "__func__", None) is type(a).forward)
+
+    def _observe_attention(self, kv_list, batch_size):
+        """The call the reference's forward makes on `attn`, through nn.Module.__call__ so that its observers fire; the
+        module computes it with wv_band_attn_maps / the host twin (BandMultiheadAttention).  The result is theirs alone."""
+        if batch_size == 0:
+            return
+        with torch.no_grad():
+            q = self.effective_queries().float().expand(batch_size, -1, -1)
+            kv = torch.stack([t.float() for t in kv_list], dim=1)
+            self.attn(query=q, key=kv, value=kv)
+
+    def attention_maps(self, features_list, per_head=False, scores=False):
+        """The attention of this head over the bands of `features_list` (S x [B, dim]), without hooks: the softmax weights
+        [B, Nq, S] (per_head: [B, H, Nq, S]); with scores=True the pair (weights, pre-softmax scores [B, H, Nq, S]).  Eval-mode
+        values (no dropout, no LL masking) in fp32 whatever `matrix_dtype` is; GPU tensors or, through the host twin, host
+        tensors."""
+        with torch.no_grad():
+            kv_list = [proj(f) for proj, f in zip(self.projections, features_list)]
+            if any(t.dim() != 2 for t in kv_list):
+                raise ValueError("attention_maps covers CLS-token inputs ([B, dim] per band)")
+            maps = band_attn_maps(torch.stack([t.float() for t in kv_list], dim=0), self.effective_queries(), self.attn, "sbe",
+                                  per_head=per_head, want=("probs", "scores") if scores else ("probs",))
+        return (maps.weights, maps.scores) if scores else maps.weights
+
     def forward(self, features_list):
         batch_size = features_list[0].shape[0]
         device = features_list[0].device
@@ -257,6 +375,8 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
                 raise _lib.WvhashUnavailable("the eval-mode fusion head on host tensors covers CLS-token inputs ([B, E] per "
                                              "band, E a multiple of 8, at most 64 bands) of a model that lives on the host")
             self.last_ortho_loss = torch.zeros(())
+            if self._attn_observed():
+                self._observe_attention(kv_list, batch_size)
             with torch.no_grad():
                 return band_attn_pool_host(kv_list, self.effective_queries(), self.attn, self.norm1, self.norm2,
                                            self.mlp[0], self.mlp[2], self.out_proj, self._pool == "mean",
@@ -268,6 +388,8 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
             if self._zero_loss is None or self._zero_loss.device != device:
                 self._zero_loss = torch.zeros((), device=device)
             self.last_ortho_loss = self._zero_loss
+            if self._attn_observed():
+                self._observe_attention(kv_list, batch_size)
             with torch.no_grad():
                 out = band_attn_pool(kv_list, self.effective_queries(), self.attn, self.norm1, self.norm2,
                                      self.mlp[0], self.mlp[2], self.out_proj, self._pool == "mean", self._ws,

@@ -53,6 +53,7 @@ const char *wv_last_error(void);
  * (wv_hamming_map_at_ks, wv_merge_relbits_map_ks[_lds_bytes], wv_map_at_ks, wv_map_at_ks_cpu) were added under 5 as well: new symbols only.
  * So were the radius histograms (wv_hamming_radius_hist, wv_hamming_radius_hist_cpu): 71 symbols.
  * So were the NDCG entry points (wv_label_overlap_hist[_cpu], wv_ndcg_weights, wv_ndcg_at_ks[_cpu]): 76 symbols.
+ * So were the attention maps of the head (wv_band_attn_maps[_workspace_bytes], wv_band_attn_maps_cpu): 79 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -527,6 +528,35 @@ size_t wv_band_attn_pool_bf16_workspace_bytes(const wv_head_params *p, int B);
 int wv_band_attn_pool_bf16(const wv_head_params *p, const void *prepared_bf16, const void *feats, int feat_dtype, int B,
                            float *out, void *workspace, size_t workspace_bytes, void *stream);
 int wv_band_attn_pool_bf16_cpu(const wv_head_params *p, const void *feats, int feat_dtype, int B, float *out);
+
+/* ------------------------------------------------------------------------------------------
+ * Attention maps of the head: what its nn.MultiheadAttention submodule returns for the call the forward makes
+ * (attn(query = q_eff broadcast over the batch, key = value = the band tokens)), as outputs of their own.  wv_band_attn_pool
+ * keeps these values in LDS; this is the diagnostic path for forward hooks on `head.attn` and for studies of the attention.
+ * Any subset of the four outputs, at least one:
+ *   probs       [B][H][Nq][S]  softmax over the S band tokens, per head (average_attn_weights=False)
+ *   probs_mean  [B][Nq][S]     its mean over the H heads, summed in head order (the module's default output[1])
+ *   scores      [B][H][Nq][S]  what the softmax is taken of: (q Wq^T + bq) . (k Wk^T + bk) / sqrt(E / H)
+ *   attn_out    [B][Nq][E]     out_proj(context) + bias (output[0])
+ * feats: the band tokens, [S][B][E] (WV_TOKENS_SBE: what wv_band_attn_pool takes) or [B][S][E] (WV_TOKENS_BSE:
+ * torch.stack(kv_list, 1), the module's batch_first key), fp32, read in place.
+ * Of `p` only embed_dim, num_heads, num_queries, num_tokens, q_eff, in_proj_w, in_proj_b, attn_out_w, attn_out_b and the
+ * optional q_proj are read (ranges as for wv_band_attn_pool); every other pointer may be NULL and `prepared` is ignored.
+ * Always fp32 arithmetic, that of wv_band_attn_pool's separate launches in the same order (fmaf chain over the head
+ * dimension, x scale, max-subtracted expf, sum over the tokens in index order, one division); V is projected only when
+ * attn_out is asked for.  Workspace: device memory of wv_band_attn_maps_workspace_bytes(p, B) bytes (enough for any subset).
+ * B == 0: WV_OK, nothing touched.  WV_EINVAL: no output asked for, an unknown layout, a workspace shorter than that (the text
+ * names the need), parameters out of range; WV_ENOTSUP: a shape wv_band_attn_pool refuses for its LDS need.  All answered on
+ * the host before anything is launched.  No hidden synchronisation.
+ * Host twin (HOST pointers, no workspace, no stream, q_proj ignored): the same outputs with the summation orders above and
+ * the twins' eight-chain products; agrees with the kernel to fp32 rounding, not bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+enum { WV_TOKENS_SBE = 0, WV_TOKENS_BSE = 1 };
+size_t wv_band_attn_maps_workspace_bytes(const wv_head_params *p, int B);
+int wv_band_attn_maps(const wv_head_params *p, const float *feats, int layout, int B, float *probs, float *probs_mean,
+                      float *scores, float *attn_out, void *workspace, size_t workspace_bytes, void *stream);
+int wv_band_attn_maps_cpu(const wv_head_params *p, const float *feats, int layout, int B, float *probs, float *probs_mean,
+                          float *scores, float *attn_out);
 
 #ifdef __cplusplus
 }
