@@ -202,6 +202,17 @@ def c_swt2_level_n(plane, wavelet, level):
     return out
 
 
+def c_transform_planes(planes_f32, wavelet, level):
+    """[P, H, W] float32 planes (already scaled) -> [P, 4, H, W]: c_swt2_level_n per plane, for any channel count and
+    for float input."""
+    planes = np.asarray(planes_f32, dtype=np.float32)
+    P, H, W = planes.shape
+    out = np.empty((P, 4, H, W), dtype=np.float32)
+    for p in range(P):
+        out[p] = c_swt2_level_n(planes[p], wavelet, level)
+    return out
+
+
 def c_transform_batch(imgs_bhwc_u8, wavelet="haar", level=1, mode="swt"):
     lo, hi = filters(wavelet)
     lo32 = np.ascontiguousarray(lo, dtype=np.float32)
