@@ -20,7 +20,7 @@
 namespace wv {
 
 // C[M][N] = epi(A[M][K] . W[N][K]^T + bias[N]), epilogues: head.hpp (store_block, GELU through erff).
-// Wave tile = (32*TM) x (32*TN); workgroup = 2 x 2 waves.  Same operand scheme as k_scores
+// Wave tile = (32*TM) x (32*TN); workgroup = 2 x 2 waves.  Same operand scheme as k_scores_lds
 // (knn_float.hip): lane l feeds row l&31, lane half h covers k in [8c+4h, 8c+4h+4).
 template <int TM, int TN, int EPI>
 __global__ __launch_bounds__(256) void k_gemm_nt(const float *__restrict__ A, const float *__restrict__ W,

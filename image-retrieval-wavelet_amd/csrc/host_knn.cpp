@@ -4,7 +4,7 @@
 //
 // Same results as the gfx950 path, bit for bit:
 //  * v_mfma_f32_32x32x2_f32 IS an fmaf chain -- D = fma(a1, b1, fma(a0, b0, C)), k = 0 before k = 1, every one of 204,800
-//    random outputs (tools/mfma_order_test.hip) -- and k_scores* feeds it k = 8c + e (lane half 0) and 8c + 4 + e (half 1)
+//    random outputs (tools/mfma_order_test.hip) -- and k_scores_lds feeds it k = 8c + e (lane half 0) and 8c + 4 + e (half 1)
 //    for e = 0..3 of every chunk c of eight; the zero padding beyond D adds exact zeros.  The dot product below walks k in
 //    that order with fused multiply-adds (the FMA instruction when the CPU has it, fmaf otherwise: the same bits);
 //  * |x|^2 as k_row_sqnorm forms it: lane l of a wave sums k = l, l + 64, ... with fmaf, the 64 partial sums meet in the
@@ -22,43 +22,15 @@
 #include <immintrin.h>
 #endif
 
-#include "../../include/wvhash.h"
-
-namespace wv {
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-
-#define HK_FAIL(code, ...)            \
-    do {                              \
-        ::wv::set_error(__VA_ARGS__); \
-        return (code);                \
-    } while (0)
-#define HK_REQUIRE(cond, ...)                         \
-    do {                                              \
-        if (!(cond)) HK_FAIL(WV_EINVAL, __VA_ARGS__); \
-    } while (0)
+#include "knn_args.hpp"
 
 namespace {
 
 constexpr int kLanes = 8;     // database rows per vector
 constexpr int kBlocks = 8;    // vectors in flight per query: eight independent fma chains
 
-inline uint32_t float_to_key(float v, bool descending)
-{
-    v += 0.0f;  // -0 -> +0
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
-    return descending ? ~u : u;
-}
-inline float key_to_float(uint32_t u, bool descending)
-{
-    if (descending) u = ~u;
-    u ^= (u >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-    float v;
-    memcpy(&v, &u, 4);
-    return v;
-}
+using wv::float_to_key;
+using wv::key_to_float;
 
 // k in the order the matrix cores accumulate it
 std::vector<int> accumulation_order(int D)
@@ -123,18 +95,26 @@ void dots(const float *qo, const float *bt, int D, float *out)
     dots_plain(qo, bt, D, out);
 }
 
+// The closing step of both twins: the k best of a row's (key << 32 | column) words in ascending order -> index and value lists
+void rank_and_write(std::vector<uint64_t> &keyed, int k, bool desc, bool root, int32_t *idx, float *val)
+{
+    if ((size_t)k < keyed.size()) std::nth_element(keyed.begin(), keyed.begin() + k, keyed.end());
+    std::sort(keyed.begin(), keyed.begin() + k);
+    for (int j = 0; j < k; ++j) {
+        const uint64_t e = keyed[(size_t)j];
+        const float v = key_to_float((uint32_t)(e >> 32), desc);
+        idx[j] = (int32_t)(uint32_t)e;
+        val[j] = root ? sqrtf(v) : v;
+    }
+}
+
 }  // namespace
 
 extern "C" int wv_knn_float_cpu(const float *q, const float *db, int Q, int64_t N, int D, int metric, int k, int32_t *idx,
                                 float *val)
 {
-    HK_REQUIRE(q && db && idx && val, "knn_float_cpu: null buffer");
-    HK_REQUIRE(Q >= 0 && N >= 1 && D >= 1, "knn_float_cpu: bad shape Q=%d N=%lld D=%d", Q, (long long)N, D);
-    HK_REQUIRE(metric == WV_METRIC_IP || metric == WV_METRIC_L2 || metric == WV_METRIC_L2_SQUARED, "knn_float_cpu: metric %d",
-               metric);
-    HK_REQUIRE(k >= 1 && k <= N, "knn_float_cpu: k=%d must be in [1, N=%lld] (torch.topk raises too)", k, (long long)N);
-    HK_REQUIRE(N <= (1ll << 26), "knn_float_cpu: N=%lld above the supported 2^26 rows", (long long)N);
-    if (Q == 0) return WV_OK;
+    const int refused = wv::knn_float_args("knn_float_cpu", q && db && idx && val, Q, N, D, metric, k);
+    if (refused != WV_OK || Q == 0) return refused;
     const bool l2 = metric != WV_METRIC_IP, desc = !l2;
     const std::vector<int> ord = accumulation_order(D);
     // database rows interleaved eight by eight, k in accumulation order (rows beyond N are zeros and never ranked)
@@ -162,38 +142,21 @@ extern "C" int wv_knn_float_cpu(const float *q, const float *db, int Q, int64_t 
             if (l2) v = fmaxf(0.f, fmaf(-2.f, v, qn + dbn[(size_t)n]));
             keyed[(size_t)n] = ((uint64_t)float_to_key(v, desc) << 32) | (uint32_t)n;
         }
-        if ((int64_t)k < N) std::nth_element(keyed.begin(), keyed.begin() + k, keyed.end());
-        std::sort(keyed.begin(), keyed.begin() + k);
-        for (int j = 0; j < k; ++j) {
-            const uint64_t e = keyed[(size_t)j];
-            const float v = key_to_float((uint32_t)(e >> 32), desc);
-            idx[(size_t)qi * k + j] = (int32_t)(uint32_t)e;
-            val[(size_t)qi * k + j] = metric == WV_METRIC_L2 ? sqrtf(v) : v;
-        }
+        rank_and_write(keyed, k, desc, metric == WV_METRIC_L2, idx + (size_t)qi * k, val + (size_t)qi * k);
     }
     return WV_OK;
 }
 
 extern "C" int wv_rank_scores_cpu(const float *S, int Q, int64_t N, int k, int flags, int32_t *idx, float *val)
 {
-    HK_REQUIRE(S && idx && val, "rank_scores_cpu: null buffer");
-    HK_REQUIRE(Q >= 0 && N >= 1, "rank_scores_cpu: bad shape Q=%d N=%lld", Q, (long long)N);
-    HK_REQUIRE(k >= 1 && k <= N, "rank_scores_cpu: k=%d must be in [1, N=%lld]", k, (long long)N);
-    HK_REQUIRE(N <= (1ll << 26), "rank_scores_cpu: N=%lld above the supported 2^26 columns", (long long)N);
-    HK_REQUIRE((flags & ~(WV_RANK_DESCENDING | WV_RANK_SQRT)) == 0, "rank_scores_cpu: flags %d", flags);
+    const int refused = wv::rank_scores_args("rank_scores_cpu", S && idx && val, Q, N, k, flags);
+    if (refused != WV_OK) return refused;
     const bool desc = (flags & WV_RANK_DESCENDING) != 0, root = (flags & WV_RANK_SQRT) != 0;
     std::vector<uint64_t> keyed((size_t)N);
     for (int qi = 0; qi < Q; ++qi) {
         const float *row = S + (size_t)qi * N;
         for (int64_t n = 0; n < N; ++n) keyed[(size_t)n] = ((uint64_t)float_to_key(row[n], desc) << 32) | (uint32_t)n;
-        if ((int64_t)k < N) std::nth_element(keyed.begin(), keyed.begin() + k, keyed.end());
-        std::sort(keyed.begin(), keyed.begin() + k);
-        for (int j = 0; j < k; ++j) {
-            const uint64_t e = keyed[(size_t)j];
-            const float v = key_to_float((uint32_t)(e >> 32), desc);
-            idx[(size_t)qi * k + j] = (int32_t)(uint32_t)e;
-            val[(size_t)qi * k + j] = root ? sqrtf(v) : v;
-        }
+        rank_and_write(keyed, k, desc, root, idx + (size_t)qi * k, val + (size_t)qi * k);
     }
     return WV_OK;
 }

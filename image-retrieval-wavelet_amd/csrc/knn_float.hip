@@ -6,16 +6,23 @@
 //     (for more than 25 rows cdist itself evaluates sqrt(max(0, |q|^2 + |r|^2 - 2 q.r)) through a
 //      matmul, which is the form used here)
 //
-// k_scores: one wave owns a 64x64 tile of the [Q, N] score matrix as 2x2 blocks of
+// k_scores_lds: one wave owns a 64x64 tile of the [Q, N] score matrix as 2x2 blocks of
 //   v_mfma_f32_32x32x2_f32 (fp32 in / fp32 accumulate: bit-for-bit an fmaf chain, so no precision
 //   is traded for the matrix cores).  Lane l feeds row (l & 31) of A and of B; lane half h = l>>5
 //   covers k in [8c+4h, 8c+4h+4) of every 8-wide chunk with ONE float4 per operand -- the MFMA
 //   sums over k, so any k <-> (step, half) bijection shared by A and B is valid.  Both operands are
-//   read from fragment images (k_pack_fragments) in which those 64 float4 are contiguous.
-// k_radix_pass: exact ranking of every row by 6 stable LSD counting-sort passes over the
-//   order-preserving 32-bit image of the float (ties therefore end in ascending index order),
-//   with the same private-column LDS histogram as the Hamming ranking kernel (topk.hip).
+//   read from fragment images (k_pack_fragments) in which those 64 float4 are contiguous; the four
+//   waves of a workgroup share them through an LDS ring.
+// k_row_topk: the k <= 15,360 best of a row ranked inside one workgroup's LDS (value bins); rows it
+//   cannot take are handed to
+// k_row_radix: exact ranking of a row in one launch -- [radix selection of the k best when 2k <= N]
+//   + 6 stable LSD counting-sort passes over the order-preserving 32-bit image of the float (ties
+//   therefore end in ascending index order), with the same private-column LDS histogram as the
+//   Hamming ranking kernel (topk.hip).
+// The entry points carve one workspace layout (KnnLayout) and rank by one plan (RankPlan); their
+// argument rules are shared with the host twins (knn_args.hpp).
 #include "common.hpp"
+#include "knn_args.hpp"
 
 namespace wv {
 
@@ -43,7 +50,7 @@ __global__ __launch_bounds__(256) void k_row_sqnorm(const float *__restrict__ x,
 
 // Fragment image of an embedding matrix x [rows, D]: for every block of 32 rows and every chunk of 8 k-values the 64
 // float4 a wave feeds to four v_mfma_f32_32x32x2_f32 -- lane (r, h) holds x[32 rb + r][8c + 4h .. 8c + 4h + 4) -- lie in
-// lane order, 1 KB contiguous.  k_scores then reads each operand fragment with ONE fully coalesced load instruction
+// lane order, 1 KB contiguous.  k_scores_lds then reads each operand fragment with ONE fully coalesced load instruction
 // (the row-major matrix gave 32 B per row per instruction, a quarter of every line it pulled through L1: the operand
 // stream, not the matrix pipe, set its pace).  Rows beyond `rows` and k beyond D are zeros; a workgroup writes the four
 // chunks that share one 128-byte line of each source row.
@@ -115,15 +122,6 @@ struct ScoreFrag {
     float4 a[2], b[2];   // the 32-row blocks of the wave's 64 x 64 tile
 };
 
-__device__ __forceinline__ void scores_load(ScoreFrag &f, const float4 *const (&af)[2], const float4 *const (&bf)[2], int c)
-{
-#pragma unroll
-    for (int blk = 0; blk < 2; ++blk) {
-        f.a[blk] = af[blk][(int64_t)c * 64];
-        f.b[blk] = bf[blk][(int64_t)c * 64];
-    }
-}
-
 __device__ __forceinline__ void scores_mma(f32x16 (&acc)[2][2], const ScoreFrag &f)
 {
     // consecutive MFMAs go to different accumulators: a dependent pair is four instructions apart
@@ -134,74 +132,16 @@ __device__ __forceinline__ void scores_mma(f32x16 (&acc)[2][2], const ScoreFrag 
 #undef WV_SC_STEP
 }
 
-__global__ __launch_bounds__(256, 3) void k_scores(const float4 *__restrict__ qf, const float4 *__restrict__ dbf,
-                                                const float *__restrict__ qn, const float *__restrict__ dbn,
-                                                float *__restrict__ S, int Q, int64_t N, int nchunk, int metric)
-{
-    const int lane = lane_id(), wv = __builtin_amdgcn_readfirstlane(wave_id());
-    const int r = lane & 31, h = lane >> 5;
-    // 128x128 per workgroup, wave (wv>>1, wv&1) owns a 64x64 quadrant
-    const int64_t i0 = (int64_t)blockIdx.y * 128 + (wv >> 1) * 64;
-    const int64_t j0 = (int64_t)blockIdx.x * 128 + (wv & 1) * 64;
-    if (i0 >= Q || j0 >= N) return;
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
-
-    // both images are padded to whole 128-row tiles, so every block a wave touches exists
-    const float4 *af[2], *bf[2];
-#pragma unroll
-    for (int blk = 0; blk < 2; ++blk) {
-        af[blk] = qf + ((i0 >> 5) + blk) * nchunk * 64 + lane;
-        bf[blk] = dbf + ((j0 >> 5) + blk) * nchunk * 64 + lane;
-    }
-    // the fragments of chunk c + 1 are in flight while the 16 MFMAs of chunk c issue (pinned with sched_barrier: left
-    // alone, the scheduler sinks every load to its first use)
-    ScoreFrag f0, f1;
-    scores_load(f0, af, bf, 0);
-    int c = 0;
-    for (; c + 2 < nchunk; c += 2) {
-        scores_load(f1, af, bf, c + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        scores_mma(acc, f0);
-        __builtin_amdgcn_sched_barrier(0);
-        scores_load(f0, af, bf, c + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        scores_mma(acc, f1);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (c + 1 < nchunk) {
-        scores_load(f1, af, bf, c + 1);
-        scores_mma(acc, f0);
-        scores_mma(acc, f1);
-    } else {
-        scores_mma(acc, f0);
-    }
-    // C/D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-    const bool interior = i0 + 64 <= Q && j0 + 64 <= N;
-    if (metric != WV_METRIC_IP) scores_store<true>(acc, S, qn, dbn, i0, j0, Q, N, r, h, interior);
-    else scores_store<false>(acc, S, qn, dbn, i0, j0, Q, N, r, h, interior);
-}
-
-// The same tile with the operands shared through LDS: a 128 x 128 workgroup tile needs 4 + 4 row blocks per chunk, but the
-// four waves of k_scores fetch 2 + 2 each -- every fragment twice, 0.0625 B/flop from L2.  Here wave w fetches block w of
-// A and of B for a stage of four chunks (8 coalesced 1 KB loads, kept in registers while the previous stage computes),
-// stores them to one half of a double-buffered LDS ring, and every wave reads its 2 + 2 blocks back as ds_read_b128
-// (lane-contiguous: conflict-free).  One barrier per stage of 64 MFMAs.
-#ifndef WV_SC_STAGE
-#define WV_SC_STAGE 4
-#endif
-#ifndef WV_SC_WAVES
-#define WV_SC_WAVES 2
-#endif
-constexpr int kScStage = WV_SC_STAGE;                          // chunks of 8 k-values per stage
+// 128 x 128 score tile per workgroup, wave (wv >> 1, wv & 1) owns a 64 x 64 quadrant, the operands shared through LDS: the
+// tile needs 4 + 4 row blocks per chunk, and four waves fetching their own 2 + 2 each would read every fragment twice
+// (0.0625 B/flop from L2).  Here wave w fetches block w of A and of B for a stage of four chunks (8 coalesced 1 KB loads,
+// kept in registers while the previous stage computes), stores them to one half of a double-buffered LDS ring, and every
+// wave reads its 2 + 2 blocks back as ds_read_b128 (lane-contiguous: conflict-free).  One barrier per stage of 64 MFMAs.
+constexpr int kScStage = 4;                                    // chunks of 8 k-values per stage
+constexpr int kScWaves = 2;                                    // waves per SIMD the register budget is set for
 constexpr int kScStageF4 = 2 * 4 * kScStage * 64;              // float4 per stage: (A, B) x 4 blocks x chunks x lanes
 
-__global__ __launch_bounds__(256, WV_SC_WAVES) void k_scores_lds(const float4 *__restrict__ qf, const float4 *__restrict__ dbf,
+__global__ __launch_bounds__(256, kScWaves) void k_scores_lds(const float4 *__restrict__ qf, const float4 *__restrict__ dbf,
                                                        const float *__restrict__ qn, const float *__restrict__ dbn,
                                                        float *__restrict__ S, int Q, int64_t N, int nchunk, int metric)
 {
@@ -228,20 +168,14 @@ __global__ __launch_bounds__(256, WV_SC_WAVES) void k_scores_lds(const float4 *_
     const float4 *ra = ring + (2 * wa * kScStage) * 64 + lane;
     const float4 *rb = ring + (4 * kScStage + 2 * wb * kScStage) * 64 + lane;
     // (named registers, not arrays: carried around the loop, arrays of float4 were promoted to LDS / scratch by the compiler)
-    static_assert(kScStage == 4 || kScStage == 2, "the staging registers below are written out for two or four chunks");
+    static_assert(kScStage == 4, "the staging registers below are written out for four chunks");
     float4 pa0, pa1, pa2, pa3, pb0, pb1, pb2, pb3;
-#if WV_SC_STAGE == 4
 #define WV_SC_FETCH(OFF)                                                                                        \
     pa0 = ga[(OFF)]; pb0 = gb[(OFF)]; pa1 = ga[(OFF) + 64]; pb1 = gb[(OFF) + 64];                               \
     pa2 = ga[(OFF) + 128]; pb2 = gb[(OFF) + 128]; pa3 = ga[(OFF) + 192]; pb3 = gb[(OFF) + 192];
 #define WV_SC_STASH(DA, DB)                                                                                     \
     (DA)[0] = pa0; (DB)[0] = pb0; (DA)[64] = pa1; (DB)[64] = pb1;                                               \
     (DA)[128] = pa2; (DB)[128] = pb2; (DA)[192] = pa3; (DB)[192] = pb3;
-#else
-#define WV_SC_FETCH(OFF) pa0 = ga[(OFF)]; pb0 = gb[(OFF)]; pa1 = ga[(OFF) + 64]; pb1 = gb[(OFF) + 64];
-#define WV_SC_STASH(DA, DB) (DA)[0] = pa0; (DB)[0] = pb0; (DA)[64] = pa1; (DB)[64] = pb1;
-    (void)pa2; (void)pa3; (void)pb2; (void)pb3;
-#endif
     const int nstage = nchunk / kScStage;
     WV_SC_FETCH((int64_t)0)
     WV_SC_STASH(la, lb)
@@ -301,20 +235,6 @@ __global__ __launch_bounds__(256, WV_SC_WAVES) void k_scores_lds(const float4 *_
     const bool interior = i0 + 64 <= Q && j0 + 64 <= N;
     if (metric != WV_METRIC_IP) scores_store<true>(acc, S, qn, dbn, i0, j0, Q, N, r, h, interior);
     else scores_store<false>(acc, S, qn, dbn, i0, j0, Q, N, r, h, interior);
-}
-
-__device__ __forceinline__ uint32_t float_to_key(float v, bool descending)
-{
-    v += 0.0f;  // -0 -> +0
-    uint32_t u = __float_as_uint(v);
-    u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // ascending float order -> ascending unsigned
-    return descending ? ~u : u;
-}
-__device__ __forceinline__ float key_to_float(uint32_t u, bool descending)
-{
-    if (descending) u = ~u;
-    u ^= (u >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-    return __uint_as_float(u);
 }
 
 // One stable counting-sort pass over digit (key >> shift) & 63 of every row.
@@ -533,9 +453,10 @@ __global__ __launch_bounds__(kRadixThreads) void k_row_radix(const float *__rest
 }
 
 // ---- one kernel per row for k <= 15,360: the list is selected, sorted and written without leaving the CU ----------
-// k_select_compact + six k_radix_pass launches move every survivor through global memory seven times with scattered
-// 8-byte stores (0.87 ms of the 1.16 ms of a 2048 x 25,000, k = 5000 search), and the selection's 11-bit histograms
-// of raw key bits pile a whole row onto the few bins of its sign / exponent.  Here the digit is a VALUE bin instead:
+// The radix ranking (k_row_radix above: selection + six passes) moves every survivor through global memory seven times
+// with scattered 8-byte stores (0.87 ms of the 1.16 ms of a 2048 x 25,000, k = 5000 search when each pass was a launch of
+// its own), and the selection's 11-bit histograms of raw key bits pile a whole row onto the few bins of its sign /
+// exponent.  Here the digit is a VALUE bin instead:
 //   bin(w) = clamp(floor(64 + (w - lo) * 3968 / (hi - lo)), 0, 4095),   w = the score in ascending rank order
 //   (v for L2, -v for IP), [lo, hi] = min / max of a strided 4096-item sample of the row.
 // Every step of bin() is monotone non-decreasing under IEEE rounding, so bin(x) < bin(y) implies x < y and equal
@@ -545,17 +466,14 @@ __global__ __launch_bounds__(kRadixThreads) void k_row_radix(const float *__rest
 // (key, index) pairs -- a handful for smooth scores -- which is its final rank; the list is permuted in place and
 // its first k entries leave as two coalesced streams.  Rows this cannot take (a bin holding more than 512
 // survivors, NaNs, a boundary bin that overflows the list: ties en masse, constant rows) set todo[row] and the radix
-// kernels above rank exactly those rows; they return at once for all others.
+// kernel above ranks exactly those rows; its workgroups return at once for all others.
 constexpr int kTkThreads = 1024;
 constexpr int kTkBins = 4096;
 constexpr int kTkSlack = 1024;        // list entries beyond k for the rest of the boundary bin
 constexpr int kTkCapMax = 16384;      // 16 entries per thread are held in registers across the in-place permutation
 constexpr int kTkGroupMax = 512;
 constexpr int kTkSample = 4096;
-#ifndef WV_TK_UNROLL
-#define WV_TK_UNROLL 8
-#endif
-constexpr int kTkUnroll = WV_TK_UNROLL;
+constexpr int kTkUnroll = 8;          // scores a thread has in flight per trip of the two row walks
 
 __device__ __forceinline__ float tk_order_value(float v, bool descending)
 {
@@ -657,13 +575,6 @@ __global__ __launch_bounds__(kTkThreads, (JMAX <= 8 ? 8 : 4)) void k_row_topk(co
     const int64_t row = blockIdx.x;
     const float *Srow = S + row * N;
     const bool desc = descending != 0;
-#ifdef WV_TK_STOPS   // phase timing by truncation (tools/knn_phases.py): the kernel ends after phase force_radix >> 8
-    const int stop_at = force_radix >> 8;
-    force_radix &= 0xff;
-#define TK_STOP(n) if (stop_at == (n)) return
-#else
-#define TK_STOP(n)
-#endif
 
     // range of the row from a sample: 64 runs of 64 consecutive scores spread over the row (the whole row if short)
     float mn = __builtin_inff(), mx = -__builtin_inff();
@@ -698,13 +609,11 @@ __global__ __launch_bounds__(kTkThreads, (JMAX <= 8 ? 8 : 4)) void k_row_topk(co
     }
     float scale = (float)(kTkBins - 128) / (hi - lo);
     if (!(scale > 0.f)) scale = 0.f;                 // constant sample, infinite range, NaN: everything in one bin
-    TK_STOP(1);
 
     // pass 1: value-bin histogram and the bin b* of the k-th item; one second attempt with a range taken from the first
     // histogram when outliers made the sampled range too coarse (tk_histogram)
     constexpr int UNR = kTkUnroll;
     bool fits = tk_histogram<false>(Srow, N, k, cap, desc, lo, scale, cursor, wpart, sel);
-    TK_STOP(2);
     if (sel[TK_NAN_SEEN] || force_radix || (!fits && !(scale > 0.f))) {
         if (tid == 0) todo[row] = 1;
         return;
@@ -731,7 +640,6 @@ __global__ __launch_bounds__(kTkThreads, (JMAX <= 8 ? 8 : 4)) void k_row_topk(co
     const int bstar = (int)sel[TK_BSTAR];
     const uint32_t n_tot = sel[TK_BEFORE] + sel[TK_COUNT];
     if (tid == 0) todo[row] = 0;
-    TK_STOP(3);
 
     // pass 2: every item of a bin <= b* takes the next slot of its bin; afterwards cursor[b] is the END of bin b, i.e. the
     // start of bin b + 1
@@ -753,7 +661,6 @@ __global__ __launch_bounds__(kTkThreads, (JMAX <= 8 ? 8 : 4)) void k_row_topk(co
         }
     }
     __syncthreads();
-    TK_STOP(4);
 
     // rank inside the bin = number of (key, index) pairs of the same bin that come first (four per trip: the reads of a
     // trip are independent, a lane's neighbours are in the same bin and read the same addresses)
@@ -778,7 +685,6 @@ __global__ __launch_bounds__(kTkThreads, (JMAX <= 8 ? 8 : 4)) void k_row_topk(co
         }
     }
     __syncthreads();
-    TK_STOP(5);
 #pragma unroll
     for (int j = 0; j < JMAX; ++j)
         if (pos[j] != 0xffffffffu) A[pos[j]] = item[j];
@@ -807,32 +713,55 @@ static int launch_row_topk(const float *S, int64_t N, int k, int cap, int descen
     return WV_OK;
 }
 
+// What a call decides once about its ranking stage, for every chunk of rows.
+struct RankPlan {
+    int64_t N;
+    int k, descending, sqrt_out;
+    int C, Ck;                     // items per thread of the radix passes over N and over k items
+    uint32_t c_magic, ck_magic;    // pos / C, pos / Ck as a multiply-high
+    int select_first;              // radix kernel: select the k best before sorting (2k <= N), else sort the whole row
+    int cap;                       // entries of k_row_topk's LDS list
+    int force_radix;               // 1: k_row_topk hands every row over (WV_KNN_FORCE_TODO, diagnostic library)
+    decltype(&launch_row_topk<2>) row_topk;   // the instantiation for cap / 1024 entries per thread (up to 2, 4, 8, 16);
+                                              // null (k > 15,360, WV_KNN_RADIX_ONLY): the radix kernel ranks every row
+};
+
+static uint32_t div_magic(int d) { return d <= 1 ? 0u : (uint32_t)(((1ull << 32) + d - 1) / d); }   // exact for pos < 2^32 / d
+
+static RankPlan rank_plan(int64_t N, int k, int descending, int sqrt_out)
+{
+    RankPlan p{};
+    p.N = N;
+    p.k = k;
+    p.descending = descending;
+    p.sqrt_out = sqrt_out;
+    p.C = (int)ceil_div(N, kRadixThreads);
+    p.Ck = (int)ceil_div(k, kRadixThreads);
+    p.c_magic = div_magic(p.C);
+    p.ck_magic = div_magic(p.Ck);
+    p.select_first = (int64_t)k * 2 <= N;
+    if (k + kTkSlack <= kTkCapMax && !::wv::tune("WV_KNN_RADIX_ONLY")) {
+        p.cap = (int)std::min<int64_t>(kTkCapMax, align_up(k + kTkSlack, kTkThreads));
+        p.force_radix = ::wv::tune("WV_KNN_FORCE_TODO") ? 1 : 0;
+        const int J = p.cap / kTkThreads;
+        p.row_topk = J <= 2 ? launch_row_topk<2> : J <= 4 ? launch_row_topk<4> : J <= 8 ? launch_row_topk<8> : launch_row_topk<16>;
+    }
+    return p;
+}
+
 // The ranking stage: the k best of every row of S [qc][N] in ascending (key, column) order.  Rows the one-kernel ranking takes
 // never reach the radix kernel (its workgroups return at once on todo[row] == 0).
-static int rank_rows(const float *S, int qc, int64_t N, int k, int descending, int sqrt_out, int32_t *idx, float *val,
-                     uint8_t *todo_buf, uint2 *bufA, uint2 *bufB, hipStream_t st)
+static int rank_rows(const RankPlan &p, const float *S, int qc, int32_t *idx, float *val, uint8_t *todo_buf, uint2 *bufA,
+                     uint2 *bufB, hipStream_t st)
 {
-    const int C = (int)ceil_div(N, kRadixThreads);
-    const uint32_t c_magic = C <= 1 ? 0u : (uint32_t)(((1ull << 32) + C - 1) / C);   // exact for pos < 2^32 / C
     const uint8_t *todo = nullptr;
-    if (k + kTkSlack <= kTkCapMax && !::wv::tune("WV_KNN_RADIX_ONLY")) {
-        const int cap = (int)std::min<int64_t>(kTkCapMax, align_up(k + kTkSlack, kTkThreads));
-        int force = ::wv::tune("WV_KNN_FORCE_TODO") ? 1 : 0;   // diagnostic build: every row takes both kernels' hand-over
-        if (const char *stop = ::wv::tune("WV_TK_STOP")) force |= atoi(stop) << 8;
-        const int J = cap / kTkThreads;
-        int rc;
-        if (J <= 2) rc = launch_row_topk<2>(S, N, k, cap, descending, idx, val, todo_buf, force, sqrt_out, qc, st);
-        else if (J <= 4) rc = launch_row_topk<4>(S, N, k, cap, descending, idx, val, todo_buf, force, sqrt_out, qc, st);
-        else if (J <= 8) rc = launch_row_topk<8>(S, N, k, cap, descending, idx, val, todo_buf, force, sqrt_out, qc, st);
-        else rc = launch_row_topk<16>(S, N, k, cap, descending, idx, val, todo_buf, force, sqrt_out, qc, st);
+    if (p.row_topk) {
+        const int rc = p.row_topk(S, p.N, p.k, p.cap, p.descending, idx, val, todo_buf, p.force_radix, p.sqrt_out, qc, st);
         if (rc != WV_OK) return rc;
         todo = todo_buf;
     }
-    const int select_first = (int64_t)k * 2 <= N && !::wv::tune("WV_KNN_FULLSORT");
-    const int Ck = (int)ceil_div(k, kRadixThreads);
-    const uint32_t ck_magic = Ck <= 1 ? 0u : (uint32_t)(((1ull << 32) + Ck - 1) / Ck);
-    hipLaunchKernelGGL(k_row_radix, dim3(qc), dim3(kRadixThreads), 0, st, S, bufA, bufB, N, C, c_magic, k, Ck, ck_magic,
-                       select_first, descending, sqrt_out, idx, val, todo);
+    hipLaunchKernelGGL(k_row_radix, dim3(qc), dim3(kRadixThreads), 0, st, S, bufA, bufB, p.N, p.C, p.c_magic, p.k, p.Ck,
+                       p.ck_magic, p.select_first, p.descending, p.sqrt_out, idx, val, todo);
     return WV_OK;
 }
 
@@ -852,6 +781,49 @@ static int64_t knn_chunk_rows(int Q, int64_t N)
     return std::min<int64_t>(rows, Q);
 }
 
+// The workspace of both entry points: what *_workspace_bytes reports (end) and what the entry points carve are this one
+// table.  Byte offsets, every buffer 256-byte aligned.  scores = false (wv_rank_scores: the caller made the scores) leaves
+// the ranking buffers only; the others are empty.
+struct KnnLayout {
+    int64_t rows;      // query rows per chunk (per launch sequence)
+    int64_t pitch;     // padded row length of the radix images
+    int nchunk;        // chunks of 8 k-values of a fragment image, whole stages (zero-padded)
+    int64_t S;         // float [rows][N]               scores of a chunk
+    int64_t bufA;      // uint2 [rows][pitch]           radix images (key, index), ping
+    int64_t bufB;      //                               ... pong
+    int64_t qn;        // float [Q]                     |q|^2 of every query (L2 metrics)
+    int64_t dbn;       // float [N]                     |db|^2
+    int64_t todo;      // uint8 [rows]                  1 = k_row_topk left the row to the radix kernel
+    int64_t qf;        // float4 fragment image of a chunk's queries, padded to whole 128-row tiles
+    int64_t dbf;       // ... of the database
+    int64_t end;
+};
+
+static KnnLayout knn_layout(int Q, int64_t N, int D, bool scores)
+{
+    KnnLayout L{};
+    if (Q <= 0 || N <= 0) return L;
+    L.rows = scores ? knn_chunk_rows(Q, N) : rank_chunk_rows(Q, N);
+    L.pitch = ceil_div(N, kRadixThreads) * kRadixThreads;
+    L.nchunk = scores ? (int)align_up(ceil_div(std::max(D, 0), 8), kScStage) : 0;
+    int64_t at = 0;
+    auto take = [&at](int64_t bytes) {
+        const int64_t off = at;
+        at += align_up(bytes, 256);
+        return off;
+    };
+    L.S = take(scores ? L.rows * N * 4 : 0);
+    L.bufA = take(L.rows * L.pitch * 8);
+    L.bufB = take(L.rows * L.pitch * 8);
+    L.qn = take(scores ? align_up(Q, 64) * 4 : 0);
+    L.dbn = take(scores ? align_up(N, 64) * 4 : 0);
+    L.todo = take(L.rows);
+    L.qf = take(align_up(L.rows, 128) * L.nchunk * 32);   // bytes: rows * nchunk * 8 floats
+    L.dbf = take(align_up(N, 128) * L.nchunk * 32);
+    L.end = at;
+    return L;
+}
+
 }  // namespace wv
 
 using namespace wv;
@@ -859,42 +831,27 @@ using namespace wv;
 extern "C" size_t wv_knn_float_workspace_bytes(int Q, int64_t N, int D, int k)
 {
     (void)k;
-    if (Q <= 0 || N <= 0) return 0;
-    const int64_t rows = knn_chunk_rows(Q, N);
-    const int64_t pitch = ceil_div(N, kRadixThreads) * kRadixThreads;
-    return (size_t)(rows * (N * 4 + pitch * 16) + (align_up(Q, 64) + align_up(N, 64)) * 4 + align_up(rows, 256) +
-                    (align_up(rows, 128) + align_up(N, 128)) * align_up(D, 8 * kScStage) * 4 + 1024);
+    return (size_t)knn_layout(Q, N, D, true).end;
 }
 
 extern "C" int wv_knn_float(const float *q, const float *db, int Q, int64_t N, int D, int metric, int k,
                             int32_t *idx, float *val, void *workspace, size_t workspace_bytes,
                             void *stream)
 {
-    WV_REQUIRE(q && db && idx && val, "knn_float: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1 && D >= 1, "knn_float: bad shape Q=%d N=%lld D=%d", Q, (long long)N, D);
-    WV_REQUIRE(metric == WV_METRIC_IP || metric == WV_METRIC_L2 || metric == WV_METRIC_L2_SQUARED, "knn_float: metric %d",
-               metric);
-    WV_REQUIRE(k >= 1 && k <= N, "knn_float: k=%d must be in [1, N=%lld] (torch.topk raises too)", k,
-               (long long)N);
-    WV_REQUIRE(N <= (1ll << 26), "knn_float: N=%lld above the supported 2^26 rows", (long long)N);
-    const size_t need = wv_knn_float_workspace_bytes(Q, N, D, k);
-    if (!workspace || workspace_bytes < need)
-        WV_FAIL(WV_ENOMEM, "knn_float: workspace %zu < %zu bytes", workspace_bytes, need);
+    const int refused = knn_float_args("knn_float", q && db && idx && val, Q, N, D, metric, k);
+    if (refused != WV_OK) return refused;
+    const KnnLayout L = knn_layout(Q, N, D, true);
+    if (!workspace || workspace_bytes < (size_t)L.end)
+        WV_FAIL(WV_ENOMEM, "knn_float: workspace %zu < %zu bytes", workspace_bytes, (size_t)L.end);
     if (Q == 0) return WV_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t rows = knn_chunk_rows(Q, N);
     char *w = (char *)workspace;
-    const int64_t pitch = ceil_div(N, kRadixThreads) * kRadixThreads;
-    float *S = (float *)w;                 w += align_up(rows * N * 4, 256);
-    uint2 *bufA = (uint2 *)w;              w += rows * pitch * 8;
-    uint2 *bufB = (uint2 *)w;              w += rows * pitch * 8;
-    float *qn = (float *)w;                w += align_up(Q, 64) * 4;
-    float *dbn = (float *)w;               w += align_up(N, 64) * 4;
-    uint8_t *todo_buf = (uint8_t *)w;      w += align_up(rows, 256);   // [rows] 1 = k_row_topk left the row to the radix kernel
-    const int nchunk = (int)align_up(ceil_div(D, 8), kScStage);   // chunks of 8 k-values, whole stages (zero-padded)
-    // fragment images, padded to whole 128-row tiles: the database once, the queries of a chunk per chunk
-    float4 *qf = (float4 *)w;              w += align_up(rows, 128) * nchunk * 32;   // bytes: rows * nchunk * 8 floats
-    float4 *dbf = (float4 *)w;
+    float *S = (float *)(w + L.S), *qn = (float *)(w + L.qn), *dbn = (float *)(w + L.dbn);
+    uint2 *bufA = (uint2 *)(w + L.bufA), *bufB = (uint2 *)(w + L.bufB);
+    uint8_t *todo_buf = (uint8_t *)(w + L.todo);
+    float4 *qf = (float4 *)(w + L.qf), *dbf = (float4 *)(w + L.dbf);
+    const int nchunk = L.nchunk;
+    // fragment images: the database once, the queries of a chunk per chunk
     {
         const int64_t tn = align_up(N, 128) / 32 * nchunk * 64;
         hipLaunchKernelGGL(k_pack_fragments, dim3((unsigned)ceil_div(tn, 256)), dim3(256), 0, st, db, dbf, N, D, nchunk, tn);
@@ -903,20 +860,17 @@ extern "C" int wv_knn_float(const float *q, const float *db, int Q, int64_t N, i
         hipLaunchKernelGGL(k_row_sqnorm, dim3((unsigned)ceil_div(Q, 4)), dim3(256), 0, st, q, (int64_t)Q, D, qn);
         hipLaunchKernelGGL(k_row_sqnorm, dim3((unsigned)ceil_div(N, 4)), dim3(256), 0, st, db, N, D, dbn);
     }
-    const int descending = metric == WV_METRIC_IP;
-    const int sqrt_out = metric == WV_METRIC_L2;   // L2 rows are ranked on SQUARED distances (what faiss ranks on; the same
-                                                   // order up to ties the rounding of the root creates); the k results get the root
-    for (int64_t q0 = 0; q0 < Q; q0 += rows) {
-        const int qc = (int)std::min<int64_t>(rows, Q - q0);
+    // L2 rows are ranked on SQUARED distances (what faiss ranks on; the same order up to ties the rounding of the root
+    // creates); the k results get the root
+    const RankPlan plan = rank_plan(N, k, metric == WV_METRIC_IP, metric == WV_METRIC_L2);
+    for (int64_t q0 = 0; q0 < Q; q0 += L.rows) {
+        const int qc = (int)std::min<int64_t>(L.rows, Q - q0);
         dim3 grid((unsigned)ceil_div(N, 128), (unsigned)ceil_div(qc, 128));
         const int64_t tq = align_up(qc, 128) / 32 * nchunk * 64;
         hipLaunchKernelGGL(k_pack_fragments, dim3((unsigned)ceil_div(tq, 256)), dim3(256), 0, st, q + q0 * D, qf, (int64_t)qc, D,
                            nchunk, tq);
-        if (::wv::tune("WV_KNN_SCORES_DIRECT"))
-            hipLaunchKernelGGL(k_scores, grid, dim3(256), 0, st, qf, dbf, qn + q0, dbn, S, qc, N, nchunk, metric);
-        else
-            hipLaunchKernelGGL(k_scores_lds, grid, dim3(256), 0, st, qf, dbf, qn + q0, dbn, S, qc, N, nchunk, metric);
-        const int rc = rank_rows(S, qc, N, k, descending, sqrt_out, idx + q0 * k, val + q0 * k, todo_buf, bufA, bufB, st);
+        hipLaunchKernelGGL(k_scores_lds, grid, dim3(256), 0, st, qf, dbf, qn + q0, dbn, S, qc, N, nchunk, metric);
+        const int rc = rank_rows(plan, S, qc, idx + q0 * k, val + q0 * k, todo_buf, bufA, bufB, st);
         if (rc != WV_OK) return rc;
     }
     WV_CHECK_LAUNCH("knn_float");
@@ -926,32 +880,24 @@ extern "C" int wv_knn_float(const float *q, const float *db, int Q, int64_t N, i
 extern "C" size_t wv_rank_scores_workspace_bytes(int Q, int64_t N, int k)
 {
     (void)k;
-    if (Q <= 0 || N <= 0) return 0;
-    const int64_t rows = rank_chunk_rows(Q, N);
-    return (size_t)(rows * ceil_div(N, kRadixThreads) * kRadixThreads * 16 + align_up(rows, 256) + 256);
+    return (size_t)knn_layout(Q, N, 0, false).end;
 }
 
 extern "C" int wv_rank_scores(const float *S, int Q, int64_t N, int k, int flags, int32_t *idx, float *val, void *workspace,
                               size_t workspace_bytes, void *stream)
 {
-    WV_REQUIRE(S && idx && val, "rank_scores: null buffer");
-    WV_REQUIRE(Q >= 0 && N >= 1, "rank_scores: bad shape Q=%d N=%lld", Q, (long long)N);
-    WV_REQUIRE(k >= 1 && k <= N, "rank_scores: k=%d must be in [1, N=%lld]", k, (long long)N);
-    WV_REQUIRE(N <= (1ll << 26), "rank_scores: N=%lld above the supported 2^26 columns", (long long)N);
-    WV_REQUIRE((flags & ~(WV_RANK_DESCENDING | WV_RANK_SQRT)) == 0, "rank_scores: flags %d", flags);
-    const size_t need = wv_rank_scores_workspace_bytes(Q, N, k);
-    if (!workspace || workspace_bytes < need)
-        WV_FAIL(WV_ENOMEM, "rank_scores: workspace %zu < %zu bytes", workspace_bytes, need);
+    const int refused = rank_scores_args("rank_scores", S && idx && val, Q, N, k, flags);
+    if (refused != WV_OK) return refused;
+    const KnnLayout L = knn_layout(Q, N, 0, false);
+    if (!workspace || workspace_bytes < (size_t)L.end)
+        WV_FAIL(WV_ENOMEM, "rank_scores: workspace %zu < %zu bytes", workspace_bytes, (size_t)L.end);
     if (Q == 0) return WV_OK;
-    const int64_t rows = rank_chunk_rows(Q, N), pitch = ceil_div(N, kRadixThreads) * kRadixThreads;
     char *w = (char *)workspace;
-    uint2 *bufA = (uint2 *)w;              w += rows * pitch * 8;
-    uint2 *bufB = (uint2 *)w;              w += rows * pitch * 8;
-    uint8_t *todo_buf = (uint8_t *)w;
-    for (int64_t q0 = 0; q0 < Q; q0 += rows) {
-        const int qc = (int)std::min<int64_t>(rows, Q - q0);
-        const int rc = rank_rows(S + q0 * N, qc, N, k, (flags & WV_RANK_DESCENDING) != 0, (flags & WV_RANK_SQRT) != 0, idx + q0 * k,
-                                 val + q0 * k, todo_buf, bufA, bufB, (hipStream_t)stream);
+    const RankPlan plan = rank_plan(N, k, (flags & WV_RANK_DESCENDING) != 0, (flags & WV_RANK_SQRT) != 0);
+    for (int64_t q0 = 0; q0 < Q; q0 += L.rows) {
+        const int qc = (int)std::min<int64_t>(L.rows, Q - q0);
+        const int rc = rank_rows(plan, S + q0 * N, qc, idx + q0 * k, val + q0 * k, (uint8_t *)(w + L.todo), (uint2 *)(w + L.bufA),
+                                 (uint2 *)(w + L.bufB), (hipStream_t)stream);
         if (rc != WV_OK) return rc;
     }
     WV_CHECK_LAUNCH("rank_scores");

@@ -1,7 +1,9 @@
 """wv_knn_float's one-kernel ranking (k_row_topk: value bins -> LDS list -> in-bin ranks) against the radix kernel it
-replaces for k <= 15,360 and against the stable oracle.  Both rank the SAME fp32 score matrix (k_scores), so indices
+replaces for k <= 15,360 and against the stable oracle.  Both rank the SAME fp32 score matrix (k_scores_lds), so indices
 and values must be equal bit for bit -- ascending (key, index), ties by ascending index (get_knn.py:60-71 semantics:
 torch.topk's order inside a tie is implementation-defined; ours is the stable one)."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -91,9 +93,10 @@ def test_row_topk_against_the_stable_oracle(metric, name):
 
 @pytest.mark.parametrize("D", [1, 3, 4, 7, 12, 16, 20, 36, 52, 70, 100, 384])
 def test_scores_are_exact_for_every_tail_of_the_k_loop(D):
-    """k_scores walks k in chunks of 16 with a two-stage register pipeline; the last chunk may hold 4, 8 or 12 values.
-    Integer-valued embeddings: every product and partial sum is exact in fp32, whatever the summation order, so the
-    sorted scores must equal torch's exactly -- on edge tiles too (Q, N not multiples of 64)."""
+    """k_scores_lds walks k in stages of four chunks of 8 values read from zero-padded fragment images: D may end
+    anywhere inside a float4, a chunk or a stage, and D = 384 takes twelve stages through the LDS ring.  Integer-valued
+    embeddings: every product and partial sum is exact in fp32, whatever the summation order, so the sorted scores must
+    equal torch's exactly -- on edge tiles too (Q, N not multiples of 64)."""
     g = torch.Generator().manual_seed(D)
     Q, N = 130, 333
     q = torch.randint(-3, 4, (Q, D), generator=g).float()
@@ -167,6 +170,74 @@ def test_rank_scores_is_the_stable_order_of_a_given_matrix(Q, N, k, flags):
     assert torch.equal(v.cpu(), want.sqrt() if root else want) or torch.allclose(v.cpu(), want.sqrt(), rtol=3e-7, atol=0)
     vh, ih = rank_scores(s, k, descending=desc, sqrt=root)
     assert torch.equal(ih, i.cpu()) and torch.equal(vh.view(torch.int32), v.cpu().view(torch.int32))
+
+
+GUARD = 1 << 20
+
+
+def _guarded_workspace(need):
+    """`need` bytes at the front of a larger byte tensor; the rest, 1 MiB, holds 0xA5."""
+    return torch.full((need + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+
+
+@pytest.mark.parametrize("metric", [IP, L2, _lib.WV_METRIC_L2_SQUARED])
+def test_knn_float_keeps_to_the_workspace_size_it_reports(metric):
+    """wv_knn_float through ctypes with workspace_bytes exactly as wv_knn_float_workspace_bytes reports: edge tiles in both
+    directions (130 x 333), a ragged D, k = N.  The lists of the normal wrapper bit for bit, and not one byte written behind
+    the reported size."""
+    lib = _lib.require_gpu()
+    Q, N, D, k = 130, 333, 7, 333
+    q, r = _pair(Q, N, D, 21)
+    v0, i0 = knn_float(r, q, k, metric)
+    need = lib.wv_knn_float_workspace_bytes(Q, N, D, k)
+    ws = _guarded_workspace(need)
+    idx = torch.empty((Q, k), dtype=torch.int32, device="cuda")
+    val = torch.empty((Q, k), dtype=torch.float32, device="cuda")
+    rc = lib.wv_knn_float(_lib.ptr(q), _lib.ptr(r), Q, N, D, metric, k, _lib.ptr(idx), _lib.ptr(val), _lib.ptr(ws),
+                          ctypes.c_size_t(need), _lib.stream_ptr())
+    assert rc == 0, lib.wv_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(idx, i0) and torch.equal(val.view(torch.int32), v0.view(torch.int32))
+    assert bool((ws[need:] == 0xA5).all())
+
+
+def test_rank_scores_keeps_to_the_workspace_size_it_reports():
+    from wvhash.engine.get_knn import rank_scores
+    lib = _lib.require_gpu()
+    Q, N, k = 9, 70, 70
+    g = torch.Generator().manual_seed(70)
+    s = ((torch.randn(Q, N, generator=g) * 8).round() / 8).cuda()
+    v0, i0 = rank_scores(s, k)
+    need = lib.wv_rank_scores_workspace_bytes(Q, N, k)
+    ws = _guarded_workspace(need)
+    idx = torch.empty((Q, k), dtype=torch.int32, device="cuda")
+    val = torch.empty((Q, k), dtype=torch.float32, device="cuda")
+    rc = lib.wv_rank_scores(_lib.ptr(s), Q, N, k, 0, _lib.ptr(idx), _lib.ptr(val), _lib.ptr(ws), ctypes.c_size_t(need),
+                            _lib.stream_ptr())
+    assert rc == 0, lib.wv_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(idx, i0) and torch.equal(val.view(torch.int32), v0.view(torch.int32))
+    assert bool((ws[need:] == 0xA5).all())
+
+
+def test_rank_scores_over_two_chunks_of_rows():
+    """1,000,000 columns: the radix images of 67 rows fill wv_rank_scores' 1 GiB, so 70 rows are ranked as 67 + 3.  Scores in
+    eighths (ties across the k-th position): the host twin's lists bit for bit, and the second chunk's rows as a call on those
+    three rows alone ranks them."""
+    from wvhash.engine.get_knn import rank_scores
+    lib = _lib.require_gpu()
+    Q, N, k = 70, 1_000_000, 50
+    pitch = (N + 255) // 256 * 256
+    assert 67 * pitch * 16 <= 1 << 30 < 68 * pitch * 16
+    assert lib.wv_rank_scores_workspace_bytes(Q, N, k) < 68 * pitch * 16          # fewer than 68 rows per chunk
+    g = torch.Generator().manual_seed(67)
+    s = (torch.randn(Q, N, generator=g) * 8).round() / 8
+    sg = s.cuda()
+    v, i = rank_scores(sg, k)
+    vh, ih = rank_scores(s, k)
+    assert torch.equal(i.cpu(), ih) and torch.equal(v.cpu().view(torch.int32), vh.view(torch.int32))
+    v3, i3 = rank_scores(sg[67:], k)
+    assert torch.equal(i[67:], i3) and torch.equal(v[67:].view(torch.int32), v3.view(torch.int32))
 
 
 def test_shard_lists_merge_to_the_unsharded_search():

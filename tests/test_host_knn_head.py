@@ -55,6 +55,61 @@ def test_knn_float_cpu_random_embeddings_and_errors():
     assert lib.wv_knn_float_cpu(_lib.ptr(x), _lib.ptr(x), 2, 2, 8, 7, 1, _lib.ptr(out_i), _lib.ptr(out_v)) == -22   # metric
 
 
+def _why(lib):
+    """The refusal's text without the entry point's name in front."""
+    return lib.wv_last_error().split(b": ", 1)[1]
+
+
+def test_device_entry_points_and_twins_refuse_the_same_arguments():
+    """wv_knn_float / wv_rank_scores and their _cpu twins answer from one set of rules (csrc/knn_args.hpp) before any HIP call
+    and before any pointer is read: dummy non-null pointers, no GPU.  Same code, same text after the entry point's name."""
+    import ctypes
+    lib = _lib.load()
+    p, ws = ctypes.c_void_p(4096), ctypes.c_size_t(1 << 40)
+    big = (1 << 26) + 1
+    #            Q  N    D  metric k  buffers
+    knn_cases = [(2, 5, 8, 0, 0, p),          # k = 0
+                 (2, 5, 8, 0, 6, p),          # k > N
+                 (2, 0, 8, 0, 1, p),          # N = 0
+                 (2, 5, 0, 0, 1, p),          # D = 0
+                 (2, 5, 8, 7, 1, p),          # metric 7
+                 (2, big, 8, 0, 1, p),        # N = 2^26 + 1
+                 (2, 5, 8, 0, 1, None)]       # a null buffer
+    for Q, N, D, metric, k, buf in knn_cases:
+        assert lib.wv_knn_float(p, p, Q, N, D, metric, k, buf, p, p, ws, None) == -22, (Q, N, D, metric, k)
+        dev = _why(lib)
+        assert lib.wv_knn_float_cpu(p, p, Q, N, D, metric, k, buf, p) == -22, (Q, N, D, metric, k)
+        assert _why(lib) == dev
+    #             Q  N    k  flags buffers
+    rank_cases = [(2, 5, 0, 0, p), (2, 5, 6, 0, p), (2, 0, 1, 0, p), (2, big, 1, 0, p), (2, 5, 1, 4, p), (2, 5, 1, 0, None)]
+    for Q, N, k, flags, buf in rank_cases:
+        assert lib.wv_rank_scores(p, Q, N, k, flags, buf, p, p, ws, None) == -22, (Q, N, k, flags)
+        dev = _why(lib)
+        assert lib.wv_rank_scores_cpu(p, Q, N, k, flags, buf, p) == -22, (Q, N, k, flags)
+        assert _why(lib) == dev
+    assert lib.wv_knn_float(p, p, 2, 5, 8, 7, 1, p, p, p, ws, None) == -22 and b"metric" in lib.wv_last_error()
+
+
+def test_a_workspace_one_byte_short_is_refused():
+    """WV_ENOMEM from both device entry points for anything below what *_workspace_bytes reports (and for no workspace at
+    all), again before any HIP call; the reported sizes are whole 256-byte units."""
+    import ctypes
+    lib = _lib.load()
+    p = ctypes.c_void_p(4096)
+    for Q, N, D, k in [(130, 333, 7, 333), (1, 1, 1, 1), (40, 3_000_000, 4, 50)]:
+        need = lib.wv_knn_float_workspace_bytes(Q, N, D, k)
+        assert need > 0 and need % 256 == 0
+        for ws, n in ((p, need - 1), (p, 0), (None, need)):
+            assert lib.wv_knn_float(p, p, Q, N, D, 0, k, p, p, ws, ctypes.c_size_t(n), None) == -12
+            assert b"workspace" in lib.wv_last_error()
+    for Q, N, k in [(9, 70, 70), (1, 1, 1), (70, 1_000_000, 50)]:
+        need = lib.wv_rank_scores_workspace_bytes(Q, N, k)
+        assert need > 0 and need % 256 == 0
+        for ws, n in ((p, need - 1), (p, 0), (None, need)):
+            assert lib.wv_rank_scores(p, Q, N, k, 0, p, p, ws, ctypes.c_size_t(n), None) == -12
+            assert b"workspace" in lib.wv_last_error()
+
+
 def test_cpu_calculator_runs_float_metrics():
     """CustomCalculator(device='cpu') with real-valued embeddings: get_knn's cosine / l2 branches (get_knn.py:63-69) and the
     faiss flavour's squared distances through the host twin."""
