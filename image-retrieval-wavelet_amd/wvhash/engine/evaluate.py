@@ -242,11 +242,6 @@ def evaluate_multi_k(net, train_dataset=None, val_dataset=None, test_dataset=Non
 
 # ---------------------------------------------------------------------------------------------------------------
 # Sharded evaluation: one process per GPU (the c3 / c4 shape: COCO's 117k-image database over 8 GPUs)
-def _even_slice(n, world, rank):
-    per = (n + world - 1) // world
-    return min(n, rank * per), min(n, (rank + 1) * per), per
-
-
 @_preserve_rng
 def evaluate_sharded(net, test_dataset, k=5000, epoch=None, batch_size=64, num_workers=16, group=None, **kwargs):
     """Hashing retrieval metrics of ``{"test": queries, "gallery": database}`` with the work split over the ranks of
@@ -270,7 +265,7 @@ def evaluate_sharded(net, test_dataset, k=5000, epoch=None, batch_size=64, num_w
     Every rank's query slice is padded to a common length by repeating its last query; the copies are not counted."""
     import torch.distributed as dist
     from torch.utils.data import Subset
-    from ..parallel import sharded_hamming_topk, sharded_hamming_map_at_k, _all_gather, _all_reduce
+    from ..parallel import shard_bounds, sharded_hamming_topk, sharded_hamming_map_at_k, _all_gather, _all_reduce
     from . import hamming as H
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -284,8 +279,8 @@ def evaluate_sharded(net, test_dataset, k=5000, epoch=None, batch_size=64, num_w
     tester = get_tester(batch_size=batch_size, num_workers=num_workers, k=k_list[0], **kwargs)   # embeds; the metrics are below
     net.eval()
     n_db, n_q = len(test_dataset["gallery"]), len(test_dataset["test"])
-    lo, hi, _ = _even_slice(n_db, world, rank)
-    qlo, qhi, q_per = _even_slice(n_q, world, rank)
+    lo, hi, _ = shard_bounds(n_db, world, rank)
+    qlo, qhi, q_per = shard_bounds(n_q, world, rank)
 
     def embed(ds, a, b):
         if b <= a:
@@ -316,7 +311,7 @@ def evaluate_sharded(net, test_dataset, k=5000, epoch=None, batch_size=64, num_w
         qp, qlp = torch.cat([qp, filler_q]).contiguous(), torch.cat([qlp, filler_l]).contiguous()
     # ---- database shard + labels of the whole database
     rp = H.pack_codes(r_codes) if r_codes is not None else torch.zeros((0, words), dtype=torch.int64, device=dev)
-    per_db = _even_slice(n_db, world, 0)[2]
+    per_db = shard_bounds(n_db, world, 0)[2]
     rlp_local = torch.zeros((per_db, lw), dtype=torch.int64, device=dev)
     if r_codes is not None:
         rlp_local[:hi - lo] = H.pack_labels(r_lab.float())

@@ -157,56 +157,48 @@ def hamming_topk(q_packed, db, nbits, k, idx_offset=0, workspace=None, want_dist
     cum[q, b] = number of rows with distance < b]."""
     lib = _lib.require_gpu()
     Q, words = q_packed.shape
-    prepared = isinstance(db, PreparedDB)
-    N, dwords = (db.N, db.words) if prepared else db.shape
-    if dwords != words or words != _words(nbits):
-        raise ValueError("hamming_topk: code widths do not match nbits")
+    prepared, N = _shard_db_args(db, words, nbits, "hamming_topk")
     dev = q_packed.device
     if prepared and db.parts and not want_cum and nbits <= 128 and Q:
-        return _virtual_shards_topk(q_packed, db, nbits, k, idx_offset, want_dist)
+        got = _virtual_shards_topk(q_packed, db, nbits, k, idx_offset, want_dist)
+        if got is not None:                                 # None: a prefix beyond the windowed kernel's lists -- rank the whole database
+            return got
     idx = torch.empty((Q, k), dtype=torch.int32, device=dev)
     dist = torch.empty((Q, k), dtype=torch.uint8, device=dev) if want_dist else None
-    if want_cum:
-        cum = torch.empty((Q, nbits + 2), dtype=torch.int32, device=dev)
-        db_packed = db.packed if prepared else db
-        use_prep = prepared and words <= 2
-        ws = None
-        if not use_prep:
-            ws_bytes = lib.wv_hamming_topk_workspace_bytes(Q, N, words, k)
-            ws = (workspace or TopkWorkspace()).get(ws_bytes, dev)
-        with torch.cuda.device(dev):
-            rc = lib.wv_hamming_topk_ex(_lib.ptr(q_packed), _lib.ptr(db_packed), _lib.ptr(db.blob) if use_prep else None,
-                                        _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(cum), Q, N, nbits, k, idx_offset,
-                                        _lib.ptr(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0),
-                                        _lib.stream_ptr())
-            _lib.check(rc, "wv_hamming_topk_ex")
-        return idx, dist, cum
+    cum = torch.empty((Q, nbits + 2), dtype=torch.int32, device=dev) if want_cum else None
+    blob = db.blob if prepared and words <= 2 else None     # the ranking images exist for codes of <= 2 words
+    ws = None
+    if blob is None:                                        # the kernel's image of the database is made per call
+        ws = (workspace or TopkWorkspace()).get(lib.wv_hamming_topk_workspace_bytes(Q, N, words, k), dev)
     with torch.cuda.device(dev):
-        if prepared and words <= 2:
-            rc = lib.wv_hamming_topk_prepared(_lib.ptr(q_packed), _lib.ptr(db.blob), _lib.ptr(idx), _lib.ptr(dist),
-                                              Q, N, nbits, k, idx_offset, _lib.stream_ptr())
-        else:
-            db_packed = db.packed if prepared else db
-            ws_bytes = lib.wv_hamming_topk_workspace_bytes(Q, N, words, k)
-            ws = (workspace or TopkWorkspace()).get(ws_bytes, dev)
-            rc = lib.wv_hamming_topk(_lib.ptr(q_packed), _lib.ptr(db_packed), _lib.ptr(idx), _lib.ptr(dist), Q, N,
-                                     nbits, k, idx_offset, _lib.ptr(ws), ctypes.c_size_t(ws.numel()),
-                                     _lib.stream_ptr())
-        _lib.check(rc, "wv_hamming_topk")
-    return idx, dist
+        rc = lib.wv_hamming_topk_ex(_lib.ptr(q_packed), _lib.ptr(db.packed if prepared else db), _lib.ptr(blob), _lib.ptr(idx),
+                                    _lib.ptr(dist), _lib.ptr(cum), Q, N, nbits, k, idx_offset, _lib.ptr(ws),
+                                    ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_ptr())
+        _lib.check(rc, "wv_hamming_topk_ex")
+    return (idx, dist, cum) if want_cum else (idx, dist)
 
 
-def _prefix_need(cums, k):
-    """cums int32 [G, Q, nbits + 2] -> the longest list prefix any shard owes any query (host int): local rows with
-    distance <= T, T = the query's global k-th distance."""
-    G, Q, _ = cums.shape
-    T = (cums.sum(0)[:, 1:] >= k).int().argmax(dim=1)
-    return int(torch.gather(cums, 2, (T + 1).view(1, Q, 1).expand(G, Q, 1).long()).max().item())
+def owed_prefix(cum, cum_total, k):
+    """The prefix rule of the sharded search.  cum int32 [..., Q, nbits + 2]: cumulative distance histograms of one shard or of
+    several; cum_total [Q, nbits + 2]: their sum over ALL shards of the database.  A query's global k-th distance T is the
+    first bin b with cum_total[q, b + 1] >= k (rows of the whole database with distance <= b); a shard owes the query its
+    cum[q, T + 1] rows with distance <= T.
+    -> int32 [1] on the histograms' device: the longest prefix any of these shards owes any query.  No host read."""
+    T = (cum_total[:, 1:] >= k).int().argmax(dim=1)
+    return torch.gather(cum, -1, (T + 1).unsqueeze(1).expand(*cum.shape[:-1], 1)).max().reshape(1)
+
+
+def _virtual_prefix(q_packed, db, nbits, k):
+    """First step of every virtual-shard route: the parts' histograms and the prefix length each part contributes (one host
+    read, as in the un-hinted sharded search) -> (cums int32 [G, Q, nbits + 2], send)."""
+    cums = torch.stack([hamming_hist(q_packed, part, nbits) for part in db.parts])
+    return cums, max(1, min(k, db.per, int(owed_prefix(cums, cums.sum(0), k).item())))
 
 
 def _virtual_shards_topk(q_packed, db, nbits, k, idx_offset, want_dist):
-    cums = torch.stack([hamming_hist(q_packed, part, nbits) for part in db.parts])
-    send = max(1, min(k, db.per, _prefix_need(cums, k)))        # one host read, as in the un-hinted sharded search
+    cums, send = _virtual_prefix(q_packed, db, nbits, k)
+    if send > RANK_K_MAX:
+        return None
     Q = q_packed.shape[0]
     lists = torch.zeros((len(db.parts), Q, send), dtype=torch.int16, device=q_packed.device)
     for g, part in enumerate(db.parts):
@@ -315,49 +307,50 @@ def rank_from_dist(dist_matrix, nbits, k):
     return idx, dist
 
 
-def map_at_k(idx, qlab_packed, dblab_packed, k=None):
-    """Average precision per query over (the first k entries of) its ranked list -> (ap float32 [Q], nrel int32 [Q])."""
+def _cuts(what, k, ks):
+    """Where a single-k entry point and its multi-k twin differ: k is one cut-off (ks None) or ks holds several, as they
+    arrive -> (the C arguments that stand where k stands, trailing shape of ap / nrel, column of every requested cut-off or
+    None, largest cut-off)."""
+    if ks is None:
+        return (k,), (), None, k
+    uniq, c_ks, cols = _cutoffs(ks, what)
+    return (c_ks, len(uniq)), (len(uniq),), cols, uniq[-1]
+
+
+def _ap_buffers(Q, tail, device):
+    return torch.empty((Q,) + tail, dtype=torch.float32, device=device), torch.empty((Q,) + tail, dtype=torch.int32, device=device)
+
+
+def _map_at(what, idx, qlab_packed, dblab_packed, k, ks=None):
     lib = _lib.require_gpu()
     Q, kfull = idx.shape
-    k = kfull if k is None else int(k)
-    if not 1 <= k <= kfull:
-        raise ValueError(f"map_at_k: k={k} outside the lists' length {kfull}")
+    cargs, tail, cols, kmax = _cuts(what, k, ks)
+    if not 1 <= kmax <= kfull:
+        raise ValueError(f"{what}: cut-off {kmax} outside the lists' length {kfull}")
     lw = qlab_packed.shape[1]
     if dblab_packed.shape[1] != lw:
-        raise ValueError("map_at_k: label widths differ")
+        raise ValueError(f"{what}: label widths differ")
     if idx.stride(1) != 1:
         idx = idx.contiguous()
-    ap = torch.empty(Q, dtype=torch.float32, device=idx.device)
-    nrel = torch.empty(Q, dtype=torch.int32, device=idx.device)
+    ap, nrel = _ap_buffers(Q, tail, idx.device)
     if Q:
+        entry = "wv_map_at_k_ld" if ks is None else "wv_map_at_ks"
         with torch.cuda.device(idx.device):
-            rc = lib.wv_map_at_k_ld(_lib.ptr(idx), idx.stride(0), Q, k, _lib.ptr(qlab_packed), _lib.ptr(dblab_packed),
-                                    lw, _lib.ptr(ap), _lib.ptr(nrel), _lib.stream_ptr())
-            _lib.check(rc, "wv_map_at_k_ld")
-    return ap, nrel
+            rc = getattr(lib, entry)(_lib.ptr(idx), idx.stride(0), Q, *cargs, _lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw,
+                                     _lib.ptr(ap), _lib.ptr(nrel), _lib.stream_ptr())
+            _lib.check(rc, entry)
+    return _columns(ap, nrel, cols)
+
+
+def map_at_k(idx, qlab_packed, dblab_packed, k=None):
+    """Average precision per query over (the first k entries of) its ranked list -> (ap float32 [Q], nrel int32 [Q])."""
+    return _map_at("map_at_k", idx, qlab_packed, dblab_packed, idx.shape[1] if k is None else int(k))
 
 
 def map_at_ks(idx, qlab_packed, dblab_packed, ks):
     """map_at_k for several cut-offs from ONE pass over the lists (read once, labels gathered once)
     -> (ap float32 [Q, len(ks)], nrel int32 [Q, len(ks)]), column i = map_at_k(idx, ..., k=ks[i])."""
-    lib = _lib.require_gpu()
-    Q, kfull = idx.shape
-    uniq, c_ks, cols = _cutoffs(ks, "map_at_ks")
-    if uniq[-1] > kfull:
-        raise ValueError(f"map_at_ks: cut-off {uniq[-1]} outside the lists' length {kfull}")
-    lw = qlab_packed.shape[1]
-    if dblab_packed.shape[1] != lw:
-        raise ValueError("map_at_ks: label widths differ")
-    if idx.stride(1) != 1:
-        idx = idx.contiguous()
-    ap = torch.empty((Q, len(uniq)), dtype=torch.float32, device=idx.device)
-    nrel = torch.empty((Q, len(uniq)), dtype=torch.int32, device=idx.device)
-    if Q:
-        with torch.cuda.device(idx.device):
-            rc = lib.wv_map_at_ks(_lib.ptr(idx), idx.stride(0), Q, c_ks, len(uniq), _lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw,
-                                  _lib.ptr(ap), _lib.ptr(nrel), _lib.stream_ptr())
-            _lib.check(rc, "wv_map_at_ks")
-    return _columns(ap, nrel, cols)
+    return _map_at("map_at_ks", idx, qlab_packed, dblab_packed, None, ks)
 
 
 class PreparedLabels:
@@ -387,41 +380,65 @@ class PreparedLabels:
                 _lib.check(rc, "wv_rank_labels_prepare")
 
 
+def _fused_gate(what, q_packed, db, labels, qlab_packed, nbits, code_width=False):
+    """The argument check of the entry points that read codes and labels in one kernel.  TypeError for unprepared inputs,
+    ValueError for shapes that disagree (code_width: the packed width must also be nbits'); -> False when the shape is outside
+    the fused kernels (labels wider than 2 words, nbits > 128): the caller answers None."""
+    if not isinstance(db, PreparedDB) or not isinstance(labels, PreparedLabels):
+        raise TypeError(f"{what}: needs a PreparedDB and PreparedLabels")
+    words = q_packed.shape[1]
+    if words != db.words or labels.N != db.N or (code_width and words != _words(nbits)):
+        raise ValueError(f"{what}: query / database / label shapes disagree")
+    return labels.ok and qlab_packed.shape[1] == labels.words and nbits <= 128
+
+
+def _fused_map(what, q_packed, db, labels, qlab_packed, nbits, k, ks=None):
+    """hamming_map_at_k (ks None) and hamming_map_at_ks: gate, virtual-shard route, direct route; the leaves differ (_cuts)."""
+    lib = _lib.require_gpu()
+    ok = _fused_gate(what, q_packed, db, labels, qlab_packed, nbits)
+    cargs, tail, cols, kmax = _cuts(what, k, ks)
+    if ks is not None and kmax > db.N:
+        raise ValueError(f"{what}: largest cut-off {kmax} must be <= N={db.N}")
+    if not ok or not 1 <= kmax <= db.N:
+        return None
+    Q = q_packed.shape[0]
+    dev = q_packed.device
+    if db.parts or labels.parts:                         # more than 32,768 rows: virtual shards, relevance strings, one merge
+        if not (db.parts and labels.parts) or len(db.parts) != len(labels.parts) or not Q:
+            return None
+        send = _virtual_prefix(q_packed, db, nbits, kmax)[1]     # one prefix length, for the largest cut-off
+        if send > RANK_K_MAX:
+            return None
+        wires = torch.zeros((len(db.parts), Q, relbits_wire_words(send, nbits)), dtype=torch.int64, device=dev)
+        for g, (part, lab) in enumerate(zip(db.parts, labels.parts)):
+            if hamming_shard_relbits(q_packed, part, lab, qlab_packed, nbits, min(send, part.N), wire=wires[g], kin=send) is None:
+                return None
+        return merge_relbits_map(wires, send, k, nbits) if ks is None else merge_relbits_map_ks(wires, send, ks, nbits)
+    ap, nrel = _ap_buffers(Q, tail, dev)
+    if Q:
+        with torch.cuda.device(dev):
+            rc = getattr(lib, "wv_" + what)(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
+                                            _lib.ptr(qlab_packed.contiguous()), labels.words, Q, db.N, nbits, *cargs, _lib.ptr(ap),
+                                            _lib.ptr(nrel), _lib.stream_ptr())
+            if rc == _lib.WV_ENOTSUP:
+                return None
+            _lib.check(rc, "wv_" + what)
+    return _columns(ap, nrel, cols)
+
+
 def hamming_map_at_k(q_packed, db, labels, qlab_packed, nbits, k):
     """mAP@k ingredients straight from the codes -> (ap float32 [Q], nrel int32 [Q]), or None when the shape is outside
     the fused kernel (the caller then runs hamming_topk + map_at_k, which return exactly the same numbers).
     db: PreparedDB; labels: PreparedLabels of the same rows; qlab_packed: int64 [Q, 1 or 2]."""
-    lib = _lib.require_gpu()
-    if not isinstance(db, PreparedDB) or not isinstance(labels, PreparedLabels):
-        raise TypeError("hamming_map_at_k: needs a PreparedDB and PreparedLabels")
-    Q, words = q_packed.shape
-    if words != db.words or labels.N != db.N:
-        raise ValueError("hamming_map_at_k: query / database / label shapes disagree")
-    if not labels.ok or qlab_packed.shape[1] != labels.words or nbits > 128 or not 1 <= k <= db.N:
-        return None
-    if db.parts or labels.parts:                         # more than 32,768 rows: virtual shards, relevance strings, one merge
-        if not (db.parts and labels.parts) or len(db.parts) != len(labels.parts) or not Q:
-            return None
-        cums = torch.stack([hamming_hist(q_packed, part, nbits) for part in db.parts])
-        send = max(1, min(k, db.per, _prefix_need(cums, k)))
-        if send > RANK_K_MAX:
-            return None
-        wires = torch.zeros((len(db.parts), Q, relbits_wire_words(send, nbits)), dtype=torch.int64, device=q_packed.device)
-        for g, (part, lab) in enumerate(zip(db.parts, labels.parts)):
-            if hamming_shard_relbits(q_packed, part, lab, qlab_packed, nbits, min(send, part.N), wire=wires[g], kin=send) is None:
-                return None
-        return merge_relbits_map(wires, send, k, nbits)
-    ap = torch.empty(Q, dtype=torch.float32, device=q_packed.device)
-    nrel = torch.empty(Q, dtype=torch.int32, device=q_packed.device)
-    if Q:
-        with torch.cuda.device(q_packed.device):
-            rc = lib.wv_hamming_map_at_k(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
-                                         _lib.ptr(qlab_packed.contiguous()), labels.words, Q, db.N, nbits, k, _lib.ptr(ap), _lib.ptr(nrel),
-                                         _lib.stream_ptr())
-            if rc == _lib.WV_ENOTSUP:
-                return None
-            _lib.check(rc, "wv_hamming_map_at_k")
-    return ap, nrel
+    return _fused_map("hamming_map_at_k", q_packed, db, labels, qlab_packed, nbits, k)
+
+
+def hamming_map_at_ks(q_packed, db, labels, qlab_packed, nbits, ks):
+    """hamming_map_at_k for several cut-offs from ONE ranking pass -> (ap float32 [Q, len(ks)], nrel int32 [Q, len(ks)]),
+    column i = what hamming_map_at_k returns for k = ks[i]; or None when the largest cut-off is outside the fused kernel
+    (the caller then runs hamming_topk at max(ks) + map_at_ks: the same numbers).  ks: any order, repeats allowed, at most
+    MAX_CUTOFFS different values."""
+    return _fused_map("hamming_map_at_ks", q_packed, db, labels, qlab_packed, nbits, None, ks)
 
 
 def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
@@ -432,13 +449,9 @@ def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
     per-part calls.  None where hamming_map_at_k answers None (labels wider than 2 words, nbits > 128).
     db: PreparedDB; labels: PreparedLabels of the same rows; qlab_packed: int64 [Q, 1 or 2]."""
     lib = _lib.require_gpu()
-    if not isinstance(db, PreparedDB) or not isinstance(labels, PreparedLabels):
-        raise TypeError("hamming_radius_hist: needs a PreparedDB and PreparedLabels")
-    Q, words = q_packed.shape
-    if words != db.words or labels.N != db.N or words != _words(nbits):
-        raise ValueError("hamming_radius_hist: query / database / label shapes disagree")
-    if not labels.ok or qlab_packed.shape[1] != labels.words or nbits > 128:
+    if not _fused_gate("hamming_radius_hist", q_packed, db, labels, qlab_packed, nbits, code_width=True):
         return None
+    Q = q_packed.shape[0]
     dev = q_packed.device
     if db.parts or labels.parts:
         if not (db.parts and labels.parts) or len(db.parts) != len(labels.parts):
@@ -480,55 +493,11 @@ def _cutoffs(ks, what):
 
 
 def _columns(ap, nrel, cols):
-    """[Q, unique cut-offs] -> [Q, requested cut-offs]"""
-    if cols == list(range(ap.shape[1])):
+    """[Q, unique cut-offs] -> [Q, requested cut-offs]; cols None: a single-k call's [Q], as they are"""
+    if cols is None or cols == list(range(ap.shape[1])):
         return ap, nrel
     sel = torch.tensor(cols, dtype=torch.long, device=ap.device)
     return ap.index_select(1, sel), nrel.index_select(1, sel)
-
-
-def hamming_map_at_ks(q_packed, db, labels, qlab_packed, nbits, ks):
-    """hamming_map_at_k for several cut-offs from ONE ranking pass -> (ap float32 [Q, len(ks)], nrel int32 [Q, len(ks)]),
-    column i = what hamming_map_at_k returns for k = ks[i]; or None when the largest cut-off is outside the fused kernel
-    (the caller then runs hamming_topk at max(ks) + map_at_ks: the same numbers).  ks: any order, repeats allowed, at most
-    MAX_CUTOFFS different values."""
-    lib = _lib.require_gpu()
-    if not isinstance(db, PreparedDB) or not isinstance(labels, PreparedLabels):
-        raise TypeError("hamming_map_at_ks: needs a PreparedDB and PreparedLabels")
-    Q, words = q_packed.shape
-    if words != db.words or labels.N != db.N:
-        raise ValueError("hamming_map_at_ks: query / database / label shapes disagree")
-    uniq, c_ks, cols = _cutoffs(ks, "hamming_map_at_ks")
-    kmax = uniq[-1]
-    if kmax > db.N:
-        raise ValueError(f"hamming_map_at_ks: largest cut-off {kmax} must be <= N={db.N}")
-    if not labels.ok or qlab_packed.shape[1] != labels.words or nbits > 128:
-        return None
-    dev = q_packed.device
-    if db.parts or labels.parts:                         # more than 32,768 rows: virtual shards, one prefix length for max(ks)
-        if not (db.parts and labels.parts) or len(db.parts) != len(labels.parts) or not Q:
-            return None
-        cums = torch.stack([hamming_hist(q_packed, part, nbits) for part in db.parts])
-        send = max(1, min(kmax, db.per, _prefix_need(cums, kmax)))
-        if send > RANK_K_MAX:
-            return None
-        wires = torch.zeros((len(db.parts), Q, relbits_wire_words(send, nbits)), dtype=torch.int64, device=dev)
-        for g, (part, lab) in enumerate(zip(db.parts, labels.parts)):
-            if hamming_shard_relbits(q_packed, part, lab, qlab_packed, nbits, min(send, part.N), wire=wires[g], kin=send) is None:
-                return None
-        got = merge_relbits_map_ks(wires, send, uniq, nbits)
-        return None if got is None else _columns(*got, cols)
-    ap = torch.empty((Q, len(uniq)), dtype=torch.float32, device=dev)
-    nrel = torch.empty((Q, len(uniq)), dtype=torch.int32, device=dev)
-    if Q:
-        with torch.cuda.device(dev):
-            rc = lib.wv_hamming_map_at_ks(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
-                                          _lib.ptr(qlab_packed.contiguous()), labels.words, Q, db.N, nbits, c_ks, len(uniq),
-                                          _lib.ptr(ap), _lib.ptr(nrel), _lib.stream_ptr())
-            if rc == _lib.WV_ENOTSUP:
-                return None
-            _lib.check(rc, "wv_hamming_map_at_ks")
-    return _columns(ap, nrel, cols)
 
 
 def _label_pair(qlab_packed, dblab_packed, what):
@@ -598,10 +567,22 @@ def ndcg_at_ks(idx, qlab_packed, dblab_packed, ks, hist=None):
     return _columns(dcg, idcg, cols)
 
 
+def _hist_words(nbits):
+    """int64 words at the head of a wire row that hold the histogram (nbits + 2 int32, padded to 8 bytes)"""
+    return (nbits + 3) // 2
+
+
 def relbits_wire_words(kin, nbits):
     """int64 words per (query, shard) row of the sharded-mAP wire buffer: [histogram: nbits + 2 int32, padded to 8 bytes |
     relevance string: ceil(kin / 64) uint64]."""
-    return (nbits + 3) // 2 + (kin + 63) // 64
+    return _hist_words(nbits) + (kin + 63) // 64
+
+
+def _wire_args(wire, nbits):
+    """The four C arguments that describe a contiguous wire buffer [.., relbits_wire_words]: relevance strings (pointer, row
+    pitch in 64-bit words), histograms (pointer, row pitch in int32)."""
+    ld = wire.shape[-1]
+    return wire.data_ptr() + 8 * _hist_words(nbits), ld, wire.data_ptr(), 2 * ld
 
 
 def hamming_shard_relbits(q_packed, db, labels, qlab_packed, nbits, k, wire=None, kin=None):
@@ -611,51 +592,49 @@ def hamming_shard_relbits(q_packed, db, labels, qlab_packed, nbits, k, wire=None
     tail of the string zero) -- a single all_to_all moves both.  `wire`: preallocated (zeroed) buffer.
     -> wire, or None when the shape is outside the fused kernel."""
     lib = _lib.require_gpu()
-    if not isinstance(db, PreparedDB) or not isinstance(labels, PreparedLabels):
-        raise TypeError("hamming_shard_relbits: needs a PreparedDB and PreparedLabels")
-    Q, words = q_packed.shape
-    if words != db.words or labels.N != db.N:
-        raise ValueError("hamming_shard_relbits: query / database / label shapes disagree")
-    if not labels.ok or qlab_packed.shape[1] != labels.words or nbits > 128 or not 1 <= k <= db.N:
+    if not _fused_gate("hamming_shard_relbits", q_packed, db, labels, qlab_packed, nbits) or not 1 <= k <= db.N:
         return None
+    Q = q_packed.shape[0]
     kin = k if kin is None else kin
-    dev = q_packed.device
     ld = relbits_wire_words(kin, nbits)
     if wire is None:
-        wire = torch.zeros((Q, ld), dtype=torch.int64, device=dev)
+        wire = torch.zeros((Q, ld), dtype=torch.int64, device=q_packed.device)
     elif tuple(wire.shape) != (Q, ld) or wire.dtype != torch.int64 or not wire.is_contiguous():
         raise ValueError("hamming_shard_relbits: wire buffer of the wrong shape")
     if Q:
-        hist_words = (nbits + 3) // 2
-        with torch.cuda.device(dev):
+        with torch.cuda.device(q_packed.device):
             rc = lib.wv_hamming_shard_relbits(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
-                                              _lib.ptr(qlab_packed.contiguous()), labels.words, wire.data_ptr() + 8 * hist_words, ld,
-                                              wire.data_ptr(), 2 * ld, Q, db.N, nbits, k, _lib.stream_ptr())
+                                              _lib.ptr(qlab_packed.contiguous()), labels.words, *_wire_args(wire, nbits),
+                                              Q, db.N, nbits, k, _lib.stream_ptr())
             if rc == _lib.WV_ENOTSUP:
                 return None
             _lib.check(rc, "wv_hamming_shard_relbits")
     return wire
 
 
+def _merge_relbits(what, wire, kin, k, ks, nbits, need_out):
+    lib = _lib.require_gpu()
+    G, Q, ld = wire.shape
+    if wire.dtype != torch.int64 or ld != relbits_wire_words(kin, nbits):
+        raise ValueError(f"{what}: expected the int64 [G, Q, relbits_wire_words(kin, nbits)] wire buffer")
+    cargs, tail, cols, _ = _cuts(what, k, ks)
+    wire = wire.contiguous()
+    ap, nrel = _ap_buffers(Q, tail, wire.device)
+    if Q:
+        with torch.cuda.device(wire.device):
+            rc = getattr(lib, "wv_" + what)(*_wire_args(wire, nbits), G, Q, kin, *cargs, nbits, _lib.ptr(ap), _lib.ptr(nrel),
+                                            _lib.ptr(need_out), _lib.stream_ptr())
+            if rc == _lib.WV_ENOTSUP and ks is not None:         # only the multi-k kernel keeps the merged string in LDS
+                return None
+            _lib.check(rc, "wv_" + what)
+    return _columns(ap, nrel, cols)
+
+
 def merge_relbits_map(wire, kin, k, nbits, need_out=None):
     """wire int64 [G, Q, relbits_wire_words(kin, nbits)] -- the rows hamming_shard_relbits made on G contiguous row shards in
     rank order -> (ap float32 [Q], nrel int32 [Q]) of the merged top-k lists, equal to map_at_k of the merged lists.
     need_out as in topk_merge_cum."""
-    lib = _lib.require_gpu()
-    G, Q, ld = wire.shape
-    if wire.dtype != torch.int64 or ld != relbits_wire_words(kin, nbits):
-        raise ValueError("merge_relbits_map: expected the int64 [G, Q, relbits_wire_words(kin, nbits)] wire buffer")
-    wire = wire.contiguous()
-    ap = torch.empty(Q, dtype=torch.float32, device=wire.device)
-    nrel = torch.empty(Q, dtype=torch.int32, device=wire.device)
-    if Q:
-        hist_words = (nbits + 3) // 2
-        with torch.cuda.device(wire.device):
-            rc = lib.wv_merge_relbits_map(wire.data_ptr() + 8 * hist_words, ld, wire.data_ptr(), 2 * ld, G, Q, kin, k, nbits,
-                                          _lib.ptr(ap), _lib.ptr(nrel), _lib.ptr(need_out) if need_out is not None else None,
-                                          _lib.stream_ptr())
-            _lib.check(rc, "wv_merge_relbits_map")
-    return ap, nrel
+    return _merge_relbits("merge_relbits_map", wire, kin, k, None, nbits, need_out)
 
 
 MERGE_LDS_LIMIT = 60 * 1024  # WV_MERGE_RELBITS_LDS_LIMIT: dynamic LDS above which wv_merge_relbits_map_ks answers WV_ENOTSUP
@@ -671,29 +650,12 @@ def merge_relbits_lds_bytes(G, k, nbits):
 def merge_relbits_map_ks(wire, kin, ks, nbits, need_out=None):
     """merge_relbits_map for several cut-offs from ONE merged string (assembled for max(ks); need_out refers to max(ks))
     -> (ap float32 [Q, len(ks)], nrel int32 [Q, len(ks)]), or None when that string does not fit the kernel's LDS."""
-    lib = _lib.require_gpu()
-    G, Q, ld = wire.shape
-    if wire.dtype != torch.int64 or ld != relbits_wire_words(kin, nbits):
-        raise ValueError("merge_relbits_map_ks: expected the int64 [G, Q, relbits_wire_words(kin, nbits)] wire buffer")
-    uniq, c_ks, cols = _cutoffs(ks, "merge_relbits_map_ks")
-    wire = wire.contiguous()
-    ap = torch.empty((Q, len(uniq)), dtype=torch.float32, device=wire.device)
-    nrel = torch.empty((Q, len(uniq)), dtype=torch.int32, device=wire.device)
-    if Q:
-        hist_words = (nbits + 3) // 2
-        with torch.cuda.device(wire.device):
-            rc = lib.wv_merge_relbits_map_ks(wire.data_ptr() + 8 * hist_words, ld, wire.data_ptr(), 2 * ld, G, Q, kin, c_ks, len(uniq),
-                                             nbits, _lib.ptr(ap), _lib.ptr(nrel), _lib.ptr(need_out) if need_out is not None else None,
-                                             _lib.stream_ptr())
-            if rc == _lib.WV_ENOTSUP:
-                return None
-            _lib.check(rc, "wv_merge_relbits_map_ks")
-    return _columns(ap, nrel, cols)
+    return _merge_relbits("merge_relbits_map_ks", wire, kin, None, ks, nbits, need_out)
 
 
 def wire_histograms(wire, nbits):
     """int32 [.., nbits + 2] view of the histograms inside a wire buffer (tests, diagnostics)."""
-    return wire.view(torch.int32).reshape(*wire.shape[:-1], 2 * wire.shape[-1])[..., :nbits + 2]
+    return wire.view(torch.int32)[..., :nbits + 2]         # the first 2 * _hist_words(nbits) int32 of a row hold them
 
 
 def hit_prefix(idx, qlab_packed, dblab_packed):

@@ -110,17 +110,76 @@ def _all_reduce(t, op, group):
             dist.all_reduce(t, op=op, group=group)
 
 
+def _gather_rows(local, world, group):
+    """all_gather of every rank's [Ql, width] rows -> [world * Ql, width], in rank order"""
+    out = torch.empty((world * local.shape[0], local.shape[1]), dtype=local.dtype, device=local.device)
+    _all_gather(out, local.contiguous(), group)
+    return out
+
+
+def _prefix_len(kin, hint):
+    """The prefix length exchanged for a hint (or a measured need): at least one entry, at most what a shard can owe"""
+    return max(1, min(int(kin), int(hint)))
+
+
+def _exact_send(cum, k, kin, group, send_hint=None):
+    """Exact sizing of an exchange from this shard's histograms cum [Q, nbits + 2]: their SUM all-reduce (Q * (nbits + 2) * 4
+    bytes) gives every rank the global k-th distance T of every query, H.owed_prefix this shard's longest prefix with
+    distance <= T (`need`, device int32 [1]).  Without a hint the prefix length is the maximum over all ranks -- one scalar
+    MAX all-reduce and the one host read of the exchange --, so the exchange stays a fixed-size all_to_all.  With a hint every
+    rank sends `send_hint` entries and `need` stays THIS shard's own requirement: no MAX all-reduce, no host read; the
+    caller verifies need <= send_hint on every rank whenever it synchronises anyway (exchange_ok).  -> (send, need)"""
+    cum_g = cum.clone()
+    _all_reduce(cum_g, dist.ReduceOp.SUM, group)
+    need = H.owed_prefix(cum, cum_g, k)
+    if send_hint is None:
+        _all_reduce(need, dist.ReduceOp.MAX, group)
+        send_hint = need.item()
+    return _prefix_len(kin, send_hint), need
+
+
+def _exchange_compact(rows, cum, send, world, per, k, nbits, group, report_need):
+    """Compact exchange and merge: 16-bit LOCAL row numbers (2 bytes per entry) and, instead of a distance row, the shard's
+    cumulative histogram of each query (a sorted list is fully described by it): 2 bytes per entry + 4 * (nbits + 2) bytes per
+    (query, shard) on the wire instead of 5 bytes per entry.  int16 storage, shipped as bytes (RCCL has no 16-bit integer
+    type).  report_need: the merge kernel has every shard's histograms of its queries, derives each query's global k-th
+    distance and reports the longest prefix any shard owed.  -> (idx, dist, need int32 [1] or None)"""
+    if rows.shape[1] < send:                            # a shard shorter than the prefix: pad (never read by the merge)
+        rows = torch.nn.functional.pad(rows, (0, send - rows.shape[1]))
+    rows_r = torch.empty_like(rows)
+    _all_to_all(rows_r.view(torch.uint8), rows.contiguous().view(torch.uint8), group)
+    cum_r = torch.empty_like(cum)
+    _all_to_all(cum_r, cum.contiguous(), group)
+    need = torch.zeros(1, dtype=torch.int32, device=rows.device) if report_need else None
+    Ql = rows.shape[0] // world                         # received layout: [shard g][my Ql queries][...]
+    idx, d = H.topk_merge_cum(rows_r.view(world, Ql, send), cum_r.view(world, Ql, nbits + 2), per, k, nbits, need_out=need)
+    return idx, d, need
+
+
+def _exchange_wide(lists, nq, send, world, k, nbits, device, group):
+    """Exchange and merge of int32 global rows + uint8 distances: shards of more than 65,536 rows, trim=False.
+    lists: (idx, dist) of this shard, or None for an empty one."""
+    idx_s = torch.full((nq, send), -1, dtype=torch.int32, device=device)
+    dist_s = torch.full((nq, send), pad_value(nbits), dtype=torch.uint8, device=device)
+    if lists is not None:
+        w = min(send, lists[0].shape[1])
+        idx_s[:, :w], dist_s[:, :w] = lists[0][:, :w], lists[1][:, :w]
+    idx_r = torch.empty_like(idx_s)                     # block j of my lists (queries of rank j) goes to rank j
+    dist_r = torch.empty_like(dist_s)
+    _all_to_all(idx_r, idx_s, group)
+    _all_to_all(dist_r, dist_s, group)
+    Ql = nq // world                                    # received layout: [shard g][my Ql queries][send]
+    return H.topk_merge(idx_r.view(world, Ql, send), dist_r.view(world, Ql, send), k, nbits)
+
+
 def sharded_hamming_topk(q_local, db_shard, nbits, k, n_total, group=None, workspace=None, trim=True,
                          send_hint=None, return_need=False, want_dist=True):
     """q_local: packed codes of THIS rank's queries [Ql, words]; db_shard: this rank's rows
     [lo:hi] of the packed database (tensor or PreparedDB).  Returns the global (idx int32 [Ql,k], dist uint8
     [Ql,k]) of the local queries.  Every rank must call with the same Ql.
 
-    trim=True: the per-shard ranking also returns each query's cumulative distance histogram; one all-reduce
-    of it (Q*(nbits+2)*4 bytes) gives every rank the global k-th distance T of every query, a shard then only
-    has to send its list prefix with distance <= T.  The prefix length used is the maximum over all queries
-    and shards (one scalar MAX all-reduce + one host read), so the exchange stays a fixed-size all_to_all --
-    typically ~k/world + ties entries per query instead of min(k, shard rows).
+    trim=True: the exchange is sized exactly first (_exact_send): a shard only has to send its list prefix with distance
+    <= T, the query's global k-th distance -- typically ~k/world + ties entries per query instead of min(k, shard rows).
 
     send_hint (with trim): prefix length to exchange WITHOUT the host read -- for a steady stream of query batches
     (serving, bench.py) whose needed length is known from earlier batches.  The call then never synchronises with the
@@ -136,107 +195,55 @@ def sharded_hamming_topk(q_local, db_shard, nbits, k, n_total, group=None, works
         out = H.hamming_topk(q_local, db_shard, nbits, k, workspace=workspace, want_dist=want_dist)
         return (out[0], out[1], None) if return_need else out
     rank = dist.get_rank(group)
-    Ql, words = q_local.shape
     lo, hi, per = shard_bounds(n_total, world, rank)
-    kin = min(k, per)                                   # longest list a shard could have to send
-    # 1. every rank needs every query
-    q_all = torch.empty((world * Ql, words), dtype=q_local.dtype, device=q_local.device)
-    _all_gather(q_all, q_local.contiguous(), group)
-    # 2. rank all queries against the local shard
     n_local = hi - lo
+    kin = min(k, per)                                   # longest list a shard could have to send
+    k_local = min(kin, n_local)
+    # 1. every rank needs every query
+    q_all = _gather_rows(q_local, world, group)
     if not isinstance(db_shard, H.PreparedDB) and db_shard.shape[0] != n_local:
         raise ValueError(f"rank {rank}: shard has {db_shard.shape[0]} rows, expected rows [{lo}, {hi}) of {n_total}")
-    k_local = min(kin, n_local)
-    dev = q_local.device
-    i = d = cum = None
-    # Two-step form (shards the windowed kernel takes): histograms first -- cheap, no list -- so that every rank knows
-    # each query's global k-th distance BEFORE any list is built; the shard then ranks only the prefix that can matter
-    # (about k / world + ties entries instead of min(k, shard rows)) and writes it straight in the 16-bit wire format.
-    two_step = trim and 0 < n_local <= H.SHARD_ROWS_MAX and per <= H.SHARD_ROWS_MAX
-    if trim and send_hint is not None and per <= H.SHARD_ROWS_MAX:
-        # Hinted steady state: the prefix length is known, so nothing has to be learned before the lists are built.
-        # ONE ranking pass per shard (the `send` nearest rows as 16-bit local numbers + the complete histograms), the two
-        # all_to_alls, the merge -- no all-reduce at all (3 collectives per step instead of 5).  Whether `send` was enough
-        # is decided where the lists arrive: the merge kernel has every shard's histograms of its queries, derives each
-        # query's global k-th distance T and reports the longest prefix any shard owed (`need`, device int32 [1]).
-        send = max(1, min(kin, int(send_hint)))
-        if n_local > 0:
-            w = min(send, n_local)
-            loc_s, cum = H.hamming_shard_prefix(q_all, db_shard, nbits, w, workspace=workspace)
-            if w < send:
-                loc_s = torch.nn.functional.pad(loc_s, (0, send - w))
+    nq, dev = q_all.shape[0], q_local.device
+    # 2. the shard step.  Shards the windowed kernel takes never rank more than the prefix that can matter, and write it
+    # straight in the 16-bit wire format: in ONE pass with the complete histograms when the prefix length is known (hinted
+    # steady state: 3 collectives per step instead of 5), else histograms first -- cheap, no list -- and the lists once the
+    # exchange is sized.  Any other shard ranks its k_local nearest rows in one step.
+    windowed = trim and per <= H.SHARD_ROWS_MAX
+    hinted = windowed and send_hint is not None
+    send = _prefix_len(kin, send_hint) if hinted else kin
+    rows = lists = cum = need = None
+    if hinted:
+        if n_local:
+            rows, cum = H.hamming_shard_prefix(q_all, db_shard, nbits, min(send, n_local), workspace=workspace)
         else:                                           # empty shard: contributes nothing
-            loc_s = torch.zeros((world * Ql, send), dtype=torch.int16, device=dev)
-            cum = torch.zeros((world * Ql, nbits + 2), dtype=torch.int32, device=dev)
-        loc_r = torch.empty_like(loc_s)
-        _all_to_all(loc_r.view(torch.uint8), loc_s.contiguous().view(torch.uint8), group)
-        cum_r = torch.empty_like(cum)
-        _all_to_all(cum_r, cum.contiguous(), group)
-        need = torch.zeros(1, dtype=torch.int32, device=dev)
-        out = H.topk_merge_cum(loc_r.view(world, Ql, send), cum_r.view(world, Ql, nbits + 2), per, k, nbits, need_out=need)
-        return (out[0], out[1], need) if return_need else out
-    if k_local > 0 and not two_step:
-        if trim:
-            # the compact exchange below ships histograms, not distance rows: do not even write them
-            i, d, cum = H.hamming_topk(q_all, db_shard, nbits, k_local, idx_offset=lo, workspace=workspace,
-                                       want_dist=per > 65536, want_cum=True)
-        else:
-            i, d = H.hamming_topk(q_all, db_shard, nbits, k_local, idx_offset=lo, workspace=workspace)
-    if two_step:
+            rows = torch.zeros((nq, send), dtype=torch.int16, device=dev)
+    elif windowed and n_local:
         cum = H.hamming_hist(q_all, db_shard, nbits, workspace=workspace)
-    send = kin
-    need = None
-    if trim:
-        if cum is None:                                 # empty shard: contributes nothing
-            cum = torch.zeros((world * Ql, nbits + 2), dtype=torch.int32, device=dev)
-        cum_g = cum.clone()
-        _all_reduce(cum_g, dist.ReduceOp.SUM, group)
-        # T = first bin b with (#rows of the whole database with distance <= b) >= k
-        T = (cum_g[:, 1:] >= k).int().argmax(dim=1)
-        need = torch.gather(cum, 1, (T + 1).unsqueeze(1).long()).max().reshape(1)   # local rows with distance <= T
-        if send_hint is None:
-            _all_reduce(need, dist.ReduceOp.MAX, group)
-            send = max(1, min(kin, int(need.item())))   # exact sizing: the one host read of the exchange
-        else:
-            # no host read and no MAX all-reduce: every rank sends `send_hint` entries, `need` stays THIS shard's own
-            # requirement and the caller verifies need <= send_hint on every rank (exchange_ok + one flag all-reduce
-            # whenever it synchronises anyway) -- one collective less in every steady-state step
-            send = max(1, min(kin, int(send_hint)))
+    elif k_local and trim:
+        # the compact exchange ships histograms, not distance rows: do not even write them
+        *lists, cum = H.hamming_topk(q_all, db_shard, nbits, k_local, idx_offset=lo, workspace=workspace,
+                                     want_dist=per > 65536, want_cum=True)
+    elif k_local:
+        lists = H.hamming_topk(q_all, db_shard, nbits, k_local, idx_offset=lo, workspace=workspace)
+    if trim and cum is None:                            # empty shard: contributes nothing
+        cum = torch.zeros((nq, nbits + 2), dtype=torch.int32, device=dev)
+    # 3. size the exchange
+    if trim and not hinted:
+        send, need = _exact_send(cum, k, kin, group, send_hint)
+    # 4. exchange and merge
     if trim and per <= 65536:
-        # compact exchange: 16-bit LOCAL row numbers (2 bytes/entry) and, instead of a distance row, the shard's
-        # cumulative histogram of each query (a sorted list is fully described by it): 2 bytes per entry + 4*(nbits+2)
-        # bytes per (query, shard) on the wire instead of 5 bytes per entry.  int16 storage, shipped as bytes (RCCL has
-        # no 16-bit integer type).
-        if two_step:
-            w = min(send, n_local)
-            loc_s = H.hamming_topk_rows16(q_all, db_shard, nbits, w, workspace=workspace)
-            if w < send:                                # a shard shorter than the prefix: pad (never read by the merge)
-                loc_s = torch.nn.functional.pad(loc_s, (0, send - w))
-        else:
-            loc_s = torch.zeros((world * Ql, send), dtype=torch.int16, device=dev)
-            if k_local > 0:
+        if windowed and n_local and rows is None:
+            rows = H.hamming_topk_rows16(q_all, db_shard, nbits, min(send, n_local), workspace=workspace)
+        elif rows is None:
+            rows = torch.zeros((nq, send), dtype=torch.int16, device=dev)
+            if lists is not None:
                 w = min(send, k_local)
-                loc_s[:, :w] = (i[:, :w] - lo).to(torch.int16)   # wraps for rows >= 32768; the kernel reads uint16
-        loc_r = torch.empty_like(loc_s)
-        _all_to_all(loc_r.view(torch.uint8), loc_s.contiguous().view(torch.uint8), group)
-        cum_r = torch.empty_like(cum)
-        _all_to_all(cum_r, cum.contiguous(), group)
-        # received layout: [shard g][my Ql queries][...]
-        out = H.topk_merge_cum(loc_r.view(world, Ql, send), cum_r.view(world, Ql, nbits + 2), per, k, nbits)
-        return (out[0], out[1], need) if return_need else out
-    idx_s = torch.full((world * Ql, send), -1, dtype=torch.int32, device=dev)
-    dist_s = torch.full((world * Ql, send), pad_value(nbits), dtype=torch.uint8, device=dev)
-    if k_local > 0:
-        w = min(send, k_local)
-        idx_s[:, :w], dist_s[:, :w] = i[:, :w], d[:, :w]
-    # 3. exchange: block j of my lists (queries of rank j) goes to rank j
-    idx_r = torch.empty_like(idx_s)
-    dist_r = torch.empty_like(dist_s)
-    _all_to_all(idx_r, idx_s, group)
-    _all_to_all(dist_r, dist_s, group)
-    # received layout: [shard g][my Ql queries][send]  ->  merge
-    out = H.topk_merge(idx_r.view(world, Ql, send), dist_r.view(world, Ql, send), k, nbits)
-    return (out[0], out[1], need) if return_need else out
+                rows[:, :w] = (lists[0][:, :w] - lo).to(torch.int16)   # wraps for rows >= 32768; the kernel reads uint16
+        idx, d, owed = _exchange_compact(rows, cum, send, world, per, k, nbits, group, report_need=hinted)
+        need = owed if hinted else need
+    else:
+        idx, d = _exchange_wide(lists, nq, send, world, k, nbits, dev, group)
+    return (idx, d, need) if return_need else (idx, d)
 
 
 def sharded_hamming_map_at_k(q_local, qlab_local, db_shard, labels_shard, nbits, k, n_total, send_hint, group=None):
@@ -259,44 +266,34 @@ def sharded_hamming_map_at_k(q_local, qlab_local, db_shard, labels_shard, nbits,
     k may be a sequence of cut-offs (any order): ap and nrel are then [Ql, len(k)], column i what the call returns for k[i];
     still one all_gather and one all_to_all, their length from max(k), and `need` refers to max(k)."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
-    ks = [int(x) for x in k] if isinstance(k, (tuple, list)) else None    # several cut-offs: ap / nrel are [Ql, len(k)]
-    if ks is not None:
-        if not ks:
+    multi = isinstance(k, (tuple, list))                 # several cut-offs: ap / nrel are [Ql, len(k)]
+    if multi:
+        k = [int(x) for x in k]
+        if not k:
             raise ValueError("sharded_hamming_map_at_k: empty k sequence")
-        k = max(ks)                                      # ranking, prefix length and exchange are sized by the largest
+    kmax = max(k) if multi else k                        # ranking, prefix length and exchange are sized by the largest
     if world == 1:
-        if ks is not None:
-            out = H.hamming_map_at_ks(q_local, db_shard, labels_shard, qlab_local, nbits, ks)
-        else:
-            out = H.hamming_map_at_k(q_local, db_shard, labels_shard, qlab_local, nbits, k)
+        out = (H.hamming_map_at_ks if multi else H.hamming_map_at_k)(q_local, db_shard, labels_shard, qlab_local, nbits, k)
         return None if out is None else (out[0], out[1], None)
     rank = dist.get_rank(group)
     Ql, words = q_local.shape
     lo, hi, per = shard_bounds(n_total, world, rank)
     n_local = hi - lo
     lwords = qlab_local.shape[1]                         # 1 label word (<= 64 classes) or 2 (COCO's 80, NUS-WIDE's 81)
-    if per > H.SHARD_ROWS_MAX or min(k, per) > H.RANK_K_MAX or lwords not in (1, 2) or nbits > 128:
+    if per > H.SHARD_ROWS_MAX or min(kmax, per) > H.RANK_K_MAX or lwords not in (1, 2) or nbits > 128:
         return None                                      # decided from values every rank shares: no rank goes another way
-    if ks is not None and (len(set(ks)) > H.MAX_CUTOFFS or H.merge_relbits_lds_bytes(world, k, nbits) > H.MERGE_LDS_LIMIT):
+    if multi and (len(set(k)) > H.MAX_CUTOFFS or H.merge_relbits_lds_bytes(world, kmax, nbits) > H.MERGE_LDS_LIMIT):
         return None                                      # likewise: world, max(k) and nbits are the same on every rank
     dev = q_local.device
-    both = torch.cat([q_local, qlab_local], dim=1).contiguous()           # codes | label words: one collective
-    both_all = torch.empty((world * Ql, words + lwords), dtype=both.dtype, device=dev)
-    _all_gather(both_all, both, group)
+    both_all = _gather_rows(torch.cat([q_local, qlab_local], dim=1), world, group)   # codes | label words: one collective
     q_all, ql_all = both_all[:, :words].contiguous(), both_all[:, words:words + lwords].contiguous()
-    kin = min(k, per)
-    if send_hint is None:
-        # exact sizing (one-off calls): every rank learns each query's global k-th distance T from the summed histograms, a
-        # shard's prefix = its rows with distance <= T, the exchange length = the longest prefix anywhere
+    kin = min(kmax, per)
+    if send_hint is None:                                # one-off call: a histogram pass, then the exact sizing
         cum = (H.hamming_hist(q_all, db_shard, nbits) if n_local > 0
                else torch.zeros((world * Ql, nbits + 2), dtype=torch.int32, device=dev))
-        cum_g = cum.clone()
-        _all_reduce(cum_g, dist.ReduceOp.SUM, group)
-        T = (cum_g[:, 1:] >= k).int().argmax(dim=1)
-        owed = torch.gather(cum, 1, (T + 1).unsqueeze(1).long()).max().reshape(1)
-        _all_reduce(owed, dist.ReduceOp.MAX, group)
-        send_hint = int(owed.item())
-    send = max(1, min(kin, int(send_hint)))
+        send = _exact_send(cum, kmax, kin, group)[0]
+    else:
+        send = _prefix_len(kin, send_hint)
     wire = torch.zeros((world * Ql, H.relbits_wire_words(send, nbits)), dtype=torch.int64, device=dev)
     if n_local > 0:
         got = H.hamming_shard_relbits(q_all, db_shard, labels_shard, ql_all, nbits, min(send, n_local), wire=wire, kin=send)
@@ -306,13 +303,10 @@ def sharded_hamming_map_at_k(q_local, qlab_local, db_shard, labels_shard, nbits,
     wire_r = torch.empty_like(wire)
     _all_to_all(wire_r, wire, group)                      # histogram + relevance string of a (query, shard) side by side
     need = torch.zeros(1, dtype=torch.int32, device=dev)
-    if ks is not None:
-        got = H.merge_relbits_map_ks(wire_r.view(world, Ql, -1), send, ks, nbits, need_out=need)
-        if got is None:
-            raise RuntimeError("sharded_hamming_map_at_k: the merged string does not fit although the shared checks passed")
-        return got[0], got[1], need
-    ap, nrel = H.merge_relbits_map(wire_r.view(world, Ql, -1), send, k, nbits, need_out=need)
-    return ap, nrel, need
+    got = (H.merge_relbits_map_ks if multi else H.merge_relbits_map)(wire_r.view(world, Ql, -1), send, k, nbits, need_out=need)
+    if got is None:
+        raise RuntimeError("sharded_hamming_map_at_k: the merged string does not fit although the shared checks passed")
+    return got[0], got[1], need
 
 
 def sharded_hamming_radius_hist(q_local, qlab_local, db_shard, labels_shard, nbits, group=None):
@@ -332,9 +326,7 @@ def sharded_hamming_radius_hist(q_local, qlab_local, db_shard, labels_shard, nbi
     dev = q_local.device
     both_all = torch.cat([q_local, qlab_local], dim=1).contiguous()          # codes | label words: one collective
     if world > 1:
-        both = both_all
-        both_all = torch.empty((world * Ql, words + lwords), dtype=both.dtype, device=dev)
-        _all_gather(both_all, both, group)
+        both_all = _gather_rows(both_all, world, group)
     q_all, ql_all = both_all[:, :words].contiguous(), both_all[:, words:].contiguous()
     tables = torch.zeros((2, world * Ql, nbits + 2), dtype=torch.int32, device=dev)
     n_local = db_shard.N if hasattr(db_shard, "N") else db_shard.shape[0]
@@ -357,7 +349,7 @@ def exchange_ok(needs, send_hint, kin):
     # the merge kernels report max_g cum[g][T+1] unclamped; a shard never owes more than `kin` = min(k, shard rows) entries
     # (with many ties at the k-th distance the raw count exceeds it although `kin` entries were exchanged: exact)
     worst = min(int(torch.stack([n.reshape(()) for n in needs]).max().item()), int(kin))
-    return worst <= max(1, min(int(kin), int(send_hint)))
+    return worst <= _prefix_len(kin, send_hint)
 
 
 def merge_knn_lists(vals, gidx, k, metric):
@@ -389,8 +381,7 @@ def sharded_knn_float(q_local, db_shard, k, metric, n_total, group=None):
     from .engine.get_knn import knn_float, knn_float_host
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
-    per = (n_total + world - 1) // world
-    lo = min(n_total, rank * per)
+    lo, _, per = shard_bounds(n_total, world, rank)
     if k > n_total:
         raise RuntimeError(f"selected index k out of range (k={k}, references={n_total})")
     q_local = q_local.float().contiguous()

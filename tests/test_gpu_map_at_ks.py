@@ -134,7 +134,7 @@ def test_merge_of_relevance_strings_at_several_cutoffs(short):
     bounds = ((0, 1000), (1000, 2000), (2000, 2700))
     parts = [(H.PreparedDB(c["rp"][lo:hi].contiguous(), 64), H.PreparedLabels(c["rlp"][lo:hi].contiguous())) for lo, hi in bounds]
     cums = torch.stack([H.hamming_hist(c["qp"], db, 64) for db, _ in parts])
-    need = H._prefix_need(cums, ks[-1])
+    need = int(H.owed_prefix(cums, cums.sum(0), ks[-1]).item())
     assert 2 <= need < 1000
     kin = need // 2 if short else need + 37
     wires = torch.zeros((3, 19, H.relbits_wire_words(kin, 64)), dtype=torch.int64, device="cuda")

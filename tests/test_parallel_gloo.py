@@ -99,6 +99,23 @@ def _fake_shard_relbits(q_packed, db, labels, qlab_packed, nbits, k, wire=None, 
     return wire
 
 
+def _owed(cum, k):
+    """The stand-ins' own statement of the prefix rule, by brute force: cum [G, Q, nbits + 2] (cum[g, q, b] = rows of shard g
+    with distance < b) -> the largest count, over shard and query, of rows no farther than the query's global k-th row."""
+    G, Q, _ = cum.shape
+    worst = 0
+    for q in range(Q):
+        total = cum[:, q].sum(0)
+        T = min(b for b in range(total.shape[0] - 1) if int(total[b + 1]) >= k)
+        worst = max(worst, max(int(cum[g, q, T + 1]) for g in range(G)))
+    return worst
+
+
+def _report_need(need_out, cum, k):
+    if need_out is not None:
+        need_out.copy_(torch.maximum(need_out, torch.tensor([_owed(cum, k)], dtype=torch.int32)))
+
+
 def _fake_merge_relbits(wire, kin, k, nbits, need_out=None):
     """Expand every shard's string to one 0/1 entry per list position, merge by (distance, shard, position), AP as the
     reference computes it (fp32 quotients, mean over the hits)."""
@@ -107,10 +124,7 @@ def _fake_merge_relbits(wire, kin, k, nbits, need_out=None):
     cum = wire[..., :hw].contiguous().view(torch.int32).reshape(G, Q, 2 * hw)[..., :nbits + 2].long()
     relbits = wire[..., hw:]
     W = relbits.shape[-1]
-    if need_out is not None:
-        T = (cum.sum(0)[:, 1:] >= k).int().argmax(dim=1)
-        owed = torch.gather(cum, 2, (T + 1).view(1, Q, 1).expand(G, Q, 1).long()).max()
-        need_out.copy_(torch.maximum(need_out, owed.reshape(1).int()))
+    _report_need(need_out, cum, k)
     sh = torch.arange(64)
     bits = ((relbits.unsqueeze(-1) >> sh) & 1).reshape(G, Q, W * 64)[:, :, :kin]
     pos = torch.arange(kin).view(1, 1, kin)
@@ -127,13 +141,17 @@ def _fake_merge_relbits(wire, kin, k, nbits, need_out=None):
     return ap.float(), nrel.int()
 
 
+def _fake_merge_relbits_ks(wire, kin, ks, nbits, need_out=None):
+    """Column i = the single-k stand-in at ks[i]; need_out refers to max(ks)."""
+    cols = [_fake_merge_relbits(wire, kin, k, nbits) for k in ks]
+    _fake_merge_relbits(wire, kin, max(ks), nbits, need_out=need_out)
+    return torch.stack([c[0] for c in cols], dim=1), torch.stack([c[1] for c in cols], dim=1)
+
+
 def _fake_merge_cum(idx_local, cum, shard_rows, k, nbits, need_out=None):
     """Expand the compact form (16-bit local rows + per-shard cumulative histograms) and merge as above."""
     G, Q, kin = idx_local.shape
-    if need_out is not None:       # longest prefix any shard owed: cum[g, q, T_q + 1], T_q = global k-th distance of query q
-        T = (cum.sum(0)[:, 1:] >= k).int().argmax(dim=1)
-        owed = torch.gather(cum, 2, (T + 1).view(1, Q, 1).expand(G, Q, 1).long()).max()
-        need_out.copy_(torch.maximum(need_out, owed.reshape(1).int()))
+    _report_need(need_out, cum, k)     # longest prefix any shard owed: cum[g, q, T_q + 1], T_q = global k-th distance of query q
     ids = (idx_local.long() & 0xffff) + (torch.arange(G) * shard_rows).view(G, 1, 1)
     pos = torch.arange(kin).view(1, 1, kin)
     # distance of position p of a sorted list = number of boundaries cum[1:] that are <= p
@@ -152,26 +170,36 @@ def _worker(rank, world, port, cases, nbits, ql, out_dir):
     H.hamming_topk, H.topk_merge, H.topk_merge_cum = _fake_topk, _fake_merge, _fake_merge_cum   # CPU stand-ins for the kernels
     H.hamming_hist, H.hamming_topk_rows16, H.hamming_shard_prefix = _fake_hist, _fake_rows16, _fake_shard_prefix
     out = {}
+
+    def counted(route, *args, **kwargs):
+        """sharded_hamming_topk with its collectives counted: one all_gather and two all_to_alls on every route, the two
+        all-reduces (SUM of the histograms, MAX of the prefix lengths) only where the exchange is sized exactly first."""
+        parallel.TRACE = parallel.ExchangeTrace()
+        got = parallel.sharded_hamming_topk(*args, **kwargs)
+        calls, parallel.TRACE = parallel.TRACE.calls, None
+        assert calls == {"all_gather": 1, "all_to_all": 2, "all_reduce": 2 if route == "trimmed" else 0}, (route, calls)
+        return got
+
     for n_db, k in cases:
         q_all, r = synth.random_codes(world * ql, n_db, nbits, seed=3)
         lo, hi, _ = parallel.shard_bounds(n_db, world, rank)
         for trim in (True, False):      # histogram-trimmed exchange and full-length exchange must agree
-            idx, d = parallel.sharded_hamming_topk(_pack(q_all[rank * ql:(rank + 1) * ql]), _pack(r[lo:hi]), nbits,
-                                                   k, n_db, trim=trim)
+            idx, d = counted("trimmed" if trim else "untrimmed", _pack(q_all[rank * ql:(rank + 1) * ql]), _pack(r[lo:hi]), nbits,
+                             k, n_db, trim=trim)
             out[(n_db, k, trim)] = (idx, d)
         # the one-step trimmed form (what shards beyond the two-step kernels' range take) gives the same lists
         keep, H.SHARD_ROWS_MAX = H.SHARD_ROWS_MAX, 0
-        idx1, d1 = parallel.sharded_hamming_topk(_pack(q_all[rank * ql:(rank + 1) * ql]), _pack(r[lo:hi]), nbits, k, n_db)
+        idx1, d1 = counted("trimmed", _pack(q_all[rank * ql:(rank + 1) * ql]), _pack(r[lo:hi]), nbits, k, n_db)
         H.SHARD_ROWS_MAX = keep
         assert torch.equal(idx1, out[(n_db, k, True)][0]) and torch.equal(d1, out[(n_db, k, True)][1])
         # hinted exchange (no host read): a generous hint is exact and verifies, a hint of 1 entry is flagged
         shard, kin = _pack(r[lo:hi]), min(k, parallel.shard_bounds(n_db, world, rank)[2])
         qs = _pack(q_all[rank * ql:(rank + 1) * ql])
-        idx_h, d_h, need = parallel.sharded_hamming_topk(qs, shard, nbits, k, n_db, send_hint=kin, return_need=True)
+        idx_h, d_h, need = counted("hinted", qs, shard, nbits, k, n_db, send_hint=kin, return_need=True)
         assert torch.equal(idx_h, out[(n_db, k, True)][0]) and torch.equal(d_h, out[(n_db, k, True)][1])
         assert parallel.exchange_ok([need], kin, kin)
         if int(need.item()) > 1:
-            *_, need1 = parallel.sharded_hamming_topk(qs, shard, nbits, k, n_db, send_hint=1, return_need=True)
+            *_, need1 = counted("hinted", qs, shard, nbits, k, n_db, send_hint=1, return_need=True)
             assert not parallel.exchange_ok([need1], 1, kin)
     torch.save(out, os.path.join(out_dir, f"r{rank}.pt"))
     dist.barrier()
@@ -186,7 +214,7 @@ def _map_worker(rank, world, port, cases, nbits, ql, out_dir, lc=12, p=0.2):
     from wvhash import parallel, synth
     from wvhash.engine import hamming as H
     H.hamming_shard_relbits, H.merge_relbits_map, H.relbits_wire_words = _fake_shard_relbits, _fake_merge_relbits, _wire_words
-    H.hamming_hist = _fake_hist
+    H.hamming_hist, H.merge_relbits_map_ks = _fake_hist, _fake_merge_relbits_ks
     out = {}
     for n_db, k in cases:
         q_all, r = synth.random_codes(world * ql, n_db, nbits, seed=3)
@@ -201,6 +229,19 @@ def _map_worker(rank, world, port, cases, nbits, ql, out_dir, lc=12, p=0.2):
             # a hinted (steady-state) call: ONE all_gather (codes + label words) and ONE all_to_all, nothing else
             assert calls == {"all_gather": 1, "all_to_all": 1, "all_reduce": 0 if hint is not None else 2}, calls
             out[(n_db, k, hint)] = (ap, nrel, need, max(1, min(min(k, per), hint)) if hint is not None else min(k, per))
+            # several cut-offs, unsorted and with a repeat: column i is the scalar call at ks[i]; exchange and `need` are
+            # those of the scalar call at max(ks) = k, collective for collective
+            ks = [k, max(1, k // 3), k]
+            parallel.TRACE = parallel.ExchangeTrace()
+            ap_s, nrel_s, need_s = parallel.sharded_hamming_map_at_k(_pack(q_all[sl]), _label_words(ql_all[sl]), _pack(r[lo:hi]),
+                                                                     _label_words(rl[lo:hi]), nbits, ks, n_db, hint)
+            calls_s, parallel.TRACE = parallel.TRACE.calls, None
+            assert calls_s == calls, (calls_s, calls)
+            assert tuple(ap_s.shape) == tuple(nrel_s.shape) == (ql, 3) and torch.equal(need_s, need)
+            for i, ki in enumerate(ks):
+                ap_i, nrel_i = (ap, nrel) if ki == k else parallel.sharded_hamming_map_at_k(
+                    _pack(q_all[sl]), _label_words(ql_all[sl]), _pack(r[lo:hi]), _label_words(rl[lo:hi]), nbits, ki, n_db, hint)[:2]
+                assert torch.equal(ap_s[:, i], ap_i) and torch.equal(nrel_s[:, i], nrel_i), (n_db, ks, hint, i)
     torch.save(out, os.path.join(out_dir, f"m{rank}.pt"))
     dist.barrier()
     dist.destroy_process_group()
