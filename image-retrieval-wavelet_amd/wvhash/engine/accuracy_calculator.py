@@ -7,7 +7,7 @@ class is self-contained (PML is not a dependency), keeps everything on the GPU -
 reference's own configuration, main/engine/evaluate.py:76-81; BASELINE config c0), on the host through the `_cpu` twins
 of the same entry points (csrc/host_rank.cpp; same integers, same AP bits) -- and routes the arithmetic through libwvhash:
   calc_hamming_dist       -> wv_hamming_dist        (:183-186)
-  calculate_maphashing    -> wv_hamming_topk + wv_map_at_k   (:203-231, the reported metric)
+  calculate_maphashing    -> wv_hamming_map_at_k, or wv_hamming_topk + wv_map_at_k   (:203-231, the reported metric)
   calculate_maphashing_at -> wv_hamming_map_at_ks / wv_map_at_ks: the same at several cut-offs from one ranking pass
   calculate_bit_balance / calculate_worst_bit_balance -> wv_bit_counts   (:188-200)
   calculate_map           -> get_knn + wv_map_at_k  (:156-167, torchmetrics RetrievalMAP)
@@ -16,17 +16,22 @@ of the same entry points (csrc/host_rank.cpp; same integers, same AP bits) -- an
                           -> wv_hamming_radius_hist (DSCH/_utils.py:469-493, 577-594: precision / recall by Hamming radius)
   calculate_ndcg_hamming (opt-in likewise) -> wv_label_overlap_hist + wv_ndcg_at_ks (DSCH/_utils.py:551-574: NDCG@ndcg_k)
 Ranking ties are broken by ascending reference index (see engine/get_knn.py).
+
+Two decisions have one place each.  Where it runs: engine/backend.py maps `device` to the primitives module, the tensor move
+and the float k-NN.  How a (query, reference) pair is packed, prepared and ranked: RankCache, the ranking session.  Every metric
+is one body over a session -- the shared one when `rank_cache=` was given, otherwise one made for that metric call and dropped
+with it, so that no list outlives the call.
 """
 import logging
 
 import torch
 
 from .. import _lib
-from . import hamming as H
-from . import hamming_host as HH
 from . import ndcg as ndcg_metrics
 from . import radius_metrics
-from .get_knn import get_knn, _to_gpu, _is_pm1
+from .backend import HOST, backend
+from .get_knn import get_knn, _is_pm1
+from .hamming import SHARD_ROWS_MAX
 
 LOGGER = logging.getLogger("RETRIEVAL")
 
@@ -36,95 +41,137 @@ _OPT_IN = ("precision_hamming_radius", "pr_curve_hamming", "ndcg_hamming")   # c
 
 
 class RankCache(object):
-    """Packed codes, packed labels and ranked lists of ONE (query, reference) embedding pair, shared by the calculators
-    of an evaluate_multi_k run: the database is packed once and ranked once at the largest k asked for; every smaller k
-    reads a prefix (the reference re-runs its whole per-query loop for every k, main/engine/evaluate.py:226-243).
+    """The ranking session of ONE (query, reference) embedding pair on one backend (`device` as in CustomCalculator): packed
+    codes, packed labels, the prepared database and its labels, ranked lists and AP columns, each made once.  Shared by the
+    calculators of an evaluate_multi_k run it ranks once at the largest k asked for and every smaller k reads a prefix (the
+    reference re-runs its whole per-query loop for every k, main/engine/evaluate.py:226-243).
     Entries are keyed by tensor identity (storage pointer, shape, version counter): new embeddings invalidate them."""
 
-    def __init__(self, kmax_hint=0, ks=()):
+    def __init__(self, kmax_hint=0, ks=(), device=None):
+        self.backend = backend(device)
         self.ks = sorted({int(k) for k in ks if isinstance(k, int) and not isinstance(k, bool) and k > 0})   # the run's cut-offs
         self.kmax_hint = max([int(kmax_hint)] + self.ks)
-        self._codes, self._labels, self._lists, self._aps, self._prep = {}, {}, None, None, None
+        self._codes, self._labels, self._lists, self._aps, self._db, self._dblabels = {}, None, None, None, None, None
 
     @staticmethod
     def _key(t):
         return (t.data_ptr(), tuple(t.shape), t.dtype, t._version)
 
-    def packed_codes(self, x):
-        key = self._key(x)
+    def packed_codes(self, x, key=None):
+        key = key or self._key(x)
         if key not in self._codes:
             self._codes = {k_: v for k_, v in self._codes.items() if len(self._codes) < 4}
-            self._codes[key] = H.pack_codes(x)
+            self._codes[key] = self.backend.H.pack_codes(x)
         return self._codes[key]
 
-    def packed_labels(self, query_labels, reference_labels):
-        key = (self._key(query_labels), self._key(reference_labels))
-        if key not in self._labels:
-            self._labels = {key: CustomCalculator._packed_labels(query_labels, reference_labels)}
-        return self._labels[key]
+    def packed_labels(self, query_labels, reference_labels, key=None):
+        key = key or (self._key(query_labels), self._key(reference_labels))
+        if self._labels is None or self._labels[0] != key:
+            if query_labels.ndim == 1:  # class-id labels: one-hot them onto bits
+                classes = torch.unique(torch.cat([query_labels, reference_labels]))
+                query_labels = (query_labels.unsqueeze(1) == classes).float()
+                reference_labels = (reference_labels.unsqueeze(1) == classes).float()
+            H = self.backend.H
+            self._labels, self._dblabels = (key, (H.pack_labels(query_labels), H.pack_labels(reference_labels))), None
+        return self._labels[1]
 
-    def lists(self, query, reference, k):
+    def _prepared_db(self, reference, make=True, key=None):
+        """PreparedDB of the reference set, laid out once per embedding pair (make=False: None when there is none yet)."""
+        key = key or self._key(reference)
+        if self._db is not None and self._db[0] == key:
+            return self._db[1]
+        if make:
+            self._db = (key, self.backend.H.PreparedDB(self.packed_codes(reference, key), reference.shape[1]))
+            return self._db[1]
+
+    def _ranking_db(self, reference):
+        """What hamming_topk ranks against: the prepared database if the session has it, a new prepared one beyond
+        SHARD_ROWS_MAX rows (virtual shards through the windowed kernel; never on the host), otherwise the packed codes."""
+        db = self._prepared_db(reference, make=reference.shape[0] > self.backend.H.SHARD_ROWS_MAX)
+        return db if db is not None else self.packed_codes(reference)
+
+    def _prepared_labels(self, rlp):
+        """PreparedLabels of the packed reference labels this session holds."""
+        if self._dblabels is None:
+            self._dblabels = self.backend.H.PreparedLabels(rlp)
+        return self._dblabels
+
+    def _has_lists(self, query, reference, k, want_dist=False):
+        got = self._lists
+        return (got is not None and got[0] == (self._key(query), self._key(reference)) and got[1].shape[1] >= k
+                and not (want_dist and got[2] is None))
+
+    def lists(self, query, reference, k, want_dist=False):
         """int32 [Q, >= k] ranked lists (ascending distance, then index); only the first k columns are meaningful to the caller."""
-        key = (self._key(query), self._key(reference))
-        if self._lists is None or self._lists[0] != key or self._lists[1].shape[1] < k:
+        if not self._has_lists(query, reference, k, want_dist):
+            db = self._ranking_db(reference)
             kk = min(reference.shape[0], max(k, self.kmax_hint))
-            idx, dist = H.hamming_topk(self.packed_codes(query), self.packed_codes(reference), reference.shape[1], kk)
-            self._lists = (key, idx, dist)
+            idx, dist = self.backend.H.hamming_topk(self.packed_codes(query), db, reference.shape[1], kk, want_dist=want_dist)
+            self._lists = ((self._key(query), self._key(reference)), idx, dist)
         return self._lists[1]
 
     def maphashing(self, query, query_labels, reference, reference_labels, topk, also=()):
         """Average precision per query at `topk` (float32 [Q]).  The first call for an embedding pair answers ALL the run's
-        cut-offs (and those in `also`: further cut-offs the caller will ask for next) from one pass and keeps the columns: from the cached lists (wv_map_at_ks) when a k-NN metric already made
-        them, otherwise from the fused ranking + AP pass (wv_hamming_map_at_ks), so that no [Q, k_max] list exists."""
+        cut-offs (and those in `also`: further cut-offs the caller will ask for next), MAX_CUTOFFS per pass, and keeps the
+        columns.  Each pass reads the session's lists when a k-NN metric already made them; otherwise it is the fused ranking +
+        AP kernel, so that no [Q, k_max] list exists; where that answers None (shape outside it; always on the host) the lists
+        are ranked at the largest cut-off and read.  One cut-off takes the single-k entry points, several the multi-k ones:
+        the same bits."""
+        H = self.backend.H
         num_ref, nbits = reference.shape
         topk = min(int(topk), num_ref)
-        key = (self._key(query), self._key(reference), self._key(query_labels), self._key(reference_labels))
+        key = (self._key(query), self._key(reference), self._key(query_labels), self._key(reference_labels))   # each tensor's key once
         if self._aps is None or self._aps[0] != key:
             self._aps = (key, {})
         done = self._aps[1]
         if topk not in done:
             want = sorted({min(int(k), num_ref) for k in (*self.ks, *also)} | {topk})
-            qlp, rlp = self.packed_labels(query_labels, reference_labels)
+            qlp, rlp = self.packed_labels(query_labels, reference_labels, key[2:])
             for s in range(0, len(want), H.MAX_CUTOFFS):
                 ks = want[s:s + H.MAX_CUTOFFS]
-                ap = None
-                have = self._lists is not None and self._lists[0] == key[:2] and self._lists[1].shape[1] >= ks[-1]
-                if not have and nbits <= 128 and rlp.shape[1] <= 2:
-                    prepared = self._prepared(reference, rlp)
-                    got = H.hamming_map_at_ks(self.packed_codes(query), prepared[0], prepared[1], qlp, nbits, ks)
-                    ap = got[0] if got is not None else None
-                if ap is None:
-                    ap = H.map_at_ks(self.lists(query, reference, ks[-1]), qlp, rlp, ks)[0]
-                for i, k in enumerate(ks):
-                    done[k] = ap[:, i]
+                got = None
+                if not self._has_lists(query, reference, ks[-1]) and nbits <= 128 and rlp.shape[1] <= 2:
+                    db, qp, labels = self._prepared_db(reference, key=key[1]), self.packed_codes(query, key[0]), self._prepared_labels(rlp)
+                    got = (H.hamming_map_at_k(qp, db, labels, qlp, nbits, ks[0]) if len(ks) == 1
+                           else H.hamming_map_at_ks(qp, db, labels, qlp, nbits, ks))
+                if got is None:
+                    idx = self.lists(query, reference, want[-1])
+                    got = H.map_at_k(idx, qlp, rlp, k=ks[0]) if len(ks) == 1 else H.map_at_ks(idx, qlp, rlp, ks)
+                done.update({k: got[0] if len(ks) == 1 else got[0][:, i] for i, k in enumerate(ks)})
         return done[topk]
 
+    def map_at_k(self, idx, query_labels, reference_labels, k=None):
+        """(ap, nrel) of lists the caller ranked (k-NN lists), over the session's packed labels."""
+        return self.backend.H.map_at_k(idx, *self.packed_labels(query_labels, reference_labels), k=k)
+
+    def hit_prefix(self, idx, query_labels, reference_labels):
+        """Running hit counts along the ranked lists, int32 [Q, k] (wv_hit_prefix)."""
+        return self.backend.H.hit_prefix(idx.int(), *self.packed_labels(query_labels, reference_labels))
+
     def radius_tables(self, query, query_labels, reference, reference_labels):
-        """(cum, cumrel) of hamming_radius_hist for the pair, from the cached packed codes / labels and prepared database."""
+        """(cum, cumrel) of hamming_radius_hist for the pair, from the packed codes / labels and the prepared database."""
         qlp, rlp = self.packed_labels(query_labels, reference_labels)
-        prepared = self._prepared(reference, rlp)
-        return H.hamming_radius_hist(self.packed_codes(query), prepared[0], prepared[1], qlp, reference.shape[1])
+        qp = self.packed_codes(query)
+        return self.backend.H.hamming_radius_hist(qp, self._prepared_db(reference), self._prepared_labels(rlp), qlp, reference.shape[1])
 
     def ndcg_sums(self, query, query_labels, reference, reference_labels, k):
-        """(dcg, idcg) float64 [Q, 1] at cut-off k from the cached packed codes / labels and prepared database."""
+        """(dcg, idcg) float64 [Q, 1] at cut-off k: from the session's lists when they reach k, otherwise from lists ranked
+        chunk by chunk (ndcg.LIST_BYTES_MAX) and dropped."""
+        H = self.backend.H
         qlp, rlp = self.packed_labels(query_labels, reference_labels)
-        qp, db, nbits = self.packed_codes(query), self._prepared(reference, rlp)[0], reference.shape[1]
-        return ndcg_metrics.ndcg_sums_packed(H, lambda lo, hi: H.hamming_topk(qp[lo:hi], db, nbits, k, want_dist=False)[0],
-                                             query.shape[0], qlp, rlp, [k])
-
-    def _prepared(self, reference, rlp):
-        """(PreparedDB, PreparedLabels) of the reference set, laid out once per embedding pair."""
-        key = (self._key(reference), rlp.data_ptr())
-        if self._prep is None or self._prep[0] != key:
-            self._prep = (key, (H.PreparedDB(self.packed_codes(reference), reference.shape[1]), H.PreparedLabels(rlp)))
-        return self._prep[1]
+        if self._has_lists(query, reference, k):
+            lists_of = lambda lo, hi: self._lists[1][lo:hi]
+        else:
+            qp, db, nbits = self.packed_codes(query), self._ranking_db(reference), reference.shape[1]
+            lists_of = lambda lo, hi: H.hamming_topk(qp[lo:hi], db, nbits, k, want_dist=False)[0]
+        return ndcg_metrics.ndcg_sums_packed(H, lists_of, query.shape[0], qlp, rlp, [k])
 
     def knn(self, reference, query, num_k, same_source):
-        """get_knn(..., distance_metric='hamming') from the cached ranking: (indices int64, inner products fp32)."""
+        """get_knn(..., distance_metric='hamming') from the session's ranking: (indices int64, inner products fp32)."""
         num_k += int(same_source)
         if num_k > reference.shape[0]:
             raise RuntimeError(f"selected index k out of range (k={num_k}, references={reference.shape[0]})")
-        idx = self.lists(query, reference, num_k)[:, :num_k]
+        idx = self.lists(query, reference, num_k, want_dist=True)[:, :num_k]
         ip = float(reference.shape[1]) - 2.0 * self._lists[2][:, :num_k].float()
         first = int(same_source)
         return idx[:, first:].long(), ip[:, first:]
@@ -154,10 +201,12 @@ class CustomCalculator(object):
         # to, main/engine/evaluate.py:76-81): the host twins of the same entry points -- explicit, never a fallback: without
         # a GPU and without device='cpu' every metric raises WvhashUnavailable.
         self.requested_device = device
-        self.host = device is not None and torch.device(device).type == "cpu"
-        self.H = HH if self.host else H
-        if self.host and self.rank_cache is not None:
-            raise ValueError("a shared RankCache holds GPU lists: not available with device='cpu'")
+        self.backend = backend(device)
+        self.host = self.backend is HOST
+        self._dev = self.backend.move       # tensor on the calculator's device (accuracy_calculator.py:290-293 moves everything to self.device)
+        if self.rank_cache is not None and self.rank_cache.backend is not self.backend:
+            side, own = ("GPU", "cpu") if self.host else ("host", "cuda")
+            raise ValueError(f"a shared RankCache holds {side} lists: not available with device='{own}'")
         self.original_function_dict = {name[len("calculate_"):]: getattr(self, name)
                                        for name in dir(self) if name.startswith("calculate_") and name not in _NOT_METRICS}
         self.check_primary_metrics(include, exclude)
@@ -178,11 +227,12 @@ class CustomCalculator(object):
         _lib.require_gpu()
         return torch.device("cuda", torch.cuda.current_device())
 
-    def _dev(self, x):
-        """Tensor on the calculator's device (accuracy_calculator.py:290-293 moves everything to self.device)."""
-        if not self.host:
-            return _to_gpu(x)
-        return (x if torch.is_tensor(x) else torch.as_tensor(x)).detach().cpu()
+    def _session(self, throw_away=True):
+        """The ranking session a metric talks to: the shared one, or (throw_away) one of its own that is dropped with the
+        metric call, lists and all."""
+        if self.rank_cache is not None:
+            return self.rank_cache
+        return RankCache(device=self.requested_device) if throw_away else None
 
     def check_primary_metrics(self, include=(), exclude=()):
         # unlike PML, names this implementation does not compute are tolerated in `exclude`
@@ -239,12 +289,13 @@ class CustomCalculator(object):
     def calc_hamming_dist(self, qB, rB):
         """0.5 * (B - qB @ rB.T) for +-1 codes (:183-186) -> fp32 [Q, N] like the reference."""
         qB, rB = self._dev(qB), self._dev(rB)
-        return self.H.hamming_dist(self.H.pack_codes(qB), self.H.pack_codes(rB), nbits=qB.shape[1]).float()
+        H = self.backend.H
+        return H.hamming_dist(H.pack_codes(qB), H.pack_codes(rB), nbits=qB.shape[1]).float()
 
     def per_bit_balance(self, reference):
         reference = self._dev(reference)
         nbits = reference.shape[1]
-        counts = self.H.bit_counts(self.H.pack_codes(reference, check=False), nbits)
+        counts = self.backend.H.bit_counts(self.backend.H.pack_codes(reference, check=False), nbits)
         frac_positive = counts.float() / float(reference.shape[0])
         return 1.0 - 2.0 * (frac_positive - 0.5).abs()
 
@@ -254,32 +305,12 @@ class CustomCalculator(object):
     def calculate_worst_bit_balance(self, reference, **kwargs):
         return self.per_bit_balance(reference).min().item()
 
-    def _ranked_lists(self, query, reference, topk):
-        """int32 [Q, >= topk]: the first topk columns are the ranked list (a shared RankCache may hold longer lists)."""
-        if self.rank_cache is not None:
-            return self.rank_cache.lists(query, reference, topk)
-        nbits = reference.shape[1]
-        rp = self.H.pack_codes(reference)
-        if rp.shape[0] > self.H.SHARD_ROWS_MAX:          # large database: virtual shards through the windowed kernel
-            rp = self.H.PreparedDB(rp, nbits)
-        return self.H.hamming_topk(self.H.pack_codes(query), rp, nbits, topk, want_dist=False)[0]
-
-    @staticmethod
-    def _packed_labels(query_labels, reference_labels, Hm=H):
-        if query_labels.ndim == 1:  # class-id labels: one-hot them onto bits
-            classes = torch.unique(torch.cat([query_labels, reference_labels]))
-            query_labels = (query_labels.unsqueeze(1) == classes).float()
-            reference_labels = (reference_labels.unsqueeze(1) == classes).float()
-        return Hm.pack_labels(query_labels), Hm.pack_labels(reference_labels)
-
     def _average_precisions(self, idx, query_labels, reference_labels, k=None):
-        packed = (self.rank_cache.packed_labels(query_labels, reference_labels) if self.rank_cache is not None
-                  else self._packed_labels(query_labels, reference_labels, self.H))
-        return self.H.map_at_k(idx, *packed, k=k)
+        return self._session().map_at_k(idx, query_labels, reference_labels, k=k)
 
     def _hits(self, idx, query_labels, reference_labels):
         """Running hit counts along the ranked lists, int32 [Q, k] (wv_hit_prefix)."""
-        return self.H.hit_prefix(idx.int(), *self._packed_labels(query_labels, reference_labels, self.H))
+        return self._session().hit_prefix(idx, query_labels, reference_labels)
 
     def calculate_maphashing(self, query, query_labels, reference, reference_labels, topk,
                              ref_includes_query=False, return_per_query=False, **kwargs):
@@ -294,25 +325,8 @@ class CustomCalculator(object):
         num_query = query.shape[0]
         if num_query == 0:
             raise ZeroDivisionError("calculate_maphashing: no queries")
-        ap = None
-        nbits = reference.shape[1]
-        if self.rank_cache is None and not self.host and nbits <= 128:
-            # one k, nothing to share: ranking and AP in one kernel, the lists never leave the GPU's LDS
-            # (same numbers as the two steps below; None = shape outside the fused kernel)
-            qlp, rlp = self._packed_labels(query_labels, reference_labels)
-            if rlp.shape[1] <= 2:
-                prepared = H.PreparedDB(H.pack_codes(reference), nbits)
-                fused = H.hamming_map_at_k(H.pack_codes(query), prepared, H.PreparedLabels(rlp), qlp, nbits, topk)
-                if fused is not None:
-                    ap = fused[0]
-                else:                                    # outside the fused kernel: rank with the database already prepared
-                    idx = H.hamming_topk(H.pack_codes(query), prepared, nbits, topk, want_dist=False)[0]
-                    ap, _ = H.map_at_k(idx, qlp, rlp, k=topk)
-        if ap is None and self.rank_cache is not None:
-            ap = self.rank_cache.maphashing(query, query_labels, reference, reference_labels, topk)   # all the run's k at once
-        if ap is None:
-            idx = self._ranked_lists(query, reference, topk)
-            ap, _ = self._average_precisions(idx, query_labels, reference_labels, k=topk)
+        # ranking and AP in one kernel where the shape allows and no list exists yet; otherwise lists, then AP (same numbers)
+        ap = self._session().maphashing(query, query_labels, reference, reference_labels, topk)
         result = ap.double().sum().item() / num_query
         if return_per_query:
             return result, ap
@@ -328,22 +342,12 @@ class CustomCalculator(object):
             raise ValueError("calculate_maphashing_at: ks must be a non-empty sequence of positive ints")
         query, reference = self._dev(query), self._dev(reference)
         query_labels, reference_labels = self._dev(query_labels), self._dev(reference_labels)
-        num_query, (num_ref, nbits) = query.shape[0], reference.shape
+        num_query, num_ref = query.shape[0], reference.shape[0]
         if num_query == 0:
             raise ZeroDivisionError("calculate_maphashing_at: no queries")
         eff = [min(k, num_ref) for k in ks]
-        cols = {}
-        if self.host:
-            qlp, rlp = self._packed_labels(query_labels, reference_labels, HH)
-            uniq = sorted(set(eff))
-            idx = HH.hamming_topk(HH.pack_codes(query), HH.pack_codes(reference), nbits, uniq[-1], want_dist=False)[0]
-            for s in range(0, len(uniq), HH.MAX_CUTOFFS):
-                ap = HH.map_at_ks(idx, qlp, rlp, uniq[s:s + HH.MAX_CUTOFFS])[0]
-                cols.update({k: ap[:, i] for i, k in enumerate(uniq[s:s + HH.MAX_CUTOFFS])})
-        else:
-            cache = self.rank_cache if self.rank_cache is not None else RankCache()
-            for k in eff:
-                cols[k] = cache.maphashing(query, query_labels, reference, reference_labels, k, also=eff)
+        session = self._session()
+        cols = {k: session.maphashing(query, query_labels, reference, reference_labels, k, also=eff) for k in eff}
         out = {}
         for k, ke in zip(ks, eff):
             value = cols[ke].double().sum().item() / num_query
@@ -402,8 +406,8 @@ class CustomCalculator(object):
         queries that are not lone and have a relevant item; writes the curve, returns 0."""
         query, reference = self._dev(query), self._dev(reference)
         query_labels, reference_labels = self._dev(query_labels), self._dev(reference_labels)
-        hits = self._hits(self._ranked_lists(query, reference, reference.shape[0])[:, :reference.shape[0]], query_labels,
-                          reference_labels)
+        session, num_ref = self._session(), reference.shape[0]
+        hits = session.hit_prefix(session.lists(query, reference, num_ref)[:, :num_ref], query_labels, reference_labels)
         ok = hits[:, -1] > 0
         if not_lone_query_mask is not None:
             ok &= not_lone_query_mask
@@ -420,15 +424,10 @@ class CustomCalculator(object):
         if query.dim() != 2 or query.shape[1] != nbits or nbits > 128 or not (_is_pm1(query) and _is_pm1(reference)):
             raise ValueError("Hamming-radius metrics need +-1 codes of at most 128 bits "
                              f"(got {tuple(query.shape)} / {tuple(reference.shape)})")
-        if self.rank_cache is not None:
-            got = self.rank_cache.radius_tables(query, query_labels, reference, reference_labels)
-        else:
-            qlp, rlp = self._packed_labels(query_labels, reference_labels, self.H)
-            got = self.H.hamming_radius_hist(self.H.pack_codes(query), self.H.PreparedDB(self.H.pack_codes(reference), nbits),
-                                             self.H.PreparedLabels(rlp), qlp, nbits)
+        got = self._session().radius_tables(query, query_labels, reference, reference_labels)
         if got is None:
             raise ValueError("Hamming-radius metrics need labels of at most 128 classes and a database of at most "
-                             f"{64 * H.SHARD_ROWS_MAX} rows on the GPU (got {tuple(reference_labels.shape)} labels, "
+                             f"{64 * SHARD_ROWS_MAX} rows on the GPU (got {tuple(reference_labels.shape)} labels, "
                              f"{reference.shape[0]} rows)")
         return got
 
@@ -465,14 +464,12 @@ class CustomCalculator(object):
         k = num_ref if k < 0 or k > num_ref else k
         if query.dim() != 2 or query.shape[1] != nbits or nbits > 128 or not (_is_pm1(query) and _is_pm1(reference)):
             raise ValueError(f"ndcg_hamming needs +-1 codes of at most 128 bits (got {tuple(query.shape)} / {tuple(reference.shape)})")
-        if query_labels.dim() != 2 or reference_labels.dim() != 2 or reference_labels.shape[1] > 128 or k < 1:
+        if query_labels.dim() != 2 or reference_labels.dim() != 2 or query_labels.shape[1] != reference_labels.shape[1] \
+                or reference_labels.shape[1] > 128 or k < 1:
             raise ValueError("ndcg_hamming needs multi-hot labels of at most 128 classes and a cut-off >= 1 "
                              f"(got {tuple(reference_labels.shape)} labels, ndcg_k={self.ndcg_k})")
-        if self.rank_cache is not None:
-            sums = self.rank_cache.ndcg_sums(query, query_labels, reference, reference_labels, k)
-            return ndcg_metrics.ndcg_from_sums(*sums)[0].item()
-        return ndcg_metrics.NDCG(query, reference, query_labels, reference_labels, what=1, k=k,
-                                 device="cpu" if self.host else None)
+        sums = self._session().ndcg_sums(query, query_labels, reference, reference_labels, k)
+        return ndcg_metrics.ndcg_from_sums(*sums)[0].item()
 
     def _knn_relevance(self, query_labels, knn_labels, k):
         return self.label_comparison_fn(query_labels[:, None], knn_labels[:, :k]) if query_labels.ndim > 1 \
@@ -509,29 +506,26 @@ class CustomCalculator(object):
         }
 
         knn_indices = None
-        if "pr_rc_hashing" in self.get_curr_metrics():
-            kwargs["not_lone_query_mask"] = (self._match_counts(query_labels, reference_labels)
-                                             - int(embeddings_come_from_same_source)) > 0
-        if any(x in self.requires_knn() for x in self.get_curr_metrics()):
+        wants_knn = any(x in self.requires_knn() for x in self.get_curr_metrics())
+        if wants_knn or "pr_rc_hashing" in self.get_curr_metrics():
             match_counts = self._match_counts(query_labels, reference_labels)
-            self_count = int(embeddings_come_from_same_source)
-            not_lone_query_mask = (match_counts - self_count) > 0
+            not_lone_query_mask = (match_counts - int(embeddings_come_from_same_source)) > 0
+            kwargs["not_lone_query_mask"] = not_lone_query_mask
+        if wants_knn:
             num_k = self.determine_k(match_counts, len(reference), embeddings_come_from_same_source)
-            if (self.rank_cache is not None and self.distance_metric == "hamming" and reference.shape[1] <= 128
+            shared = self._session(throw_away=False)     # its lists answer +-1 codes under the hamming metric
+            if (shared is not None and self.distance_metric == "hamming" and reference.shape[1] <= 128
                     and _is_pm1(reference) and _is_pm1(query)):
-                knn_indices, knn_distances = self.rank_cache.knn(reference, query, num_k, embeddings_come_from_same_source)
-            elif self.host:
-                knn_indices, knn_distances = self._host_knn(reference, query, num_k, embeddings_come_from_same_source)
+                knn_indices, knn_distances = shared.knn(reference, query, num_k, embeddings_come_from_same_source)
             else:
                 knn_indices, knn_distances = get_knn(
                     reference, query, num_k, embeddings_come_from_same_source,
-                    with_faiss=self.with_faiss, distance_metric=self.distance_metric,
+                    with_faiss=self.with_faiss, distance_metric=self.distance_metric, device=self.requested_device,
                 )
             if not bool(not_lone_query_mask.any()):
                 LOGGER.warning("None of the query labels are in the reference set.")
             kwargs["knn_indices"] = knn_indices
             kwargs["knn_distances"] = knn_distances
-            kwargs["not_lone_query_mask"] = not_lone_query_mask
             if any(m.startswith("recall_at_") or m == "precision_at_1" for m in self.get_curr_metrics()):
                 kwargs["knn_labels"] = reference_labels[knn_indices[:, :1000]]
 
@@ -539,25 +533,6 @@ class CustomCalculator(object):
         if return_indices:
             return knn_indices, result
         return result
-
-    def _host_knn(self, reference, query, num_k, same_source):
-        """get_knn (get_knn.py:9-24) on the host: +-1 codes under the hamming metric through the packed twins, everything
-        else through wv_knn_float_cpu -- the same lists and values as the GPU path in both cases."""
-        from .get_knn import knn_float_host
-        num_k += int(same_source)
-        nbits = reference.shape[1]
-        if num_k > reference.shape[0]:
-            raise RuntimeError(f"selected index k out of range (k={num_k}, references={reference.shape[0]})")
-        first = int(same_source)
-        if self.distance_metric == "hamming" and nbits <= 128 and _is_pm1(reference) and _is_pm1(query):
-            idx, dist = HH.hamming_topk(HH.pack_codes(query, check=False), HH.pack_codes(reference, check=False), nbits, num_k)
-            return idx[:, first:].long(), (float(nbits) - 2.0 * dist.float())[:, first:]
-        if self.distance_metric in ("hamming", "cosine"):
-            metric = _lib.WV_METRIC_IP
-        else:                                   # faiss IndexFlatL2 returns squared distances, torch.cdist the root
-            metric = _lib.WV_METRIC_L2_SQUARED if self.with_faiss else _lib.WV_METRIC_L2
-        val, idx = knn_float_host(reference, query, num_k, metric)
-        return idx[:, first:].long(), val[:, first:]
 
     def _get_accuracy(self, function_dict, **kwargs):
         return {k: v(**kwargs) for k, v in function_dict.items()}

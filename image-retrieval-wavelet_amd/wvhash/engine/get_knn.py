@@ -1,5 +1,6 @@
 """k-NN of queries vs references on the GPU -- same signature and return order as
-/root/reference/main/engine/get_knn.py:9-24.
+/root/reference/main/engine/get_knn.py:9-24 -- or, with the trailing keyword ``device='cpu'``, through the host twins: the
+same lists and values.
 
 * ``distance_metric in ("hamming", "cosine")``: scores = q @ r.T, top-k largest (get_knn.py:63-66).
   +-1 codes take the bit-packed XOR/popcount kernel; the returned "distances" are the same inner
@@ -16,7 +17,6 @@ import logging
 import torch
 
 from .. import _lib
-from . import hamming as H
 
 LOGGER = logging.getLogger("RETRIEVAL")
 
@@ -89,31 +89,31 @@ def rank_scores(scores, k, descending=False, sqrt=False):
     return val, idx
 
 
-def get_knn(references, queries, num_k, embeddings_come_from_same_source, with_faiss=True, distance_metric="l2"):
+def get_knn(references, queries, num_k, embeddings_come_from_same_source, with_faiss=True, distance_metric="l2", device=None):
+    from .backend import backend                    # backend.py imports this module
+    B = backend(device)
     num_k += embeddings_come_from_same_source
 
     LOGGER.info("running k-nn with k=%d" % num_k)
     LOGGER.info("embedding dimensionality is %d" % references.size(-1))
     LOGGER.info(f"distance metric: {distance_metric}")
 
-    references, queries = _to_gpu(references), _to_gpu(queries)
+    references, queries = B.move(references), B.move(queries)
     if num_k > references.shape[0]:
         raise RuntimeError(f"selected index k out of range (k={num_k}, references={references.shape[0]})")
 
     nbits = references.shape[1]
     if distance_metric == "hamming" and nbits <= 128 and _is_pm1(references) and _is_pm1(queries):
-        idx, dist = H.hamming_topk(H.pack_codes(queries, check=False), H.pack_codes(references, check=False),
-                                   nbits, num_k)
+        idx, dist = B.H.hamming_topk(B.H.pack_codes(queries, check=False), B.H.pack_codes(references, check=False),
+                                     nbits, num_k)
         distances = float(nbits) - 2.0 * dist.float()
-        indices = idx.long()
     elif distance_metric in ["hamming", "cosine"]:
-        distances, idx = knn_float(references, queries, num_k, _lib.WV_METRIC_IP)
-        indices = idx.long()
+        distances, idx = B.knn_float(references, queries, num_k, _lib.WV_METRIC_IP)
     else:
         # IndexFlatL2.search returns squared L2 (get_knn.py:38-39,55), torch.cdist the root (:67-69); same neighbours
-        distances, idx = knn_float(references, queries, num_k,
-                                   _lib.WV_METRIC_L2_SQUARED if with_faiss else _lib.WV_METRIC_L2)
-        indices = idx.long()
+        distances, idx = B.knn_float(references, queries, num_k,
+                                     _lib.WV_METRIC_L2_SQUARED if with_faiss else _lib.WV_METRIC_L2)
+    indices = idx.long()
 
     if embeddings_come_from_same_source:
         return indices[:, 1:], distances[:, 1:]

@@ -1,5 +1,6 @@
 """Host-side Hamming retrieval primitives: the `_cpu` twins of libwvhash.so (csrc/host_rank.cpp) behind the names of
-engine/hamming.py, on CPU tensors.  Used ONLY by CustomCalculator(device='cpu') -- the configuration the reference itself
+engine/hamming.py, on CPU tensors.  This is the module of the host backend (engine/backend.py): what an explicit device='cpu'
+selects in CustomCalculator, RankCache, get_knn, NDCG / ndcg_at / p_topK and the radius metrics -- the configuration the reference itself
 runs its calculator in (/root/reference/main/engine/evaluate.py:76-81, accuracy_calculator.py:290-293) and BASELINE config
 c0 ("CPU ... plumbing, no GPU").  Same integers as the kernels; average precision bit-identical (same summation order).
 No GPU is touched and none is needed."""
@@ -83,7 +84,7 @@ def hamming_topk(q_packed, db, nbits, k, idx_offset=0, workspace=None, want_dist
     if want_cum:
         raise NotImplementedError("hamming_topk on the host: histograms are a by-product of the sharded GPU search only")
     lib = _lib.load()
-    q_packed, db = _host(q_packed), _host(db)
+    q_packed, db = _host(q_packed), _host(db.packed if isinstance(db, PreparedDB) else db)
     Q, words = q_packed.shape
     N = db.shape[0]
     if db.shape[1] != words or words != _words(nbits):
@@ -96,48 +97,34 @@ def hamming_topk(q_packed, db, nbits, k, idx_offset=0, workspace=None, want_dist
     return idx, dist
 
 
-def map_at_k(idx, qlab_packed, dblab_packed, k=None):
+def _map_at(what, idx, qlab_packed, dblab_packed, k, ks=None):
+    from .hamming import _cuts, _columns
     lib = _lib.load()
     idx = _host(idx, torch.int32) if idx.stride(-1) != 1 or idx.dtype != torch.int32 or idx.is_cuda else idx
     qlab_packed, dblab_packed = _host(qlab_packed), _host(dblab_packed)
     Q, kfull = idx.shape
-    k = kfull if k is None else int(k)
-    if not 1 <= k <= kfull:
-        raise ValueError(f"map_at_k: k={k} outside the lists' length {kfull}")
+    cargs, tail, cols, kmax = _cuts(what, k, ks)
+    if not 1 <= kmax <= kfull:
+        raise ValueError(f"{what}: cut-off {kmax} outside the lists' length {kfull}")
     lw = qlab_packed.shape[1]
     if dblab_packed.shape[1] != lw:
-        raise ValueError("map_at_k: label widths differ")
-    ap = torch.empty(Q, dtype=torch.float32)
-    nrel = torch.empty(Q, dtype=torch.int32)
+        raise ValueError(f"{what}: label widths differ")
+    ap = torch.empty((Q,) + tail, dtype=torch.float32)
+    nrel = torch.empty((Q,) + tail, dtype=torch.int32)
     if Q:
-        _lib.check(lib.wv_map_at_k_cpu(_lib.ptr(idx), idx.stride(0), Q, k, _lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw,
-                                       _lib.ptr(ap), _lib.ptr(nrel)), "wv_map_at_k_cpu")
-    return ap, nrel
+        entry = "wv_map_at_k_cpu" if ks is None else "wv_map_at_ks_cpu"
+        _lib.check(getattr(lib, entry)(_lib.ptr(idx), idx.stride(0), Q, *cargs, _lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw,
+                                       _lib.ptr(ap), _lib.ptr(nrel)), entry)
+    return _columns(ap, nrel, cols)
+
+
+def map_at_k(idx, qlab_packed, dblab_packed, k=None):
+    return _map_at("map_at_k", idx, qlab_packed, dblab_packed, idx.shape[1] if k is None else int(k))
 
 
 def map_at_ks(idx, qlab_packed, dblab_packed, ks):
     """map_at_k for several cut-offs from one walk -> (ap float32 [Q, len(ks)], nrel int32 [Q, len(ks)])."""
-    lib = _lib.load()
-    idx = _host(idx, torch.int32) if idx.stride(-1) != 1 or idx.dtype != torch.int32 or idx.is_cuda else idx
-    qlab_packed, dblab_packed = _host(qlab_packed), _host(dblab_packed)
-    Q, kfull = idx.shape
-    ks = [int(k) for k in ks]
-    uniq = sorted(set(ks))
-    if not uniq or len(uniq) > MAX_CUTOFFS:
-        raise ValueError(f"map_at_ks: {len(uniq)} different cut-offs (1..{MAX_CUTOFFS} per call)")
-    if uniq[0] < 1 or uniq[-1] > kfull:
-        raise ValueError(f"map_at_ks: cut-offs {uniq[0]}..{uniq[-1]} outside the lists' length {kfull}")
-    lw = qlab_packed.shape[1]
-    if dblab_packed.shape[1] != lw:
-        raise ValueError("map_at_ks: label widths differ")
-    ap = torch.empty((Q, len(uniq)), dtype=torch.float32)
-    nrel = torch.empty((Q, len(uniq)), dtype=torch.int32)
-    if Q:
-        _lib.check(lib.wv_map_at_ks_cpu(_lib.ptr(idx), idx.stride(0), Q, (ctypes.c_int * len(uniq))(*uniq), len(uniq),
-                                        _lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw, _lib.ptr(ap), _lib.ptr(nrel)),
-                   "wv_map_at_ks_cpu")
-    sel = torch.tensor([uniq.index(k) for k in ks], dtype=torch.long)
-    return ap.index_select(1, sel), nrel.index_select(1, sel)
+    return _map_at("map_at_ks", idx, qlab_packed, dblab_packed, None, ks)
 
 
 def hit_prefix(idx, qlab_packed, dblab_packed):

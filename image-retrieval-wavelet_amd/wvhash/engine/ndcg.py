@@ -14,9 +14,8 @@ p_topK (:496-513) is relevant entries / K at each cut-off: the hit counts wv_ham
 import torch
 
 from .. import _lib
-from . import hamming as H
-from . import hamming_host as HH
-from .get_knn import _to_gpu, knn_float, knn_float_host
+from .backend import backend
+from .hamming import MAX_CUTOFFS
 
 LIST_BYTES_MAX = 256 << 20          # the ranked lists of one query chunk (int32 [chunk, k_max]) stay below 256 MB
 P_TOPK_DEFAULT = (1, 100, 200, 300, 400, 500, 600, 700, 800, 900, 1000)
@@ -36,10 +35,6 @@ def ndcg_from_sums(dcg, idcg):
     return ratio.sum(0) / torch.full((), float(dcg.shape[0]), dtype=torch.float64, device=dcg.device)
 
 
-def _host(device):
-    return device is not None and torch.device(device).type == "cpu"
-
-
 def _chunk(kmax):
     return max(1, LIST_BYTES_MAX // (4 * max(int(kmax), 1)))
 
@@ -55,9 +50,8 @@ def ndcg_sums_packed(Hm, lists_of, Q, qlp, rlp, ks):
 
 
 def _prepare(qF, rF, qL, rL, device, what_name):
-    host = _host(device)
-    move = (lambda t: (t if torch.is_tensor(t) else torch.as_tensor(t)).detach().cpu()) if host else _to_gpu
-    q, r, ql, rl = (move(t) for t in (qF, rF, qL, rL))
+    B = backend(device)
+    q, r, ql, rl = (B.move(t) for t in (qF, rF, qL, rL))
     if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1] or ql.dim() != 2 or rl.dim() != 2 or ql.shape[1] != rl.shape[1] \
             or ql.shape[0] != q.shape[0] or rl.shape[0] != r.shape[0]:
         raise ValueError(f"{what_name}: expected [Q, D] / [N, D] features and [Q, classes] / [N, classes] multi-hot labels")
@@ -65,44 +59,43 @@ def _prepare(qF, rF, qL, rL, device, what_name):
         raise ValueError(f"{what_name}: at most 128 classes (got {rl.shape[1]})")
     if q.shape[0] == 0 or r.shape[0] == 0:
         raise ZeroDivisionError(f"{what_name}: no queries or no database rows")
-    return host, (HH if host else H), q, r, ql, rl
+    return B, q, r, ql, rl
 
 
-def _ranker(Hm, host, q, r, what, kmax):
+def _ranker(B, q, r, what, kmax):
     """lists_of(lo, hi) for the ranking `what` of NDCG: 0 cosine, 1 Hamming, 2 squared L2."""
     if what == 1:
         nbits = q.shape[1]
         if nbits > 128:
             raise ValueError(f"NDCG(what=1): +-1 codes of at most 128 bits (got {nbits})")
-        qp, rp = Hm.pack_codes(q), Hm.pack_codes(r)           # raises ValueError for anything but exactly +1 / -1
-        db = Hm.PreparedDB(rp, nbits) if rp.shape[0] > Hm.SHARD_ROWS_MAX else rp
-        return lambda lo, hi: Hm.hamming_topk(qp[lo:hi], db, nbits, kmax, want_dist=False)[0]
+        qp, rp = B.H.pack_codes(q), B.H.pack_codes(r)         # raises ValueError for anything but exactly +1 / -1
+        db = B.H.PreparedDB(rp, nbits) if rp.shape[0] > B.H.SHARD_ROWS_MAX else rp
+        return lambda lo, hi: B.H.hamming_topk(qp[lo:hi], db, nbits, kmax, want_dist=False)[0]
     if what not in (0, 2):
         raise ValueError(f"NDCG: what={what} (0 cosine, 1 Hamming, 2 Euclidean)")
     q, r = q.float(), r.float()
     if what == 0:                                             # rows normalised like the reference's cos()
         q, r = q / q.norm(dim=1, keepdim=True), r / r.norm(dim=1, keepdim=True)
     metric = _lib.WV_METRIC_IP if what == 0 else _lib.WV_METRIC_L2_SQUARED
-    knn = knn_float_host if host else knn_float
-    return lambda lo, hi: knn(r, q[lo:hi], kmax, metric)[1]
+    return lambda lo, hi: B.knn_float(r, q[lo:hi], kmax, metric)[1]
 
 
 def ndcg_at(qF, rF, qL, rL, ks, what=1, device=None):
     """NDCG at several cut-offs from ONE ranking -> float64 [len(ks)] (on the device that computed it).  ks: positive ints,
     any order; a cut-off beyond the database clips at its size.  Arguments as NDCG."""
-    host, Hm, q, r, ql, rl = _prepare(qF, rF, qL, rL, device, "ndcg_at")
+    B, q, r, ql, rl = _prepare(qF, rF, qL, rL, device, "ndcg_at")
     N = r.shape[0]
     ks = [int(k) for k in ks]
     if not ks or min(ks) < 1:
         raise ValueError("ndcg_at: ks must be a non-empty sequence of positive ints")
     eff = [min(k, N) for k in ks]
     uniq = sorted(set(eff))
-    qlp, rlp = Hm.pack_labels(ql), Hm.pack_labels(rl)
-    lists_of = _ranker(Hm, host, q, r, what, uniq[-1])
+    qlp, rlp = B.H.pack_labels(ql), B.H.pack_labels(rl)
+    lists_of = _ranker(B, q, r, what, uniq[-1])
     cols = {}
-    for s in range(0, len(uniq), H.MAX_CUTOFFS):
-        part = uniq[s:s + H.MAX_CUTOFFS]
-        vals = ndcg_from_sums(*ndcg_sums_packed(Hm, lists_of, q.shape[0], qlp, rlp, part))
+    for s in range(0, len(uniq), MAX_CUTOFFS):
+        part = uniq[s:s + MAX_CUTOFFS]
+        vals = ndcg_from_sums(*ndcg_sums_packed(B.H, lists_of, q.shape[0], qlp, rlp, part))
         cols.update({k: vals[i] for i, k in enumerate(part)})
     return torch.stack([cols[k] for k in eff])
 
@@ -123,7 +116,8 @@ def p_topK(qB, rB, qL, rL, K=None, device=None):
     at each min(K_i, N) the relevant entries among the K_i nearest rows / that number, mean over ALL queries.  The counts are
     the nrel column of wv_hamming_map_at_ks (where that kernel does not cover the shape: hamming_topk + map_at_ks); float64
     from exact integers."""
-    host, Hm, q, r, ql, rl = _prepare(qB, rB, qL, rL, device, "p_topK")
+    B, q, r, ql, rl = _prepare(qB, rB, qL, rL, device, "p_topK")
+    Hm = B.H
     K = list(P_TOPK_DEFAULT) if K is None else [int(x) for x in K]
     if not K or min(K) < 1:
         raise ValueError("p_topK: K must be a non-empty sequence of positive ints")
@@ -134,16 +128,15 @@ def p_topK(qB, rB, qL, rL, K=None, device=None):
     uniq = sorted(set(eff))
     qp, rp = Hm.pack_codes(q), Hm.pack_codes(r)
     qlp, rlp = Hm.pack_labels(ql), Hm.pack_labels(rl)
-    prepared = None if host else (H.PreparedDB(rp, nbits), H.PreparedLabels(rlp))
+    db, labels = Hm.PreparedDB(rp, nbits), Hm.PreparedLabels(rlp)
     cols = {}
-    for s in range(0, len(uniq), H.MAX_CUTOFFS):
-        part = uniq[s:s + H.MAX_CUTOFFS]
-        got = None if host else H.hamming_map_at_ks(qp, prepared[0], prepared[1], qlp, nbits, part)
+    for s in range(0, len(uniq), MAX_CUTOFFS):
+        part = uniq[s:s + MAX_CUTOFFS]
+        got = Hm.hamming_map_at_ks(qp, db, labels, qlp, nbits, part)      # None: outside the fused kernel (always, on the host)
         if got is not None:
             nrel = got[1]
         else:
             step = _chunk(part[-1])
-            db = rp if host else prepared[0]
             nrel = torch.cat([Hm.map_at_ks(Hm.hamming_topk(qp[lo:lo + step], db, nbits, part[-1], want_dist=False)[0],
                                            qlp[lo:lo + step], rlp, part)[1] for lo in range(0, Q, step)])
         cols.update({k: nrel[:, i].long().sum() for i, k in enumerate(part)})      # exact integers

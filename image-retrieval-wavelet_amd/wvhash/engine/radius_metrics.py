@@ -8,9 +8,8 @@ two small integer tables per query -- rows at distance < b, and those of them th
 """
 import torch
 
-from . import hamming as H
-from . import hamming_host as HH
-from .get_knn import _to_gpu
+from .backend import backend
+from .hamming import SHARD_ROWS_MAX
 
 
 def _tables(cum, cumrel):
@@ -48,17 +47,12 @@ def precision_within_radius(cum, cumrel, radius=2):
     return torch.where(found > 0, hit / found.clamp(min=1), torch.zeros_like(hit)).mean().item()
 
 
-def _as_tensor(x):
-    return x if torch.is_tensor(x) else torch.as_tensor(x)
-
-
 def _radius_tables(query_codes, database_codes, query_labels, database_labels, device, what):
     """+-1 codes and multi-hot labels -> (cum, cumrel): packed, prepared and counted on the GPU, or with an explicit
     device='cpu' through the host twins.  Nothing the caller passed is modified."""
-    host = device is not None and torch.device(device).type == "cpu"
-    Hm = HH if host else H
-    move = (lambda t: _as_tensor(t).detach().cpu()) if host else _to_gpu
-    q, r, ql, rl = (move(t) for t in (query_codes, database_codes, query_labels, database_labels))
+    B = backend(device)
+    Hm = B.H
+    q, r, ql, rl = (B.move(t) for t in (query_codes, database_codes, query_labels, database_labels))
     if q.dim() != 2 or r.dim() != 2 or q.shape[1] != r.shape[1] or ql.dim() != 2 or rl.dim() != 2 or ql.shape[1] != rl.shape[1]:
         raise ValueError(f"{what}: expected [Q, nbits] / [N, nbits] codes and [Q, classes] / [N, classes] multi-hot labels")
     nbits = q.shape[1]
@@ -68,7 +62,7 @@ def _radius_tables(query_codes, database_codes, query_labels, database_labels, d
     qlp, rlp = Hm.pack_labels(ql), Hm.pack_labels(rl)
     got = Hm.hamming_radius_hist(qp, Hm.PreparedDB(rp, nbits), Hm.PreparedLabels(rlp), qlp, nbits)
     if got is None:
-        raise ValueError(f"{what}: {r.shape[0]} rows are outside the radius histograms (at most {64 * H.SHARD_ROWS_MAX} on the GPU)")
+        raise ValueError(f"{what}: {r.shape[0]} rows are outside the radius histograms (at most {64 * SHARD_ROWS_MAX} on the GPU)")
     return got
 
 

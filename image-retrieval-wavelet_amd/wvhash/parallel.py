@@ -378,7 +378,7 @@ def sharded_knn_float(q_local, db_shard, k, metric, n_total, group=None):
     whole database, bit for bit, for every world size.  Host tensors (gloo) take the library's host twins.
     -> (values [Ql, k], global rows int32 [Ql, k])."""
     from . import _lib
-    from .engine.get_knn import knn_float, knn_float_host
+    from .engine.backend import backend
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     lo, _, per = shard_bounds(n_total, world, rank)
@@ -400,7 +400,7 @@ def sharded_knn_float(q_local, db_shard, k, metric, n_total, group=None):
     rows = torch.full((world * Ql, kk), -1, dtype=torch.int32, device=dev)
     k_loc = min(kk, n_loc)
     if k_loc:
-        v, i = (knn_float if dev.type == "cuda" else knn_float_host)(db_shard, q_all, k_loc, shard_metric)
+        v, i = backend(dev).knn_float(db_shard, q_all, k_loc, shard_metric)
         vals[:, :k_loc] = v
         rows[:, :k_loc] = i + lo
     # one 8-byte word per entry: value bits | global row

@@ -9,7 +9,7 @@ import torch
 
 from oracle import ranking
 from wvhash import _lib
-from wvhash.engine import CustomCalculator
+from wvhash.engine import CustomCalculator, get_knn
 from wvhash.engine.get_knn import knn_float_host
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -117,11 +117,11 @@ def test_cpu_calculator_runs_float_metrics():
     r, q = torch.randn(300, 32, generator=g), torch.randn(12, 32, generator=g)
     for metric, faiss in (("cosine", False), ("l2", False), ("l2", True)):
         calc = CustomCalculator(k=10, device="cpu", distance_metric=metric, with_faiss=faiss)
-        idx, dist = calc._host_knn(r, q, 10, False)
+        idx, dist = get_knn(r, q, 10, False, with_faiss=calc.with_faiss, distance_metric=calc.distance_metric, device="cpu")
         sd, si = ranking.knn_stable(r, q, 10, metric)
         assert torch.equal(idx, si.long())
         np.testing.assert_allclose(dist.numpy(), (sd * sd if faiss else sd).numpy(), rtol=2e-5, atol=2e-5)
-    idx, dist = CustomCalculator(k=5, device="cpu", distance_metric="l2", with_faiss=False)._host_knn(r, r[:7], 5, True)
+    idx, dist = get_knn(r, r[:7], 5, True, with_faiss=False, distance_metric="l2", device="cpu")
     assert idx.shape == (7, 5) and not (idx == torch.arange(7)[:, None]).any()       # same source: column 0 (self) stripped
 
 

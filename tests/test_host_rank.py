@@ -11,7 +11,7 @@ import torch
 
 from oracle import ranking
 from wvhash import synth
-from wvhash.engine import CustomCalculator, get_accuracy_calculator
+from wvhash.engine import CustomCalculator, get_accuracy_calculator, get_knn
 from wvhash.engine import hamming_host as HH
 
 CASES = ["rand_q5_n64_b16", "rand_q16_n500_b32", "struct_q12_n1000_b64", "struct_q8_n777_b128", "tiefree_q8_n60_b128"]
@@ -61,9 +61,10 @@ def test_twins_reproduce_the_reference_executed_outputs(gold, n):
     np.testing.assert_allclose([calc.calculate_bit_balance(r), calc.calculate_worst_bit_balance(r)], gold[f"{n}/ref_bit_balance"],
                                rtol=0, atol=1e-7)
     # get_knn (get_knn.py:9-24, 60-71): inner products equal; same index sets per score bucket; same-source drops column 0
-    ki, kd = calc._host_knn(r, q, gold[f"{n}/ref_knn_ip"].shape[1], False)
+    knn = dict(with_faiss=calc.with_faiss, distance_metric=calc.distance_metric, device="cpu")
+    ki, kd = get_knn(r, q, gold[f"{n}/ref_knn_ip"].shape[1], False, **knn)
     np.testing.assert_array_equal(kd.numpy(), gold[f"{n}/ref_knn_ip"])
-    si, sd = calc._host_knn(r, r[:q.shape[0]], gold[f"{n}/ref_selfknn_ip"].shape[1], True)
+    si, sd = get_knn(r, r[:q.shape[0]], gold[f"{n}/ref_selfknn_ip"].shape[1], True, **knn)
     np.testing.assert_array_equal(sd.numpy(), gold[f"{n}/ref_selfknn_ip"])
 
 
@@ -94,7 +95,7 @@ def test_cpu_calculator_refuses_what_it_does_not_cover():
     from wvhash import _lib
     calc = CustomCalculator(k=5, device="cpu", distance_metric="cosine", with_faiss=False)
     x = torch.randn(6, 18)
-    idx, _ = calc._host_knn(x, x[:2], 3, False)                  # real-valued embeddings: the float twin (any dimension)
+    idx, _ = get_knn(x, x[:2], 3, False, with_faiss=calc.with_faiss, distance_metric=calc.distance_metric, device="cpu")   # real-valued embeddings: the float twin (any dimension)
     assert idx[:, 0].tolist() == [0, 1]
     with pytest.raises(ValueError, match="exactly"):
         calc.calculate_maphashing(torch.zeros(2, 16), torch.ones(2, 3), torch.ones(4, 16), torch.ones(4, 3), 2)
