@@ -23,6 +23,7 @@ WV_RANK_DESCENDING, WV_RANK_SQRT = 1, 2
 ABI_VERSION = 5        # what include/wvhash.h documents; load() refuses a library that reports another one
 WV_BANDS_INNER, WV_BANDS_OUTER = 0, 1
 WV_TOKENS_SBE, WV_TOKENS_BSE = 0, 1      # band tokens as [S][B][E] (wv_band_attn_pool's) or [B][S][E] (torch.stack(kv_list, 1))
+WV_RESAMPLE_BILINEAR, WV_RESAMPLE_BICUBIC = 2, 3      # PIL's enum values
 WV_ENOTSUP = -95            # return code: the shape is outside the kernel asked for (callers fall back)
 
 
@@ -53,6 +54,14 @@ class HeadParams(ctypes.Structure):
         ("q_proj", ctypes.c_void_p),
         ("prepared", ctypes.c_void_p),
     ]
+
+
+class SizeStage(ctypes.Structure):
+    """wv_size_stage: one step (crop -> resample -> window -> mirror) of one image; 80 bytes = 20 int32 words."""
+    _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64)] + [
+        (name, ctypes.c_int32) for name in (
+            "src_h", "src_w", "src_row_bytes", "crop_y", "crop_x", "crop_h", "crop_w", "res_h", "res_w",
+            "win_y", "win_x", "out_h", "out_w", "dst_row_bytes", "filter", "flip")]
 
 
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
@@ -139,6 +148,9 @@ SIGNATURES = {
     "wv_band_attn_maps_workspace_bytes": (_sz, [ctypes.POINTER(HeadParams), _i]),
     "wv_band_attn_maps": (_i, [ctypes.POINTER(HeadParams), _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wv_band_attn_maps_cpu": (_i, [ctypes.POINTER(HeadParams), _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "wv_image_size": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "wv_image_size_cpu": (_i, [_vp, _vp, _vp, _i]),
+    "wv_image_size_check": (_i, [_vp, _i]),
 }
 
 _LIB = None

@@ -6,7 +6,8 @@
   DEVICE tensor (the reference copies each batch to the CPU and ranks there);
 * a dataset built with a deferred ``SWTTransform(defer=True)`` yields raw uint8 ``[3, H, W]`` tensors:
   16x fewer bytes cross PCIe than the reference's pre-expanded ``[3, 4, H, W]`` fp32 tensors, and the
-  model wrapper runs the batched HIP SWT after the H2D copy (SURVEY.md 8 f-1);
+  model wrapper runs the batched HIP SWT after the H2D copy; built with ``sizing="device"`` as well,
+  it yields the decoded images and their recorded geometry, and the GPU sizes them too (transforms/sizing.py);
 * metrics come from ``CustomCalculator`` (engine/accuracy_calculator.py) and are reported under the
   reference's key names ``<metric>_level0``.
 
@@ -23,6 +24,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from .. import _lib
+from ..transforms.sizing import RawBatch, raw_collate
 from .accuracy_calculator import get_accuracy_calculator
 
 LOGGER = logging.getLogger("RETRIEVAL")
@@ -57,7 +59,7 @@ class GlobalEmbeddingSpaceTester:
             LOGGER.info("Computing embeddings")
             for i, data in enumerate(dataloader):
                 img, label = self.data_and_label_getter(data)
-                if expand is not None and img.dim() == 4:
+                if expand is not None and (isinstance(img, RawBatch) or img.dim() == 4):
                     img = expand(img)
                 q = trunk_model(img)
                 if embedder_model is not None:
@@ -95,8 +97,12 @@ class GlobalEmbeddingSpaceTester:
         return tf.apply_batch
 
     def get_all_embeddings(self, dataset, trunk_model, embedder_model=None):
+        # a plugin built with sizing="device" yields RawItems (pixels as decoded + recorded geometry): packed by raw_collate
+        from ..transforms.custom_transforms import find_wavelet_transform
+        tf = find_wavelet_transform(dataset)
+        collate = raw_collate if getattr(tf, "sizing", "host") == "device" else None
         dl = DataLoader(dataset, batch_size=self.batch_size, num_workers=self.dataloader_num_workers,
-                        shuffle=False, drop_last=False, pin_memory=True)
+                        shuffle=False, drop_last=False, pin_memory=True, collate_fn=collate)
         return self.compute_all_embeddings(dl, trunk_model, embedder_model)
 
     def get_splits_to_compute_embeddings(self, dataset_dict, splits_to_eval):

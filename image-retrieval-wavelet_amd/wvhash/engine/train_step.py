@@ -13,7 +13,10 @@ the reference's ``_single_pass_optimization`` / ``_gradient_cached_optimization`
   its slice of the cached gradient -- exactly the full-batch gradient at the memory of one micro-batch;
 * the fusion head's orthogonality loss is picked up from ``fusion_head.last_ortho_loss`` (base_update.py:130-137);
 * raw ``uint8 [B,3,H,W]`` batches of a deferred transform go straight into the model: the batched HIP SWT runs inside
-  the step (bf16 sub-bands under bf16 autocast), so the wavelet expansion no longer happens per image on the host.
+  the step (bf16 sub-bands under bf16 autocast), so the wavelet expansion no longer happens per image on the host;
+* ``RawBatch``es of a ``sizing="device"`` pipeline (decoded images + the geometry the workers drew: resize, random
+  resized crop, flip) are sized on the GPU first (``transforms.functional.size_images``), so the augmentation of
+  config/transform/basic_swt.yaml's train node runs batched as well.
 
 What is frozen stays out of the exchange: only parameters with ``requires_grad`` are bucketed (the DINOv2 backbones of
 the headline configs are frozen, so a step moves the head, ``hash_fc``, ``bn`` -- a few MB -- over xGMI).
@@ -24,6 +27,9 @@ import logging
 
 import torch
 import torch.distributed as dist
+
+from ..transforms.functional import size_images
+from ..transforms.sizing import RawBatch
 
 LOGGER = logging.getLogger("RETRIEVAL")
 
@@ -155,10 +161,14 @@ def _ortho_loss(net):
 
 def backward_step(net, images, labels, criteria, autocast_dtype=torch.bfloat16, scaler=None, sub_batch=None):
     """Forward + backward of one LOCAL batch (gradients accumulate into .grad; no optimizer step, no exchange).
-    images: what the DataLoader collated -- expanded sub-bands [B,3,4,H,W] or raw uint8 [B,3,H,W] (deferred transform
-    bound to the model).  criteria: [(loss module, weight)].  Returns a dict of logged scalars."""
+    images: what the DataLoader collated -- expanded sub-bands [B,3,4,H,W], raw uint8 [B,3,H,W] (deferred transform
+    bound to the model) or a transforms.sizing.RawBatch (sizing="device": sized here on the GPU, then as raw images).
+    criteria: [(loss module, weight)].  Returns a dict of logged scalars."""
     device = next(p for p in net.parameters()).device
     images = images.to(device, non_blocking=True)
+    if isinstance(images, RawBatch):
+        with torch.cuda.device(device):
+            images = size_images(images).permute(0, 3, 1, 2)    # [B,3,H,W] view; the model reads it channels-last in place
     labels = labels.to(device, non_blocking=True)
     total = images.shape[0]
     logs = {}

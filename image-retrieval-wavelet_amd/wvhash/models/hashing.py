@@ -95,7 +95,14 @@ class _WaveletHashingBase(nn.Module):
         return self.bind_transform(SWTTransform(level=level, wavelet=wavelet, defer=True))
 
     def _band_major(self, x):
-        """-> [4, B, 3, H, W] (band-major; a view whenever the memory already lies that way)."""
+        """-> [4, B, 3, H, W] (band-major; a view whenever the memory already lies that way).  A sizing.RawBatch (the
+        collated batch of a sizing="device" pipeline) is sized on the GPU first; its images are [B, H, W, 3]."""
+        from ..transforms.sizing import RawBatch
+        channels_last = False
+        if isinstance(x, RawBatch):
+            x, channels_last = TF.size_images(x), True
+        elif x.dim() == 4 and x.shape[1] == 3 and not x.is_contiguous() and x.permute(0, 2, 3, 1).is_contiguous():
+            x, channels_last = x.permute(0, 2, 3, 1), True       # [B,3,H,W] view of sized [B,H,W,3] images: read in place
         if x.dim() == 5:
             return x.permute(2, 0, 1, 3, 4)
         if x.dim() != 4:
@@ -111,9 +118,9 @@ class _WaveletHashingBase(nn.Module):
             # written band-major by the kernel: the band split below is a view, the sub-bands exist once in HBM.
             # Under bf16 autocast the backbone's first op casts its input to bf16 anyway: emit bf16 directly.
             bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
-            return TF.swt2d(x, tf.wavelet, tf.level, band_major=True,
+            return TF.swt2d(x, tf.wavelet, tf.level, band_major=True, channels_last=channels_last,
                             out_dtype=torch.bfloat16 if bf16 else torch.float32)
-        return tf.apply_batch(x).permute(2, 0, 1, 3, 4)
+        return tf.apply_batch(x, channels_last=channels_last).permute(2, 0, 1, 3, 4)
 
     def _tail(self, fused_embedding):
         host = not fused_embedding.is_cuda and getattr(self, "host_twin", False)      # explicit: model.host_twin = True

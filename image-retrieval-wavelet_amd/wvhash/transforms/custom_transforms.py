@@ -14,6 +14,9 @@ the expanded fp32 sub-bands), and the evaluation engine / the model run ``transf
 collate.  A deferred batch carries no wavelet name: ``engine.evaluate`` reads it from ``dataset.transform`` and binds
 the transform to the model (``model.bind_transform``); a model that receives a raw 4-D batch without a bound
 transform raises instead of guessing.
+With ``sizing="device"`` as well (``build_transform(cfg, defer=True, sizing="device")``) the workers do not even size the
+image: the plugin returns a ``sizing.RawItem`` (decoded pixels + recorded geometry, fix_size included) and ``apply_batch``
+takes the collated ``sizing.RawBatch``: sized on the GPU (``functional.size_images``), then transformed.
 """
 import numpy as np
 import torch
@@ -25,11 +28,16 @@ from . import functional as F
 class BaseWaveletTransform(object):
     """Shared wavelet pipeline: resize to fit the level, transform each RGB channel, stack."""
 
-    def __init__(self, level=1, wavelet='haar', defer=False, device=None):
+    def __init__(self, level=1, wavelet='haar', defer=False, device=None, sizing="host"):
+        if sizing not in ("host", "device"):
+            raise ValueError(f"sizing must be 'host' or 'device', got {sizing!r}")
+        if sizing == "device" and not defer:
+            raise ValueError("sizing='device' needs defer=True: the batch is sized on the GPU after collate")
         self.level = level
         self.wavelet = wavelet
         self.defer = defer
         self.device = device
+        self.sizing = sizing
 
     def fix_size(self, image):
         w, h = image.size
@@ -55,7 +63,7 @@ class BaseWaveletTransform(object):
 
     def apply_batch(self, batch, channels_last=False, **kwargs):
         """Batched path.  batch: uint8/float32 [B,3,H,W] (or [B,H,W,3]); GPU tensors take the HIP kernel, host
-        tensors the host twin."""
+        tensors the host twin.  A sizing.RawBatch (sizing="device") is sized first, where it lives."""
         raise NotImplementedError
 
     def _use_host(self):
@@ -66,6 +74,10 @@ class BaseWaveletTransform(object):
         return get_worker_info() is not None
 
     def __call__(self, img):
+        if self.sizing == "device":
+            from .sizing import LazyImage
+            lazy = img if isinstance(img, LazyImage) else LazyImage(img)
+            return self.fix_size(lazy).to_item()
         arr = self._to_u8_hwc(img)
         if self.defer:
             if arr.dtype != np.uint8:
@@ -117,6 +129,7 @@ class SWTTransform(BaseWaveletTransform):
     """Stationary wavelet transform (size preserved: H, W)."""
 
     def apply_batch(self, batch, channels_last=False, **kwargs):
+        batch, channels_last = F.sized(batch, channels_last)
         if not batch.is_cuda:
             return F.swt2d_host(batch, self.wavelet, self.level, channels_last=channels_last)
         return F.swt2d(batch, self.wavelet, self.level, channels_last=channels_last, **kwargs)
@@ -128,11 +141,12 @@ class SWTTransform(BaseWaveletTransform):
 class RawStackTransform(BaseWaveletTransform):
     """Parameter-matched control: every 'subband' is an identical copy of the raw channel."""
 
-    def __init__(self, level=1, wavelet='haar', copies=4, defer=False, device=None):
-        super().__init__(level=level, wavelet=wavelet, defer=defer, device=device)
+    def __init__(self, level=1, wavelet='haar', copies=4, defer=False, device=None, sizing="host"):
+        super().__init__(level=level, wavelet=wavelet, defer=defer, device=device, sizing=sizing)
         self.copies = copies
 
     def apply_batch(self, batch, channels_last=False, **kwargs):
+        batch, channels_last = F.sized(batch, channels_last)
         if not batch.is_cuda:
             return F.rawstack_host(batch, self.copies, channels_last=channels_last)
         return F.rawstack(batch, self.copies, channels_last=channels_last)
@@ -146,10 +160,11 @@ class DWTTransform(BaseWaveletTransform):
     ``pywt.wavedec2`` with PyWavelets' default symmetric extension (a plain, untuned kernel: this
     transform is outside the hot path)."""
 
-    def __init__(self, level=1, wavelet='haar', defer=False, device=None):
-        super().__init__(level=level, wavelet=wavelet, defer=defer, device=device)
+    def __init__(self, level=1, wavelet='haar', defer=False, device=None, sizing="host"):
+        super().__init__(level=level, wavelet=wavelet, defer=defer, device=device, sizing=sizing)
 
     def apply_batch(self, batch, channels_last=False, **kwargs):
+        batch, channels_last = F.sized(batch, channels_last)
         if not batch.is_cuda:
             return F.dwt2d_host(batch, self.wavelet, self.level, channels_last=channels_last)
         return F.dwt2d(batch, self.wavelet, self.level, channels_last=channels_last)

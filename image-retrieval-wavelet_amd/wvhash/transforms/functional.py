@@ -25,6 +25,56 @@ def _in_dtype(x):
     raise TypeError(f"images must be uint8 (0..255) or float32 (already scaled), got {x.dtype}")
 
 
+def _size_launches(raw_batch, call, work):
+    from .sizing import STAGE_WORDS
+    base = raw_batch.desc.data_ptr()
+    for s, (first, count, max_h, max_w, max_k) in enumerate(raw_batch.launches):
+        src = raw_batch.data if s == 0 else work          # later stages read what earlier ones wrote
+        call(_lib.ptr(src), _lib.ptr(work), ctypes.c_void_p(base + first * STAGE_WORDS * 4), count, max_h, max_w, max_k)
+    B, H, W = raw_batch.out_shape
+    return work[:B * H * W * 3].view(B, H, W, 3)
+
+
+def size_images(raw_batch):
+    """sizing.RawBatch on the GPU -> uint8 [B, H, W, 3]: crop, resample (Pillow's 8-bit BILINEAR / BICUBIC bit for bit),
+    window / zero pad and mirror of every image, one wv_image_size launch per stage index on the current stream; the
+    intermediate images of pipelines with two resamples live in the same freshly allocated buffer as the result."""
+    lib = _lib.require_gpu()
+    if not raw_batch.is_cuda:
+        raise ValueError("size_images: the batch must live on the GPU (size_images_host is the host twin)")
+    if raw_batch.desc.dtype != torch.int32 or not raw_batch.desc.is_contiguous() or not raw_batch.data.is_contiguous():
+        raise ValueError("size_images: descriptor tensor must be contiguous int32, data contiguous uint8")
+    work = torch.empty(raw_batch.work_bytes, dtype=torch.uint8, device=raw_batch.device)
+
+    def call(src, dst, stages, count, max_h, max_w, max_k):
+        _lib.check(lib.wv_image_size(src, dst, stages, count, max_h, max_w, max_k, _lib.stream_ptr()), "wv_image_size")
+
+    with torch.cuda.device(raw_batch.device):
+        return _size_launches(raw_batch, call, work)
+
+
+def size_images_host(raw_batch):
+    """Host twin of size_images (wv_image_size_cpu): the same bytes from a RawBatch of host tensors."""
+    lib = _lib.load()
+    if raw_batch.is_cuda:
+        raise ValueError("size_images_host: the host twin takes host tensors (size_images is the device function)")
+    work = torch.empty(raw_batch.work_bytes, dtype=torch.uint8)
+
+    def call(src, dst, stages, count, max_h, max_w, max_k):
+        _lib.check(lib.wv_image_size_cpu(src, dst, stages, count), "wv_image_size_cpu")
+
+    return _size_launches(raw_batch, call, work)
+
+
+def sized(batch, channels_last):
+    """(batch, channels_last) with a sizing.RawBatch replaced by its sized uint8 [B, H, W, 3] images (on the GPU when it
+    lives there, by the host twin otherwise); tensors pass through."""
+    from .sizing import RawBatch
+    if isinstance(batch, RawBatch):
+        return (size_images(batch) if batch.is_cuda else size_images_host(batch)), True
+    return batch, channels_last
+
+
 def swt2d(x, wavelet="haar", level=1, channels_last=False, out_dtype=torch.float32, out=None, band_major=False):
     """Batch of images on the GPU -> [B, C, 4, H, W] level-`level` sub-bands (cA, cH, cV, cD).
 

@@ -5,8 +5,16 @@ pipeline (Getter.get_transform, /root/reference/main/getter.py:25-35).
 The reference takes Resize / CenterCrop / Compose from torchvision; torchvision is an optional dependency here
 (absent -> these PIL equivalents are used: same output size rule, PIL bilinear filter like torchvision applies to
 PIL images).  They decode and size images on the host; the arithmetic of the path (SWT) stays on the GPU.
+
+With ``build_transform(cfg, defer=True, sizing="device")`` the same classes receive a ``sizing.LazyImage`` and only record
+the geometry; the pixels are sized on the GPU by ``functional.size_images`` (bit-identical to Pillow, see sizing.py).
 """
+import math
+
+import torch
 from PIL import Image
+
+from .sizing import LazyImage
 
 
 class Resize(object):
@@ -43,6 +51,11 @@ class CenterCrop(object):
     def __call__(self, img):
         th, tw = self.size
         w, h = img.size
+        if isinstance(img, LazyImage):
+            # the zero-padded canvas and the crop from it as ONE window of the image: canvas origin = -(pad before)
+            cw, ch = max(w, tw), max(h, th)
+            left, top = int(round((cw - tw) / 2.0)) - (cw - w) // 2, int(round((ch - th) / 2.0)) - (ch - h) // 2
+            return img.crop((left, top, left + tw, top + th))
         if w < tw or h < th:  # torchvision pads with zeros first
             canvas = Image.new(img.mode, (max(w, tw), max(h, th)))
             canvas.paste(img, ((max(w, tw) - w) // 2, (max(h, th) - h) // 2))
@@ -52,6 +65,68 @@ class CenterCrop(object):
 
     def __repr__(self):
         return f"CenterCrop(size={self.size})"
+
+
+class RandomResizedCrop(object):
+    """torchvision.transforms.RandomResizedCrop for PIL input: a random rectangle of `scale` x the area and an aspect ratio
+    log-uniform in `ratio`, resized to `size`.  The parameter rule is torchvision's get_params: ten attempts of
+    ``torch.empty(1).uniform_`` area and log-ratio draws, sides ``int(round(sqrt(...)))``, origins from ``torch.randint``
+    (row first), then the ratio-clamped centre crop.  All draws come from the torch global RNG in that order.
+    torchvision is not installed where this was written: draw-for-draw parity with it is the intent and is NOT pinned
+    by a test."""
+
+    def __init__(self, size, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), interpolation=Image.BILINEAR, **kwargs):
+        self.size = (size, size) if isinstance(size, int) else ((size[0], size[0]) if len(size) == 1 else tuple(size))
+        self.scale, self.ratio, self.interpolation = tuple(scale), tuple(ratio), interpolation
+
+    @staticmethod
+    def get_params(width, height, scale, ratio):
+        """-> (top, left, h, w)"""
+        area = height * width
+        log_ratio = torch.log(torch.tensor(ratio))
+        for _ in range(10):
+            target_area = area * torch.empty(1).uniform_(scale[0], scale[1]).item()
+            aspect_ratio = torch.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1])).item()
+            w = int(round(math.sqrt(target_area * aspect_ratio)))
+            h = int(round(math.sqrt(target_area / aspect_ratio)))
+            if 0 < w <= width and 0 < h <= height:
+                i = torch.randint(0, height - h + 1, size=(1,)).item()
+                j = torch.randint(0, width - w + 1, size=(1,)).item()
+                return i, j, h, w
+        in_ratio = float(width) / float(height)
+        if in_ratio < min(ratio):
+            w = width
+            h = int(round(w / min(ratio)))
+        elif in_ratio > max(ratio):
+            h = height
+            w = int(round(h * max(ratio)))
+        else:
+            w, h = width, height
+        return (height - h) // 2, (width - w) // 2, h, w
+
+    def __call__(self, img):
+        width, height = img.size
+        i, j, h, w = self.get_params(width, height, self.scale, self.ratio)
+        th, tw = self.size
+        return img.crop((j, i, j + w, i + h)).resize((int(tw), int(th)), self.interpolation)
+
+    def __repr__(self):
+        return f"RandomResizedCrop(size={self.size}, scale={self.scale}, ratio={self.ratio})"
+
+
+class RandomHorizontalFlip(object):
+    """Mirror left-right when ``torch.rand(1) < p`` (torchvision's rule and draw; parity unpinned like RandomResizedCrop)."""
+
+    def __init__(self, p=0.5, **kwargs):
+        self.p = p
+
+    def __call__(self, img):
+        if torch.rand(1) < self.p:
+            return img.transpose(Image.FLIP_LEFT_RIGHT)
+        return img
+
+    def __repr__(self):
+        return f"RandomHorizontalFlip(p={self.p})"
 
 
 class Compose(object):
@@ -67,25 +142,41 @@ class Compose(object):
         return "Compose(\n" + "\n".join(f"    {t}" for t in self.transforms) + "\n)"
 
 
-def build_transform(config, defer=False, device=None):
+def build_transform(config, defer=False, device=None, sizing="host"):
     """``{name: kwargs}`` mapping (a YAML node) -> Compose, resolved like Getter.get_transform: wavelet plugins of
     this package first, then torchvision.transforms when importable, else the PIL equivalents above.
-    defer / device are forwarded to the wavelet plugins (see custom_transforms.py)."""
+    defer / device are forwarded to the wavelet plugins (see custom_transforms.py).
+    sizing="host" (default): the geometry steps resample with PIL in the worker.  sizing="device" (needs defer=True and a
+    wavelet plugin at the end): they only record -- always this module's classes, which know how to --, the plugin
+    returns a ``sizing.RawItem`` per image, ``sizing.raw_collate`` packs a batch and the GPU sizes it
+    (``functional.size_images``): same pixels bit for bit."""
     from . import custom_transforms as ct
+    if sizing not in ("host", "device"):
+        raise ValueError(f"build_transform: sizing must be 'host' or 'device', got {sizing!r}")
+    if sizing == "device" and not defer:
+        raise ValueError("build_transform: sizing='device' sizes batches on the GPU after collate and needs defer=True")
     try:
         import torchvision.transforms as tvt
     except ImportError:
         tvt = None
-    local = {"Resize": Resize, "CenterCrop": CenterCrop}
+    if sizing == "device":
+        tvt = None
+    local = {"Resize": Resize, "CenterCrop": CenterCrop, "RandomResizedCrop": RandomResizedCrop,
+             "RandomHorizontalFlip": RandomHorizontalFlip}
     steps = []
     for name, kwargs in dict(config).items():
         kwargs = dict(kwargs or {})
         if hasattr(ct, name) and name.endswith("Transform"):
-            steps.append(getattr(ct, name)(defer=defer, device=device, **kwargs))
+            extra = {"sizing": sizing} if sizing != "host" else {}
+            steps.append(getattr(ct, name)(defer=defer, device=device, **extra, **kwargs))
         elif tvt is not None and hasattr(tvt, name):
             steps.append(getattr(tvt, name)(**kwargs))
         elif name in local:
             steps.append(local[name](**kwargs))
         else:
             raise AttributeError(f"transform '{name}' is neither a wvhash plugin nor available without torchvision")
+    if sizing == "device":
+        if not steps or not isinstance(steps[-1], ct.BaseWaveletTransform):
+            raise ValueError("build_transform: sizing='device' needs a wavelet plugin as the last step of the pipeline")
+        steps.insert(0, LazyImage)
     return Compose(steps)

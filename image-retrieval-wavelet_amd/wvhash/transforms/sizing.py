@@ -1,0 +1,299 @@
+"""Sizing on the device: the workers record the geometry, the GPU touches the pixels.
+
+With ``build_transform(cfg, defer=True, sizing="device")`` the geometry steps of a pipeline (``Resize``, ``CenterCrop``,
+``RandomResizedCrop``, ``RandomHorizontalFlip`` and the wavelet plugin's BICUBIC ``fix_size``) receive a ``LazyImage``
+instead of a PIL image: it answers ``.size`` / ``.resize`` / ``.crop`` / ``.transpose`` like one, but only logs the calls.
+The plugin at the end of the pipeline turns the log into ``wv_size_stage`` records (include/wvhash.h) and returns a
+``RawItem``: the decoded image untouched plus its records.  ``raw_collate`` packs the items of a batch into a ``RawBatch``
+(one byte buffer, one descriptor tensor), ``functional.size_images`` runs one ``wv_image_size`` launch per stage index on
+the GPU and returns ``uint8 [B, H, W, 3]`` -- bit-identical to what Pillow makes of the same calls.
+
+How calls become stages (one stage = crop -> resample -> window / zero pad -> mirror):
+* a crop before the stage's resample narrows its crop rectangle, a crop after it moves its window (which may hang over the
+  resampled image: zero pad, like ``Image.crop`` and torchvision's ``CenterCrop`` of a too small image);
+* a mirror toggles the stage's flag (a crop after a mirror is the mirrored crop of the window); a crop that hangs over an
+  earlier crop's window opens a new stage (its zero pad is relative to that window, not to the image);
+* a resample after a resample, after a mirror or after a padded window opens a new stage -- resampling and mirroring do not
+  commute exactly, the ``(int)(x + 0.5)`` bounds of the resampler are not symmetric;
+* a call Pillow answers with an unchanged copy (``resize`` to the size the image has) records nothing.
+An image outside the kernel's limits (``wv_image_size_check`` answers WV_ENOTSUP), or one that is not 8-bit RGB, is sized
+with PIL in the worker by replaying the log, and carries an empty stage list.
+"""
+import ctypes
+import math
+from collections.abc import Mapping
+
+import numpy as np
+import torch
+from PIL import Image
+
+from .. import _lib
+
+STAGE_WORDS = ctypes.sizeof(_lib.SizeStage) // 4           # 20 int32 words per descriptor
+STAGE_DTYPE = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8")] + [(n, "<i4") for n, _ in _lib.SizeStage._fields_[2:]])
+assert STAGE_DTYPE.itemsize == ctypes.sizeof(_lib.SizeStage) == 80
+_ALIGN = 16
+_FILTERS = {int(Image.BILINEAR): _lib.WV_RESAMPLE_BILINEAR, int(Image.BICUBIC): _lib.WV_RESAMPLE_BICUBIC}
+
+
+def _align(n):
+    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+def ksize(in_len, out_len, filt):
+    """Taps of a coefficient row of one axis: csrc/image_size.hpp's axis_ksize, same double arithmetic."""
+    if in_len == out_len:
+        return 1
+    return min(int(math.ceil((1.0 if filt == _lib.WV_RESAMPLE_BILINEAR else 2.0) * max(in_len / out_len, 1.0))) * 2 + 1, in_len)
+
+
+def stages_from_ops(width, height, ops):
+    """The call log of a LazyImage -> list of stage dicts (sizes only, offsets and row pitches are the packer's)."""
+    stages, cur = [], None
+    w, h = width, height
+
+    def fresh():
+        return {"src_w": w, "src_h": h, "crop": [0, 0, w, h], "res": None, "win": [0, 0, w, h], "flip": 0,
+                "filter": _lib.WV_RESAMPLE_BILINEAR}
+
+    def shown(st):
+        rw, rh = st["res"] if st["res"] is not None else st["crop"][2:]
+        return rw, rh
+
+    for op in ops:
+        if op[0] == "resize":
+            (nw, nh), filt = op[1], op[2]
+            if (nw, nh) == (w, h):
+                continue                                    # Pillow returns a copy: nothing is resampled
+            if cur is None:
+                cur = fresh()
+            rw, rh = shown(cur)
+            x, y, ww, wh = cur["win"]
+            padded = x < 0 or y < 0 or x + ww > rw or y + wh > rh
+            if cur["res"] is not None or cur["flip"] or padded:
+                stages.append(cur)
+                cur = fresh()
+                x, y, ww, wh = cur["win"]
+            cx, cy = cur["crop"][:2]
+            cur["crop"] = [cx + x, cy + y, ww, wh]          # the window of an unresampled stage is a crop
+            cur["res"], cur["filter"], cur["win"] = (nw, nh), filt, [0, 0, nw, nh]
+            w, h = nw, nh
+        elif op[0] == "crop":
+            x, y, cw, ch = op[1]
+            if cur is None:
+                cur = fresh()
+            wx, wy, ww, wh = cur["win"]
+            if (x < 0 or y < 0 or x + cw > ww or y + ch > wh) and [wx, wy, ww, wh] != [0, 0, *shown(cur)]:
+                stages.append(cur)                          # the zero pad is relative to the window, not to the image
+                cur = fresh()
+            if cur["flip"]:
+                x = cur["win"][2] - x - cw
+            cur["win"] = [cur["win"][0] + x, cur["win"][1] + y, cw, ch]
+            w, h = cw, ch
+        elif op[0] == "mirror":
+            if cur is None:
+                cur = fresh()
+            cur["flip"] ^= 1
+        else:
+            raise ValueError(f"unknown sizing op {op[0]!r}")
+    if cur is not None:
+        stages.append(cur)
+    return stages
+
+
+def _records(stages):
+    rec = np.zeros(len(stages), dtype=STAGE_DTYPE)
+    for r, st in zip(rec, stages):
+        rw, rh = st["res"] if st["res"] is not None else st["crop"][2:]
+        r["src_h"], r["src_w"], r["src_row_bytes"] = st["src_h"], st["src_w"], 3 * st["src_w"]
+        r["crop_x"], r["crop_y"], r["crop_w"], r["crop_h"] = st["crop"]
+        r["res_h"], r["res_w"] = rh, rw
+        r["win_x"], r["win_y"], r["out_w"], r["out_h"] = st["win"]
+        r["dst_row_bytes"], r["filter"], r["flip"] = 3 * st["win"][2], st["filter"], st["flip"]
+    return rec
+
+
+def check_records(rec):
+    """wv_image_size_check on host descriptors -> return code (0, WV_EINVAL or WV_ENOTSUP); the message is wv_last_error()."""
+    rec = np.ascontiguousarray(rec)
+    return _lib.load().wv_image_size_check(ctypes.c_void_p(rec.ctypes.data), len(rec))
+
+
+class LazyImage(object):
+    """Stands in for a PIL image in a sizing pipeline: answers like one, logs instead of resampling."""
+
+    def __init__(self, img):
+        if not isinstance(img, Image.Image):
+            raise TypeError(f"sizing='device' pipelines start from a PIL image, got {type(img).__name__}")
+        self.img = img
+        self.ops = []
+        self.size = img.size
+        self.mode = img.mode
+
+    def _log(self, op, size):
+        out = LazyImage.__new__(LazyImage)
+        out.img, out.ops, out.size, out.mode = self.img, self.ops + [op], size, self.mode
+        return out
+
+    def resize(self, size, resample=Image.BICUBIC, **kwargs):
+        if kwargs.get("box") is not None or kwargs.get("reducing_gap") is not None:
+            raise ValueError("LazyImage.resize: box / reducing_gap are not recorded")
+        if int(resample) not in _FILTERS:
+            raise ValueError(f"LazyImage.resize: only BILINEAR and BICUBIC are recorded, got resample={resample}")
+        size = (int(size[0]), int(size[1]))
+        return self._log(("resize", size, _FILTERS[int(resample)]), size)
+
+    def crop(self, box):
+        x0, y0, x1, y1 = (int(round(v)) for v in box)
+        return self._log(("crop", (x0, y0, x1 - x0, y1 - y0)), (x1 - x0, y1 - y0))
+
+    def transpose(self, method):
+        if method != Image.FLIP_LEFT_RIGHT:
+            raise ValueError("LazyImage.transpose: only FLIP_LEFT_RIGHT is recorded")
+        return self._log(("mirror",), self.size)
+
+    def materialize(self):
+        """The PIL image the log describes: the same calls on the real image (the oracle of the recorded stages)."""
+        img = self.img
+        for op in self.ops:
+            if op[0] == "resize":
+                img = img.resize(op[1], op[2])
+            elif op[0] == "crop":
+                x, y, w, h = op[1]
+                img = img.crop((x, y, x + w, y + h))
+            else:
+                img = img.transpose(Image.FLIP_LEFT_RIGHT)
+        return img
+
+    def to_item(self):
+        if self.mode == "RGB":
+            rec = _records(stages_from_ops(self.img.size[0], self.img.size[1], self.ops))
+            rc = 0
+            for i in range(len(rec)):                       # one record per launch: each on its own
+                rc = rc or check_records(rec[i:i + 1])
+            if rc == 0:
+                return RawItem(torch.from_numpy(np.array(self.img)), rec)
+            if rc != _lib.WV_ENOTSUP:
+                _lib.check(rc, "wv_image_size_check")
+        arr = np.array(self.materialize())                  # outside the kernel: PIL in the worker, as sizing="host" does
+        if arr.ndim != 3 or arr.shape[2] < 3 or arr.dtype != np.uint8:
+            raise ValueError(f"expected an 8-bit RGB image (H, W, 3), got array of shape {arr.shape} and dtype {arr.dtype}")
+        return RawItem(torch.from_numpy(np.ascontiguousarray(arr[:, :, :3])), np.zeros(0, dtype=STAGE_DTYPE))
+
+
+class RawItem(object):
+    """What a worker returns for one image: ``pixels`` uint8 [h, w, 3] as decoded, ``stages`` its wv_size_stage records
+    (offsets 0, tight rows; empty = the pixels are final)."""
+
+    def __init__(self, pixels, stages):
+        self.pixels = pixels
+        self.stages = stages
+
+    @property
+    def out_hw(self):
+        if len(self.stages):
+            return int(self.stages[-1]["out_h"]), int(self.stages[-1]["out_w"])
+        return int(self.pixels.shape[0]), int(self.pixels.shape[1])
+
+
+class RawBatch(object):
+    """A collated batch of RawItems.
+    data      uint8 [bytes]: the decoded images back to back (16-byte aligned starts)
+    desc      int32 [records, 20]: wv_size_stage records, all of stage index 0 first, then all of stage index 1, ...
+    launches  ((first record, records, max_out_h, max_out_w, max_ksize), ...) one entry per stage index
+    out_shape (B, H, W); work_bytes: the device buffer size_images allocates -- the B sized images first, then the
+              intermediate images of pipelines with more than one resample.
+    Stage 0 reads ``data``; later stages read the work buffer.  Every image's last stage writes its slot of the result."""
+
+    def __init__(self, data, desc, launches, out_shape, work_bytes):
+        self.data, self.desc, self.launches, self.out_shape, self.work_bytes = data, desc, tuple(launches), tuple(out_shape), work_bytes
+
+    def __len__(self):
+        return self.out_shape[0]
+
+    @property
+    def is_cuda(self):
+        return self.data.is_cuda
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def _moved(self, fn):
+        return RawBatch(fn(self.data), fn(self.desc), self.launches, self.out_shape, self.work_bytes)
+
+    def pin_memory(self):
+        return self._moved(lambda t: t.pin_memory())
+
+    def cuda(self, device=None, non_blocking=False):
+        return self._moved(lambda t: t.cuda(device, non_blocking=non_blocking))
+
+    def to(self, device, non_blocking=False):
+        return self._moved(lambda t: t.to(device, non_blocking=non_blocking))
+
+
+def _identity_record(h, w):
+    return _records([{"src_w": w, "src_h": h, "crop": [0, 0, w, h], "res": None, "win": [0, 0, w, h], "flip": 0,
+                      "filter": _lib.WV_RESAMPLE_BILINEAR}])
+
+
+def pack(items):
+    """list of RawItem -> RawBatch (host tensors).  The packed descriptors pass wv_image_size_check here, on the host copy:
+    the device entry point cannot read them."""
+    if not items:
+        raise ValueError("raw_collate: empty batch")
+    H, W = items[0].out_hw
+    for it in items:
+        if it.out_hw != (H, W):
+            raise ValueError(f"raw_collate: images of one batch must be sized alike, got {it.out_hw} and {(H, W)}")
+    B = len(items)
+    recs = [it.stages if len(it.stages) else _identity_record(*it.out_hw) for it in items]
+    data_off, total = [], 0
+    for it in items:
+        data_off.append(total)
+        total = _align(total + it.pixels.numel())
+    data = torch.empty(total, dtype=torch.uint8)
+    for it, off in zip(items, data_off):
+        data[off:off + it.pixels.numel()] = it.pixels.reshape(-1)
+    work = _align(B * H * W * 3)
+    per_stage = []
+    for i, rec in enumerate(recs):
+        src = data_off[i]
+        for s in range(len(rec)):
+            r = rec[s:s + 1].copy()
+            r["src_offset"] = src
+            if s == len(rec) - 1:
+                r["dst_offset"] = i * H * W * 3
+            else:
+                r["dst_offset"] = src = work
+                work = _align(work + int(r["out_h"][0]) * int(r["dst_row_bytes"][0]))
+            while len(per_stage) <= s:
+                per_stage.append([])
+            per_stage[s].append(r)
+    launches, first, chunks = [], 0, []
+    for group in per_stage:
+        g = np.concatenate(group)
+        rc = check_records(g)
+        if rc != 0:
+            _lib.check(rc, "wv_image_size_check")
+        ks = max(max(ksize(int(r["crop_w"]), int(r["res_w"]), int(r["filter"])),
+                     ksize(int(r["crop_h"]), int(r["res_h"]), int(r["filter"]))) for r in g)
+        launches.append((first, len(g), int(g["out_h"].max()), int(g["out_w"].max()), ks))
+        first += len(g)
+        chunks.append(g)
+    desc = torch.from_numpy(np.concatenate(chunks).view(np.int32).reshape(-1, STAGE_WORDS).copy())
+    return RawBatch(data, desc, launches, (B, H, W), work)
+
+
+def raw_collate(batch):
+    """collate_fn of a DataLoader over a dataset whose transform was built with sizing="device": RawItems become one
+    RawBatch, everything else goes through torch's default collate (dict items key by key, like the default)."""
+    from torch.utils.data import default_collate
+    first = batch[0]
+    if isinstance(first, RawItem):
+        return pack(list(batch))
+    if isinstance(first, Mapping):
+        return {k: raw_collate([b[k] for b in batch]) for k in first}
+    if isinstance(first, (tuple, list)) and any(isinstance(v, RawItem) for v in first):
+        return type(first)(raw_collate(list(col)) for col in zip(*batch))
+    return default_collate(batch)

@@ -54,6 +54,7 @@ const char *wv_last_error(void);
  * So were the radius histograms (wv_hamming_radius_hist, wv_hamming_radius_hist_cpu): 71 symbols.
  * So were the NDCG entry points (wv_label_overlap_hist[_cpu], wv_ndcg_weights, wv_ndcg_at_ks[_cpu]): 76 symbols.
  * So were the attention maps of the head (wv_band_attn_maps[_workspace_bytes], wv_band_attn_maps_cpu): 79 symbols.
+ * So was the image sizing (wv_image_size, wv_image_size_cpu, wv_image_size_check, struct wv_size_stage): 82 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -557,6 +558,51 @@ int wv_band_attn_maps(const wv_head_params *p, const float *feats, int layout, i
                       float *scores, float *attn_out, void *workspace, size_t workspace_bytes, void *stream);
 int wv_band_attn_maps_cpu(const wv_head_params *p, const float *feats, int layout, int B, float *probs, float *probs_mean,
                           float *scores, float *attn_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Image sizing: crop -> resample -> window / zero pad -> mirror, for a RAGGED batch of 3-channel uint8 HWC images in one
+ * launch -- what stands in front of the wavelet transform in the reference's YAML pipelines (config/transform/basic_swt.yaml:
+ * Resize -> CenterCrop | RandomResizedCrop -> RandomHorizontalFlip on PIL images inside DataLoader workers) and the BICUBIC
+ * fix_size of BaseWaveletTransform (custom_transforms.py:132-141).  The resample is Pillow's 8-bit ImagingResample restated
+ * (csrc/image_size.hpp): horizontal pass, then vertical pass, 22-bit fixed-point coefficients, uint8 intermediate; an axis
+ * whose length does not change is not resampled.  Bit-identical to Image.resize of Pillow 12 for both filters; the device
+ * entry point and the host twin agree byte for byte (the coefficient routine is one function compiled for both).
+ * One wv_size_stage is one step of one image:
+ *   1. the integer rectangle crop_* of the source is a new image (bounds clamp at ITS edge, as img.crop(box).resize(...));
+ *   2. it is resampled to res_h x res_w with `filter`;
+ *   3. the out_h x out_w window at (win_y, win_x) of the resampled image is written to dst; the window may hang over any edge:
+ *      pixels outside [0, res) are 0 (torchvision's CenterCrop zero-pads an image smaller than the crop);
+ *   4. flip != 0 mirrors the written window left-right.
+ * src / dst: base pointers of two byte buffers; an image lies at src + src_offset with row pitch src_row_bytes (dst likewise).
+ * A pipeline with two resamples is two stages (two launches, the first writing an intermediate ragged buffer).
+ * wv_image_size        stages: DEVICE array of n descriptors.  max_out_h / max_out_w / max_ksize: maxima over the n stages of
+ *                      out_h, out_w and the tap count min(ceil(S * max(crop / res, 1)) * 2 + 1, crop) of either axis (S = 1
+ *                      bilinear, 2 bicubic; 1 for an unchanged axis) -- they size the grid and the LDS, the kernel reads everything
+ *                      else from the descriptors.  No workspace, no table, no copy, no hidden synchronisation.  The descriptors
+ *                      are device memory: the entry point cannot check them; the caller runs wv_image_size_check on its host
+ *                      copy before the upload.  Maxima smaller than the truth leave pixels unwritten, never write elsewhere.
+ * wv_image_size_cpu    host twin (HOST pointers); runs wv_image_size_check itself.
+ * wv_image_size_check  the one argument check (HOST descriptors): WV_EINVAL for values that describe no image (a side < 1, a
+ *                      crop outside the source, a row pitch shorter than the row, a negative offset, an unknown filter,
+ *                      destinations of two stages that overlap), WV_ENOTSUP for images outside the kernel's limits (a side above
+ *                      16384, a window origin beyond +-16384, a down-scale above 64 on an axis of more than 257 samples -- 257 taps
+ *                      per coefficient row is what the limit protects, and a row has no more taps than its axis has samples);
+ *                      the message names the field.
+ * ------------------------------------------------------------------------------------------ */
+#define WV_RESAMPLE_BILINEAR 2 /* PIL's enum values */
+#define WV_RESAMPLE_BICUBIC 3
+typedef struct wv_size_stage {
+    int64_t src_offset, dst_offset;         /* bytes from `src` / `dst` to the image's first pixel */
+    int32_t src_h, src_w, src_row_bytes;
+    int32_t crop_y, crop_x, crop_h, crop_w; /* integer rectangle that is resampled */
+    int32_t res_h, res_w;                   /* size the rectangle is resampled to */
+    int32_t win_y, win_x, out_h, out_w;     /* window of the resampled image that is written */
+    int32_t dst_row_bytes, filter, flip;
+} wv_size_stage;
+int wv_image_size(const uint8_t *src, uint8_t *dst, const wv_size_stage *stages, int n, int max_out_h, int max_out_w,
+                  int max_ksize, void *stream);
+int wv_image_size_cpu(const uint8_t *src, uint8_t *dst, const wv_size_stage *stages, int n);
+int wv_image_size_check(const wv_size_stage *stages, int n);
 
 #ifdef __cplusplus
 }
