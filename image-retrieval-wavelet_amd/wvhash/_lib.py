@@ -24,6 +24,7 @@ ABI_VERSION = 5        # what include/wvhash.h documents; load() refuses a libra
 WV_BANDS_INNER, WV_BANDS_OUTER = 0, 1
 WV_TOKENS_SBE, WV_TOKENS_BSE = 0, 1      # band tokens as [S][B][E] (wv_band_attn_pool's) or [B][S][E] (torch.stack(kv_list, 1))
 WV_RESAMPLE_BILINEAR, WV_RESAMPLE_BICUBIC = 2, 3      # PIL's enum values
+WV_COLOUR_BRIGHTNESS, WV_COLOUR_CONTRAST, WV_COLOUR_SATURATION = 0, 1, 2
 WV_ENOTSUP = -95            # return code: the shape is outside the kernel asked for (callers fall back)
 
 
@@ -62,6 +63,12 @@ class SizeStage(ctypes.Structure):
         (name, ctypes.c_int32) for name in (
             "src_h", "src_w", "src_row_bytes", "crop_y", "crop_x", "crop_h", "crop_w", "res_h", "res_w",
             "win_y", "win_x", "out_h", "out_w", "dst_row_bytes", "filter", "flip")]
+
+
+class ColourOps(ctypes.Structure):
+    """wv_colour_ops: the colour operations of one image, in the order they run; 48 bytes = 12 32-bit words."""
+    _fields_ = [("offset", ctypes.c_int64), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("row_bytes", ctypes.c_int32),
+                ("n_ops", ctypes.c_int32), ("kind", ctypes.c_int32 * 3), ("factor", ctypes.c_float * 3)]
 
 
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
@@ -151,6 +158,10 @@ SIGNATURES = {
     "wv_image_size": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wv_image_size_cpu": (_i, [_vp, _vp, _vp, _i]),
     "wv_image_size_check": (_i, [_vp, _i]),
+    "wv_colour_jitter_workspace_bytes": (_sz, [_i]),
+    "wv_colour_jitter": (_i, [_vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "wv_colour_jitter_cpu": (_i, [_vp, _vp, _i]),
+    "wv_colour_jitter_check": (_i, [_vp, _i]),
 }
 
 _LIB = None

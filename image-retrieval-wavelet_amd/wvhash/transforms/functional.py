@@ -25,12 +25,16 @@ def _in_dtype(x):
     raise TypeError(f"images must be uint8 (0..255) or float32 (already scaled), got {x.dtype}")
 
 
-def _size_launches(raw_batch, call, work):
-    from .sizing import STAGE_WORDS
+def _size_launches(raw_batch, call, work, colour_call):
+    from .sizing import COLOUR_WORDS, STAGE_WORDS
     base = raw_batch.desc.data_ptr()
+    colour_launches = getattr(raw_batch, "colour_launches", ())
     for s, (first, count, max_h, max_w, max_k) in enumerate(raw_batch.launches):
         src = raw_batch.data if s == 0 else work          # later stages read what earlier ones wrote
         call(_lib.ptr(src), _lib.ptr(work), ctypes.c_void_p(base + first * STAGE_WORDS * 4), count, max_h, max_w, max_k)
+        if s < len(colour_launches) and colour_launches[s][1]:
+            first, count, max_h, max_w = colour_launches[s]  # the colour chains of what this stage wrote, in place
+            colour_call(_lib.ptr(work), ctypes.c_void_p(raw_batch.colour.data_ptr() + first * COLOUR_WORDS * 4), count, max_h, max_w)
     B, H, W = raw_batch.out_shape
     return work[:B * H * W * 3].view(B, H, W, 3)
 
@@ -38,23 +42,34 @@ def _size_launches(raw_batch, call, work):
 def size_images(raw_batch):
     """sizing.RawBatch on the GPU -> uint8 [B, H, W, 3]: crop, resample (Pillow's 8-bit BILINEAR / BICUBIC bit for bit),
     window / zero pad and mirror of every image, one wv_image_size launch per stage index on the current stream; the
-    intermediate images of pipelines with two resamples live in the same freshly allocated buffer as the result."""
+    intermediate images of pipelines with two resamples live in the same freshly allocated buffer as the result.  The
+    colour chains recorded on a stage (ColorJitter; Pillow's ImageEnhance bit for bit) follow its launch as one
+    wv_colour_jitter call, in place."""
     lib = _lib.require_gpu()
     if not raw_batch.is_cuda:
         raise ValueError("size_images: the batch must live on the GPU (size_images_host is the host twin)")
     if raw_batch.desc.dtype != torch.int32 or not raw_batch.desc.is_contiguous() or not raw_batch.data.is_contiguous():
         raise ValueError("size_images: descriptor tensor must be contiguous int32, data contiguous uint8")
+    colour = getattr(raw_batch, "colour", None)
+    if colour is not None and (colour.dtype != torch.int32 or not colour.is_contiguous() or colour.device != raw_batch.device):
+        raise ValueError("size_images: colour descriptor tensor must be contiguous int32 on the batch's device")
     work = torch.empty(raw_batch.work_bytes, dtype=torch.uint8, device=raw_batch.device)
 
     def call(src, dst, stages, count, max_h, max_w, max_k):
         _lib.check(lib.wv_image_size(src, dst, stages, count, max_h, max_w, max_k, _lib.stream_ptr()), "wv_image_size")
 
+    def colour_call(img, ops, count, max_h, max_w):
+        nbytes = lib.wv_colour_jitter_workspace_bytes(count)
+        sums = torch.empty(nbytes, dtype=torch.uint8, device=raw_batch.device)
+        _lib.check(lib.wv_colour_jitter(img, ops, count, max_h, max_w, _lib.ptr(sums), ctypes.c_size_t(nbytes), _lib.stream_ptr()),
+                   "wv_colour_jitter")
+
     with torch.cuda.device(raw_batch.device):
-        return _size_launches(raw_batch, call, work)
+        return _size_launches(raw_batch, call, work, colour_call)
 
 
 def size_images_host(raw_batch):
-    """Host twin of size_images (wv_image_size_cpu): the same bytes from a RawBatch of host tensors."""
+    """Host twin of size_images (wv_image_size_cpu, wv_colour_jitter_cpu): the same bytes from a RawBatch of host tensors."""
     lib = _lib.load()
     if raw_batch.is_cuda:
         raise ValueError("size_images_host: the host twin takes host tensors (size_images is the device function)")
@@ -63,7 +78,10 @@ def size_images_host(raw_batch):
     def call(src, dst, stages, count, max_h, max_w, max_k):
         _lib.check(lib.wv_image_size_cpu(src, dst, stages, count), "wv_image_size_cpu")
 
-    return _size_launches(raw_batch, call, work)
+    def colour_call(img, ops, count, max_h, max_w):
+        _lib.check(lib.wv_colour_jitter_cpu(img, ops, count), "wv_colour_jitter_cpu")
+
+    return _size_launches(raw_batch, call, work, colour_call)
 
 
 def sized(batch, channels_last):

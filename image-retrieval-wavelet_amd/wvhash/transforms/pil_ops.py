@@ -8,13 +8,15 @@ PIL images).  They decode and size images on the host; the arithmetic of the pat
 
 With ``build_transform(cfg, defer=True, sizing="device")`` the same classes receive a ``sizing.LazyImage`` and only record
 the geometry; the pixels are sized on the GPU by ``functional.size_images`` (bit-identical to Pillow, see sizing.py).
+``ColorJitter`` (config/transform/voc_swt.yaml, cub_swt.yaml) records its drawn operations the same way.
 """
 import math
+import numbers
 
 import torch
 from PIL import Image
 
-from .sizing import LazyImage
+from .sizing import LazyImage, pil_colour
 
 
 class Resize(object):
@@ -129,6 +131,68 @@ class RandomHorizontalFlip(object):
         return f"RandomHorizontalFlip(p={self.p})"
 
 
+class ColorJitter(object):
+    """torchvision.transforms.ColorJitter for PIL input: brightness, contrast, saturation (Pillow's ImageEnhance) and hue in
+    a random order with random factors.
+    A number v means the range [max(0, 1 - v), 1 + v] (hue: [-v, v], v <= 0.5), a pair is the range itself; a range that is
+    the neutral value at both ends switches the operation off (None).  A negative number, a range outside [0, inf) (hue:
+    [-0.5, 0.5]) or with its ends swapped raise ValueError, anything that is neither a number nor a pair TypeError.
+    The draws are torchvision's get_params: ``torch.randperm(4)`` first, then one ``torch.empty(1).uniform_(lo, hi)`` for
+    each operation that is on, in the order brightness, contrast, saturation, hue -- all from the torch global RNG.
+    torchvision is not installed where this was written: draw-for-draw parity with it is the intent and is NOT pinned by
+    a test.
+    A ``sizing.LazyImage`` records the operations; the GPU applies them after sizing (hue is outside the kernel: such an
+    image is finished with PIL in the worker)."""
+
+    KINDS = ("brightness", "contrast", "saturation", "hue")
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, **kwargs):
+        self.brightness = self._check_input(brightness, "brightness")
+        self.contrast = self._check_input(contrast, "contrast")
+        self.saturation = self._check_input(saturation, "saturation")
+        self.hue = self._check_input(hue, "hue", center=0.0, bound=(-0.5, 0.5), clip_first_on_zero=False)
+
+    @staticmethod
+    def _check_input(value, name, center=1.0, bound=(0.0, float("inf")), clip_first_on_zero=True):
+        if isinstance(value, numbers.Number):
+            if value < 0:
+                raise ValueError(f"If {name} is a single number, it must be non negative.")
+            value = [center - float(value), center + float(value)]
+            if clip_first_on_zero:
+                value[0] = max(value[0], 0.0)
+        elif isinstance(value, (tuple, list)) and len(value) == 2:
+            value = [float(value[0]), float(value[1])]
+        else:
+            raise TypeError(f"{name} should be a single number or a list/tuple with length 2.")
+        if not bound[0] <= value[0] <= value[1] <= bound[1]:
+            raise ValueError(f"{name} values should be between {bound} and in ascending order, got {value}.")
+        if value[0] == value[1] == center:
+            return None
+        return tuple(value)
+
+    @staticmethod
+    def get_params(brightness, contrast, saturation, hue):
+        """-> (order: the permutation of 0..3 as a list, then the four factors, None for an operation that is off)"""
+        fn_idx = torch.randperm(4)
+        drawn = [None if r is None else float(torch.empty(1).uniform_(r[0], r[1])) for r in (brightness, contrast, saturation, hue)]
+        return (fn_idx.tolist(), *drawn)
+
+    def __call__(self, img):
+        order, *factors = self.get_params(self.brightness, self.contrast, self.saturation, self.hue)
+        for fn_id in order:
+            if factors[fn_id] is None:
+                continue
+            if isinstance(img, LazyImage):
+                img = img.colour(self.KINDS[fn_id], factors[fn_id])
+            else:
+                img = pil_colour(img, self.KINDS[fn_id], factors[fn_id])
+        return img
+
+    def __repr__(self):
+        return (f"ColorJitter(brightness={self.brightness}, contrast={self.contrast}, saturation={self.saturation}, "
+                f"hue={self.hue})")
+
+
 class Compose(object):
     def __init__(self, transforms):
         self.transforms = list(transforms)
@@ -146,7 +210,7 @@ def build_transform(config, defer=False, device=None, sizing="host"):
     """``{name: kwargs}`` mapping (a YAML node) -> Compose, resolved like Getter.get_transform: wavelet plugins of
     this package first, then torchvision.transforms when importable, else the PIL equivalents above.
     defer / device are forwarded to the wavelet plugins (see custom_transforms.py).
-    sizing="host" (default): the geometry steps resample with PIL in the worker.  sizing="device" (needs defer=True and a
+    sizing="host" (default): the geometry steps resample, and ColorJitter enhances, with PIL in the worker.  sizing="device" (needs defer=True and a
     wavelet plugin at the end): they only record -- always this module's classes, which know how to --, the plugin
     returns a ``sizing.RawItem`` per image, ``sizing.raw_collate`` packs a batch and the GPU sizes it
     (``functional.size_images``): same pixels bit for bit."""
@@ -162,7 +226,7 @@ def build_transform(config, defer=False, device=None, sizing="host"):
     if sizing == "device":
         tvt = None
     local = {"Resize": Resize, "CenterCrop": CenterCrop, "RandomResizedCrop": RandomResizedCrop,
-             "RandomHorizontalFlip": RandomHorizontalFlip}
+             "RandomHorizontalFlip": RandomHorizontalFlip, "ColorJitter": ColorJitter}
     steps = []
     for name, kwargs in dict(config).items():
         kwargs = dict(kwargs or {})

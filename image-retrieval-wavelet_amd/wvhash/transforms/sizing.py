@@ -18,6 +18,14 @@ How calls become stages (one stage = crop -> resample -> window / zero pad -> mi
 * a call Pillow answers with an unchanged copy (``resize`` to the size the image has) records nothing.
 An image outside the kernel's limits (``wv_image_size_check`` answers WV_ENOTSUP), or one that is not 8-bit RGB, is sized
 with PIL in the worker by replaying the log, and carries an empty stage list.
+
+Colour operations (``ColorJitter``: brightness, contrast, saturation; ``wv_colour_ops`` records, ``wv_colour_jitter``) are not
+geometry but ride on it: an operation attaches to the stage that is open when it is recorded (an identity stage if there is
+none) and runs, in place, on what that stage wrote -- its whole window, zero pad included, as PIL would see it.
+* a later mirror only toggles the flag: pointwise operations and a mean over the whole image commute with it;
+* a later crop or resample opens a new stage: the contrast mean belongs to the image as it was;
+* a stage holds one chain, each kind at most once.  A second operation of a kind on one stage, or a hue operation (which
+  the kernel does not implement), sends the image down the PIL fallback above.
 """
 import ctypes
 import math
@@ -25,13 +33,20 @@ from collections.abc import Mapping
 
 import numpy as np
 import torch
-from PIL import Image
+from PIL import Image, ImageEnhance
 
 from .. import _lib
 
 STAGE_WORDS = ctypes.sizeof(_lib.SizeStage) // 4           # 20 int32 words per descriptor
 STAGE_DTYPE = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8")] + [(n, "<i4") for n, _ in _lib.SizeStage._fields_[2:]])
 assert STAGE_DTYPE.itemsize == ctypes.sizeof(_lib.SizeStage) == 80
+COLOUR_WORDS = ctypes.sizeof(_lib.ColourOps) // 4          # 12 32-bit words per descriptor
+COLOUR_DTYPE = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("row_bytes", "<i4"), ("n_ops", "<i4"),
+                         ("kind", "<i4", (3,)), ("factor", "<f4", (3,))])
+assert COLOUR_DTYPE.itemsize == ctypes.sizeof(_lib.ColourOps) == 48
+COLOUR_KINDS = {"brightness": _lib.WV_COLOUR_BRIGHTNESS, "contrast": _lib.WV_COLOUR_CONTRAST,
+                "saturation": _lib.WV_COLOUR_SATURATION}
+_ENHANCERS = {"brightness": ImageEnhance.Brightness, "contrast": ImageEnhance.Contrast, "saturation": ImageEnhance.Color}
 _ALIGN = 16
 _FILTERS = {int(Image.BILINEAR): _lib.WV_RESAMPLE_BILINEAR, int(Image.BICUBIC): _lib.WV_RESAMPLE_BICUBIC}
 
@@ -47,14 +62,37 @@ def ksize(in_len, out_len, filt):
     return min(int(math.ceil((1.0 if filt == _lib.WV_RESAMPLE_BILINEAR else 2.0) * max(in_len / out_len, 1.0))) * 2 + 1, in_len)
 
 
+def pil_colour(img, kind, factor):
+    """One colour operation on a PIL image, as torchvision applies it to PIL input: ImageEnhance for brightness, contrast and
+    saturation; for hue ``convert("HSV")``, ``int(factor * 255) & 0xFF`` added to H modulo 256, merged and converted back
+    (images without colour -- modes L, 1, I, F -- are returned as they are)."""
+    if kind in _ENHANCERS:
+        return _ENHANCERS[kind](img).enhance(factor)
+    if kind != "hue":
+        raise ValueError(f"unknown colour operation {kind!r}")
+    if not -0.5 <= factor <= 0.5:
+        raise ValueError(f"hue factor {factor} is not in [-0.5, 0.5]")
+    mode = img.mode
+    if mode in ("L", "1", "I", "F"):
+        return img
+    h, s, v = img.convert("HSV").split()
+    h = h.point([(i + (int(factor * 255) & 0xFF)) & 0xFF for i in range(256)])
+    return Image.merge("HSV", (h, s, v)).convert(mode)
+
+
+class NotRecordable(ValueError):
+    """The call log describes something the stages cannot express (to_item sizes such an image with PIL)."""
+
+
 def stages_from_ops(width, height, ops):
-    """The call log of a LazyImage -> list of stage dicts (sizes only, offsets and row pitches are the packer's)."""
+    """The call log of a LazyImage -> list of stage dicts (sizes only, offsets and row pitches are the packer's).  A stage's
+    "colour" is its chain [(kind name, factor), ...] in running order."""
     stages, cur = [], None
     w, h = width, height
 
     def fresh():
         return {"src_w": w, "src_h": h, "crop": [0, 0, w, h], "res": None, "win": [0, 0, w, h], "flip": 0,
-                "filter": _lib.WV_RESAMPLE_BILINEAR}
+                "filter": _lib.WV_RESAMPLE_BILINEAR, "colour": []}
 
     def shown(st):
         rw, rh = st["res"] if st["res"] is not None else st["crop"][2:]
@@ -70,7 +108,7 @@ def stages_from_ops(width, height, ops):
             rw, rh = shown(cur)
             x, y, ww, wh = cur["win"]
             padded = x < 0 or y < 0 or x + ww > rw or y + wh > rh
-            if cur["res"] is not None or cur["flip"] or padded:
+            if cur["res"] is not None or cur["flip"] or padded or cur["colour"]:
                 stages.append(cur)
                 cur = fresh()
                 x, y, ww, wh = cur["win"]
@@ -83,7 +121,10 @@ def stages_from_ops(width, height, ops):
             if cur is None:
                 cur = fresh()
             wx, wy, ww, wh = cur["win"]
-            if (x < 0 or y < 0 or x + cw > ww or y + ch > wh) and [wx, wy, ww, wh] != [0, 0, *shown(cur)]:
+            if cur["colour"]:
+                stages.append(cur)                          # the contrast mean belongs to the image before the crop
+                cur = fresh()
+            elif (x < 0 or y < 0 or x + cw > ww or y + ch > wh) and [wx, wy, ww, wh] != [0, 0, *shown(cur)]:
                 stages.append(cur)                          # the zero pad is relative to the window, not to the image
                 cur = fresh()
             if cur["flip"]:
@@ -94,6 +135,15 @@ def stages_from_ops(width, height, ops):
             if cur is None:
                 cur = fresh()
             cur["flip"] ^= 1
+        elif op[0] == "colour":
+            kind, factor = op[1], op[2]
+            if cur is None:
+                cur = fresh()
+            if kind not in COLOUR_KINDS:
+                raise NotRecordable(f"colour operation {kind!r} is not one of the kernel's")
+            if any(k == kind for k, _ in cur["colour"]):
+                raise NotRecordable(f"a second {kind} operation on one stage")
+            cur["colour"].append((kind, float(factor)))
         else:
             raise ValueError(f"unknown sizing op {op[0]!r}")
     if cur is not None:
@@ -111,6 +161,23 @@ def _records(stages):
         r["win_x"], r["win_y"], r["out_w"], r["out_h"] = st["win"]
         r["dst_row_bytes"], r["filter"], r["flip"] = 3 * st["win"][2], st["filter"], st["flip"]
     return rec
+
+
+def _colour_records(stages):
+    """One wv_colour_ops record per stage (n_ops = 0 where the stage has no chain): the image is what the stage writes."""
+    rec = np.zeros(len(stages), dtype=COLOUR_DTYPE)
+    for r, st in zip(rec, stages):
+        r["h"], r["w"], r["row_bytes"] = st["win"][3], st["win"][2], 3 * st["win"][2]
+        r["n_ops"] = len(st["colour"])
+        for i, (kind, factor) in enumerate(st["colour"]):
+            r["kind"][i], r["factor"][i] = COLOUR_KINDS[kind], factor
+    return rec
+
+
+def check_colour_records(rec):
+    """wv_colour_jitter_check on host descriptors -> return code; the message is wv_last_error()."""
+    rec = np.ascontiguousarray(rec)
+    return _lib.load().wv_colour_jitter_check(ctypes.c_void_p(rec.ctypes.data), len(rec))
 
 
 def check_records(rec):
@@ -152,6 +219,13 @@ class LazyImage(object):
             raise ValueError("LazyImage.transpose: only FLIP_LEFT_RIGHT is recorded")
         return self._log(("mirror",), self.size)
 
+    def colour(self, kind, factor):
+        """Record one colour operation: kind 'brightness', 'contrast', 'saturation' or 'hue', factor as ImageEnhance (and
+        torchvision's adjust_hue) take it."""
+        if kind not in _ENHANCERS and kind != "hue":
+            raise ValueError(f"LazyImage.colour: unknown operation {kind!r}")
+        return self._log(("colour", kind, float(factor)), self.size)
+
     def materialize(self):
         """The PIL image the log describes: the same calls on the real image (the oracle of the recorded stages)."""
         img = self.img
@@ -161,20 +235,31 @@ class LazyImage(object):
             elif op[0] == "crop":
                 x, y, w, h = op[1]
                 img = img.crop((x, y, x + w, y + h))
+            elif op[0] == "colour":
+                img = pil_colour(img, op[1], op[2])
             else:
                 img = img.transpose(Image.FLIP_LEFT_RIGHT)
         return img
 
     def to_item(self):
-        if self.mode == "RGB":
-            rec = _records(stages_from_ops(self.img.size[0], self.img.size[1], self.ops))
+        try:
+            stages = stages_from_ops(self.img.size[0], self.img.size[1], self.ops) if self.mode == "RGB" else None
+        except NotRecordable:
+            stages = None
+        if stages is not None:
+            rec, col = _records(stages), _colour_records(stages)
             rc = 0
             for i in range(len(rec)):                       # one record per launch: each on its own
                 rc = rc or check_records(rec[i:i + 1])
+            what = "wv_image_size_check"
             if rc == 0:
-                return RawItem(torch.from_numpy(np.array(self.img)), rec)
+                what = "wv_colour_jitter_check"
+                for i in range(len(col)):
+                    rc = rc or check_colour_records(col[i:i + 1])
+            if rc == 0:
+                return RawItem(torch.from_numpy(np.array(self.img)), rec, col if col["n_ops"].any() else None)
             if rc != _lib.WV_ENOTSUP:
-                _lib.check(rc, "wv_image_size_check")
+                _lib.check(rc, what)
         arr = np.array(self.materialize())                  # outside the kernel: PIL in the worker, as sizing="host" does
         if arr.ndim != 3 or arr.shape[2] < 3 or arr.dtype != np.uint8:
             raise ValueError(f"expected an 8-bit RGB image (H, W, 3), got array of shape {arr.shape} and dtype {arr.dtype}")
@@ -183,11 +268,13 @@ class LazyImage(object):
 
 class RawItem(object):
     """What a worker returns for one image: ``pixels`` uint8 [h, w, 3] as decoded, ``stages`` its wv_size_stage records
-    (offsets 0, tight rows; empty = the pixels are final)."""
+    (offsets 0, tight rows; empty = the pixels are final), ``colour`` None or one wv_colour_ops record per stage: the chain
+    that runs on what the stage wrote (n_ops = 0: none)."""
 
-    def __init__(self, pixels, stages):
+    def __init__(self, pixels, stages, colour=None):
         self.pixels = pixels
         self.stages = stages
+        self.colour = colour
 
     @property
     def out_hw(self):
@@ -203,10 +290,15 @@ class RawBatch(object):
     launches  ((first record, records, max_out_h, max_out_w, max_ksize), ...) one entry per stage index
     out_shape (B, H, W); work_bytes: the device buffer size_images allocates -- the B sized images first, then the
               intermediate images of pipelines with more than one resample.
-    Stage 0 reads ``data``; later stages read the work buffer.  Every image's last stage writes its slot of the result."""
+    Stage 0 reads ``data``; later stages read the work buffer.  Every image's last stage writes its slot of the result.
+    colour          None, or int32 [records, 12]: wv_colour_ops records (bit patterns; the factors are fp32), grouped by
+                    stage index like ``desc``; only images that have a chain on that stage are listed
+    colour_launches () or one (first record, records, max_h, max_w) per stage index, records = 0 where no image has a chain:
+                    the wv_colour_jitter call that follows the stage's wv_image_size launch, in place on the work buffer."""
 
-    def __init__(self, data, desc, launches, out_shape, work_bytes):
+    def __init__(self, data, desc, launches, out_shape, work_bytes, colour=None, colour_launches=()):
         self.data, self.desc, self.launches, self.out_shape, self.work_bytes = data, desc, tuple(launches), tuple(out_shape), work_bytes
+        self.colour, self.colour_launches = colour, tuple(colour_launches)
 
     def __len__(self):
         return self.out_shape[0]
@@ -220,7 +312,8 @@ class RawBatch(object):
         return self.data.device
 
     def _moved(self, fn):
-        return RawBatch(fn(self.data), fn(self.desc), self.launches, self.out_shape, self.work_bytes)
+        return RawBatch(fn(self.data), fn(self.desc), self.launches, self.out_shape, self.work_bytes,
+                        None if self.colour is None else fn(self.colour), self.colour_launches)
 
     def pin_memory(self):
         return self._moved(lambda t: t.pin_memory())
@@ -234,12 +327,12 @@ class RawBatch(object):
 
 def _identity_record(h, w):
     return _records([{"src_w": w, "src_h": h, "crop": [0, 0, w, h], "res": None, "win": [0, 0, w, h], "flip": 0,
-                      "filter": _lib.WV_RESAMPLE_BILINEAR}])
+                      "filter": _lib.WV_RESAMPLE_BILINEAR, "colour": []}])
 
 
 def pack(items):
-    """list of RawItem -> RawBatch (host tensors).  The packed descriptors pass wv_image_size_check here, on the host copy:
-    the device entry point cannot read them."""
+    """list of RawItem -> RawBatch (host tensors).  The packed descriptors pass wv_image_size_check (and the colour
+    descriptors wv_colour_jitter_check) here, on the host copy: the device entry points cannot read them."""
     if not items:
         raise ValueError("raw_collate: empty batch")
     H, W = items[0].out_hw
@@ -256,7 +349,7 @@ def pack(items):
     for it, off in zip(items, data_off):
         data[off:off + it.pixels.numel()] = it.pixels.reshape(-1)
     work = _align(B * H * W * 3)
-    per_stage = []
+    per_stage, colour_per_stage = [], []
     for i, rec in enumerate(recs):
         src = data_off[i]
         for s in range(len(rec)):
@@ -269,7 +362,13 @@ def pack(items):
                 work = _align(work + int(r["out_h"][0]) * int(r["dst_row_bytes"][0]))
             while len(per_stage) <= s:
                 per_stage.append([])
+                colour_per_stage.append([])
             per_stage[s].append(r)
+            col = getattr(items[i], "colour", None)
+            if col is not None and len(items[i].stages) and int(col["n_ops"][s]):
+                c = col[s:s + 1].copy()                     # the image the stage wrote: same place, same pitch
+                c["offset"], c["h"], c["w"], c["row_bytes"] = r["dst_offset"], r["out_h"], r["out_w"], r["dst_row_bytes"]
+                colour_per_stage[s].append(c)
     launches, first, chunks = [], 0, []
     for group in per_stage:
         g = np.concatenate(group)
@@ -282,7 +381,22 @@ def pack(items):
         first += len(g)
         chunks.append(g)
     desc = torch.from_numpy(np.concatenate(chunks).view(np.int32).reshape(-1, STAGE_WORDS).copy())
-    return RawBatch(data, desc, launches, (B, H, W), work)
+    if not any(colour_per_stage):
+        return RawBatch(data, desc, launches, (B, H, W), work)
+    colour_launches, first, chunks = [], 0, []
+    for group in colour_per_stage:
+        if not group:
+            colour_launches.append((first, 0, 0, 0))
+            continue
+        g = np.concatenate(group)
+        rc = check_colour_records(g)
+        if rc != 0:
+            _lib.check(rc, "wv_colour_jitter_check")
+        colour_launches.append((first, len(g), int(g["h"].max()), int(g["w"].max())))
+        first += len(g)
+        chunks.append(g)
+    colour = torch.from_numpy(np.concatenate(chunks).view(np.int32).reshape(-1, COLOUR_WORDS).copy())
+    return RawBatch(data, desc, launches, (B, H, W), work, colour, colour_launches)
 
 
 def raw_collate(batch):

@@ -55,6 +55,8 @@ const char *wv_last_error(void);
  * So were the NDCG entry points (wv_label_overlap_hist[_cpu], wv_ndcg_weights, wv_ndcg_at_ks[_cpu]): 76 symbols.
  * So were the attention maps of the head (wv_band_attn_maps[_workspace_bytes], wv_band_attn_maps_cpu): 79 symbols.
  * So was the image sizing (wv_image_size, wv_image_size_cpu, wv_image_size_check, struct wv_size_stage): 82 symbols.
+ * So was the colour jitter (wv_colour_jitter[_workspace_bytes], wv_colour_jitter_cpu, wv_colour_jitter_check, struct
+ * wv_colour_ops): 86 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -603,6 +605,47 @@ int wv_image_size(const uint8_t *src, uint8_t *dst, const wv_size_stage *stages,
                   int max_ksize, void *stream);
 int wv_image_size_cpu(const uint8_t *src, uint8_t *dst, const wv_size_stage *stages, int n);
 int wv_image_size_check(const wv_size_stage *stages, int n);
+
+/* ------------------------------------------------------------------------------------------
+ * Colour jitter: brightness, contrast and saturation in a per-image order, IN PLACE on a ragged batch of 3-channel uint8 HWC
+ * images inside one byte buffer -- torchvision's ColorJitter on PIL input (config/transform/voc_swt.yaml, cub_swt.yaml:
+ * brightness = contrast = saturation = 0.25, hue 0), which is Pillow's ImageEnhance.  Restated in csrc/colour.hpp; bit-identical
+ * to ImageEnhance of Pillow 12, and the device entry point and the host twin agree byte for byte.
+ * Every operation is Image.blend(degenerate, image, factor): byte = (uint8)clamp((float)d + f * (float)(x - d), 0, 255), one
+ * fp32 multiply and one fp32 add, truncated; d = 0 (brightness), L of the pixel (saturation), or int(mean(L) + 0.5) of the
+ * whole image AS IT IS WHEN CONTRAST RUNS (contrast); L = (19595 r + 38470 g + 7471 b + 0x8000) >> 16.  Hue is not
+ * implemented.
+ * One wv_colour_ops is one image: it lies at img + offset, h rows of w pixels, row pitch row_bytes; kind[0 .. n_ops) and
+ * factor[0 .. n_ops) are its operations in the order they run (n_ops = 0: the image is left alone).
+ * wv_colour_jitter                 ops: DEVICE array of n descriptors.  max_h / max_w: maxima of h and w over them (they size
+ *                                  the grid; smaller than the truth leaves pixels unchanged, never writes elsewhere).
+ *                                  Two launches: the L sums of the images whose chain has contrast (64-bit integers in
+ *                                  `workspace`, which the entry point clears on the stream), then the chain.  Only bytes of
+ *                                  the images' rows are written; gaps between images and row padding are never touched.  No
+ *                                  hidden synchronisation.  The descriptors are device memory: the caller runs
+ *                                  wv_colour_jitter_check on its host copy before the upload.
+ * wv_colour_jitter_workspace_bytes the n 64-bit sums; a shorter workspace is WV_ENOMEM.
+ * wv_colour_jitter_cpu             host twin (HOST pointers); runs wv_colour_jitter_check itself.
+ * wv_colour_jitter_check           the one argument check (HOST descriptors): WV_EINVAL for a side < 1, a row pitch shorter
+ *                                  than the row, a negative offset, an unknown kind, a kind listed twice, n_ops outside 0..3, a
+ *                                  factor that is negative or not finite, images of two descriptors that overlap; WV_ENOTSUP
+ *                                  for a side above 16384; the message names the field.
+ * ------------------------------------------------------------------------------------------ */
+#define WV_COLOUR_BRIGHTNESS 0
+#define WV_COLOUR_CONTRAST 1
+#define WV_COLOUR_SATURATION 2
+typedef struct wv_colour_ops {
+    int64_t offset; /* bytes from `img` to the image's first pixel */
+    int32_t h, w, row_bytes;
+    int32_t n_ops;
+    int32_t kind[3]; /* WV_COLOUR_*, in the order the operations run */
+    float factor[3];
+} wv_colour_ops;
+size_t wv_colour_jitter_workspace_bytes(int n);
+int wv_colour_jitter(uint8_t *img, const wv_colour_ops *ops, int n, int max_h, int max_w, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int wv_colour_jitter_cpu(uint8_t *img, const wv_colour_ops *ops, int n);
+int wv_colour_jitter_check(const wv_colour_ops *ops, int n);
 
 #ifdef __cplusplus
 }
