@@ -6,63 +6,27 @@
 // H (even / odd ROWS), then along W, both with zero-padded shifts ('constant' pad of the shifted operand at every
 // lifting step, not a signal extension), coefficients joined as [s | d] per axis; LL = top-left, LH = bottom-left,
 // HL = top-right, HH = bottom-right, then the 2-D scales (1/sqrt(2)^2, 1, 1, sqrt(2)).
-// Every product and sum is rounded separately and in the reference's order (__fmul_rn / __fadd_rn: no FMA
-// contraction), so the output is bit-identical to the reference's float32 torch ops.
+// Every product and sum is rounded separately and in the reference's order (plain operators in lifting.hpp, compiled
+// without FMA contraction), so the output is bit-identical to the reference's float32 torch ops.
 #include "common.hpp"
-#include <cmath>
+#include "lifting.hpp"
 
-// hipcc contracts a*b + c into an FMA by default, and its __fmul_rn / __fadd_rn are plain operators that take part in
-// that: this file is compiled with -ffp-contract=off (csrc/Makefile), which is what makes the result bit-identical to
-// the reference.  The pragma covers builds that forget the flag where the compiler honours it.
+// hipcc contracts a*b + c into an FMA by default: this file is compiled with -ffp-contract=off (csrc/Makefile), which is
+// what makes the result bit-identical to the reference.  The pragma covers builds that forget the flag where the compiler
+// honours it.  The lifting chain itself is lifting.hpp's, shared with wv_lift_images and the host twin.
 #pragma clang fp contract(off)
 
 namespace wv {
 
-struct LiftConsts {
-    float a1, a2, a3, a4, k, rk;    // cdf 9/7 steps and scale; for haar k = sqrt(2), rk = 1/sqrt(2)
-    float sc_ll, sc_hh;             // 2-D scales of LL and HH (LH, HL: 1)
-};
+using LiftConsts = lift::Consts;
 
 // s and d of pair index i along a strided 1-D signal of n pairs: ev(j) = p[2j*stride], od(j) = p[(2j+1)*stride]
 template <int BASIS>
 __device__ __forceinline__ void lift_pair(const float *__restrict__ p, int64_t stride, int n, int i, const LiftConsts &c,
                                           float &s, float &d)
 {
-    auto ev = [&](int j) { return p[(int64_t)(2 * j) * stride]; };
-    auto od = [&](int j) { return p[(int64_t)(2 * j + 1) * stride]; };
-    if constexpr (BASIS == 0) {
-        const float e = ev(i);
-        const float od1 = __fadd_rn(od(i), __fmul_rn(-1.0f, e));
-        const float ev1 = __fadd_rn(e, __fmul_rn(0.5f, od1));
-        s = __fmul_rn(c.k, ev1);
-        d = __fmul_rn(c.rk, od1);
-    } else {
-        // od1 on [i-2, i+1], ev1 on [i-1, i+1], od2 on [i-1, i], ev2 at i; an index outside [0, n) stands for the zero pad
-        float e[5];                       // ev(i-2 .. i+2)
-#pragma unroll
-        for (int u = 0; u < 5; ++u) { const int j = i - 2 + u; e[u] = (j >= 0 && j < n) ? ev(j) : 0.f; }
-        float od1[4];                     // od1(i-2 .. i+1)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = i - 2 + u;
-            od1[u] = (j >= 0 && j < n) ? __fadd_rn(od(j), __fadd_rn(__fmul_rn(c.a1, e[u]), __fmul_rn(c.a1, e[u + 1]))) : 0.f;
-        }
-        float ev1[3];                     // ev1(i-1 .. i+1)
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-            const int j = i - 1 + u;
-            ev1[u] = (j >= 0 && j < n) ? __fadd_rn(e[u + 1], __fadd_rn(__fmul_rn(c.a2, od1[u]), __fmul_rn(c.a2, od1[u + 1]))) : 0.f;
-        }
-        float od2[2];                     // od2(i-1, i)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int j = i - 1 + u;
-            od2[u] = (j >= 0 && j < n) ? __fadd_rn(od1[u + 1], __fadd_rn(__fmul_rn(c.a3, ev1[u]), __fmul_rn(c.a3, ev1[u + 1]))) : 0.f;
-        }
-        const float ev2 = __fadd_rn(ev1[1], __fadd_rn(__fmul_rn(c.a4, od2[0]), __fmul_rn(c.a4, od2[1])));
-        s = __fmul_rn(c.k, ev2);
-        d = __fmul_rn(c.rk, od2[1]);
-    }
+    lift::pair<BASIS>([&](int j) { return p[(int64_t)(2 * j) * stride]; }, [&](int j) { return p[(int64_t)(2 * j + 1) * stride]; }, n, i, c, s,
+                      d);
 }
 
 // pass along H: in [P][H][W] -> tmp [P][H][W], rows [0, H/2) = s, [H/2, H) = d
@@ -123,16 +87,7 @@ extern "C" int wv_lifting2d_forward(const float *in, int64_t planes, int H, int 
     if (planes == 0) return WV_OK;
     const size_t need = wv_lifting2d_workspace_bytes(planes, H, W);
     if (!workspace || workspace_bytes < need) WV_FAIL(WV_ENOMEM, "lifting2d: workspace %zu < %zu bytes", workspace_bytes, need);
-    LiftConsts c;
-    if (basis == 0) {
-        const double k = std::sqrt(2.0);
-        c = {0.f, 0.f, 0.f, 0.f, (float)k, (float)(1.0 / k), 0.f, 0.f};
-    } else {
-        const double k = 1.149604398;
-        c = {(float)-1.58613432, (float)-0.05298011854, (float)0.8829110762, (float)0.4435068522, (float)k, (float)(1.0 / k), 0.f, 0.f};
-    }
-    c.sc_ll = (float)(1.0 / (std::sqrt(2.0) * std::sqrt(2.0)));
-    c.sc_hh = (float)std::sqrt(2.0);
+    const LiftConsts c = lift::consts(basis);
     hipStream_t st = (hipStream_t)stream;
     float *tmp = (float *)workspace;
     const int64_t na = planes * (H / 2) * W, nb = planes * H * (W / 2);

@@ -162,6 +162,12 @@ SIGNATURES = {
     "wv_colour_jitter": (_i, [_vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "wv_colour_jitter_cpu": (_i, [_vp, _vp, _i]),
     "wv_colour_jitter_check": (_i, [_vp, _i]),
+    "wv_lift_out_size": (_i, [_i, _i, _i]),
+    "wv_lift_images_tile": (_i, [_i]),
+    "wv_lift_images_check": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "wv_lift_images_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "wv_lift_images": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "wv_lift_images_cpu": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _i, _i, _i, _vp]),
 }
 
 _LIB = None

@@ -226,6 +226,65 @@ def rawstack(x, copies=4, channels_last=False):
     return out
 
 
+_LIFT_BASIS = {"haar": 0, "cdf97": 1}
+
+
+def _lift_args(x, channels_last, mean, std, basis, levels, ll_only, what):
+    """-> (x contiguous, C-ABI arguments between `in` and `out`, output shape).  The argument check is the library's."""
+    if basis not in _LIFT_BASIS:
+        raise ValueError(f"{what}: basis must be 'haar' or 'cdf97', got {basis!r}")
+    x = x.contiguous()
+    layout, B, C, H, W = _layout_and_shape(x, channels_last)
+    dt = _in_dtype(x)
+    if (mean is None) != (std is None):
+        raise ValueError(f"{what}: mean and std come together")
+    if mean is not None and (len(mean) != C or len(std) != C):
+        raise ValueError(f"{what}: mean / std need one value per channel ({C}), got {len(mean)} / {len(std)}")
+    lib = _lib.load()
+    b, levels, ll_only = _LIFT_BASIS[basis], int(levels), int(bool(ll_only))
+    _lib.check(lib.wv_lift_images_check(dt, layout, B, C, H, W, b, levels, ll_only), "wv_lift_images_check")
+    h, w = (lib.wv_lift_out_size(H, b, levels), lib.wv_lift_out_size(W, b, levels)) if levels else (H, W)
+    shape = (B, C, h, w) if levels == 0 or ll_only else (B, C, 4, h, w)
+    fm = _lib.host_floats(mean) if mean is not None else None
+    fs = _lib.host_floats(std) if std is not None else None
+    args = (dt, layout, B, C, H, W, int(dt == _lib.WV_DT_U8), fm, fs, b, levels, ll_only)
+    return x, args, shape
+
+
+def lift_images(x, mean=None, std=None, basis="haar", levels=1, ll_only=False, channels_last=False):
+    """The tensor tail of the legacy configs on a GPU batch: ToTensor -> [Normalize(mean, std)] -> [CustomTransform(levels,
+    basis, coarse_only=True, ll_only)], bit-identical to the reference's float32 torch ops (wv_lift_images: one launch per
+    level).  x: uint8 [B,C,H,W] (or [B,H,W,C] with channels_last: what size_images returns), divided by 255 and normalised;
+    or float32, used as it is (mean / std must be None).  -> float32 [B,C,4,h,w] = (LL, LH, HL, HH) of the coarsest level,
+    [B,C,h,w] with ll_only, [B,C,H,W] for levels = 0 (the conversion alone)."""
+    lib = _lib.require_gpu()
+    if not x.is_cuda:
+        raise ValueError("lift_images: input must live on the GPU (lift_images_host is the host twin)")
+    x, args, shape = _lift_args(x, channels_last, mean, std, basis, levels, ll_only, "lift_images")
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if shape[0] == 0:
+        return out
+    ws_bytes = lib.wv_lift_images_workspace_bytes(*args[2:6], args[9], args[10])
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    with torch.cuda.device(x.device):
+        _lib.check(lib.wv_lift_images(_lib.ptr(x), *args, _lib.ptr(out), _lib.ptr(ws), ctypes.c_size_t(ws_bytes), _lib.stream_ptr()),
+                   "wv_lift_images")
+    return out
+
+
+def lift_images_host(x, mean=None, std=None, basis="haar", levels=1, ll_only=False, channels_last=False):
+    """Host twin of lift_images (wv_lift_images_cpu): host tensors in, the same bits out."""
+    lib = _lib.load()
+    if x.is_cuda:
+        raise ValueError("lift_images_host: the host twin takes host tensors (lift_images is the device function)")
+    x, args, shape = _lift_args(x, channels_last, mean, std, basis, levels, ll_only, "lift_images_host")
+    out = torch.empty(shape, dtype=torch.float32)
+    if shape[0] == 0:
+        return out
+    _lib.check(lib.wv_lift_images_cpu(_lib.ptr(x), *args, _lib.ptr(out)), "wv_lift_images_cpu")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Host twins (wv_*_forward_cpu): what the plugins' __call__ runs inside forked DataLoader workers, where the
 # reference runs pywt (flikr_coco.py:59-60 -> custom_transforms.py:145-157) and the GPU is out of reach.

@@ -4,7 +4,11 @@
 (``wv_lifting2d_forward``, bit-identical to the reference's float32 torch ops); padding and the level cascade are host
 logic.  Inputs are float tensors ``[C, H, W]`` or ``[N, C, H, W]`` (what ToTensor / Normalize hand over); a CPU tensor is
 moved to the GPU for the call and the result comes back on its original device, so the classes also work as a
-per-image transform in a ``num_workers=0`` pipeline.
+per-image transform in a ``num_workers=0`` pipeline.  With ``device="cpu"``, or inside a DataLoader worker, ``CustomTransform``
+takes the library's host twin instead (``wv_lift_images_cpu``: same bits, no GPU touched).
+
+The batched form is ``TensorTailTransform``: the whole tensor tail ``ToTensor [-> Normalize] [-> CustomTransform]`` of a
+deferred pipeline as one plugin step whose ``apply_batch`` is one ``wv_lift_images`` call on the sized uint8 batch.
 """
 import ctypes
 from collections.abc import Sequence
@@ -14,6 +18,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
+from . import functional as Fn
+from .custom_transforms import BaseWaveletTransform
 
 _BASIS = {"haar": 0, "cdf97": 1}
 
@@ -132,10 +138,31 @@ class CustomTransform:
 
     def __init__(self, decompose_levels=3, basis="haar", coarse_only=True, ll_only=False, device='cuda', dwt_mode='dwt'):
         self.dwt = WAVELET_DICT[basis](n_levels=decompose_levels)
-        self.decompose_levels = decompose_levels
+        self.decompose_levels, self.basis, self.device = decompose_levels, basis, device
         self.coarse_only, self.ll_only = coarse_only, ll_only
 
+    def _use_host(self, img):
+        """A host tensor with device='cpu', or inside a DataLoader worker (which cannot use the parent's GPU context): the
+        library's host twin."""
+        if img.is_cuda:
+            return False
+        if self.device is not None and torch.device(self.device).type == "cpu":
+            return True
+        from torch.utils.data import get_worker_info
+        return get_worker_info() is not None
+
+    def _check_stackable(self):
+        if not self.coarse_only and self.decompose_levels > 1:   # levels have different sizes: nothing to stack (the reference raises as well)
+            what = "approx" if self.ll_only else "subbands"
+            raise NotImplementedError(f"Full {what} not implemented yet for decompose_levels > 1 ")
+
     def __call__(self, img):
+        if self._use_host(img):
+            self._check_stackable()                 # one level: every option pair is the coarsest level's bands
+            *lead, H, W = img.shape
+            planes = img.float().reshape(-1, 1, H, W)
+            out = Fn.lift_images_host(planes, basis=self.basis, levels=self.decompose_levels, ll_only=self.ll_only)
+            return out.reshape(*lead, *out.shape[2:])
         approx, details = self.dwt(img)
         if self.coarse_only:
             top = approx[-1]
@@ -145,3 +172,70 @@ class CustomTransform:
             raise NotImplementedError(f"Full {what} not implemented yet for decompose_levels > 1 ")
         bands = list(approx) if self.ll_only else [a.unsqueeze(-3) for a in approx] + list(details)
         return torch.cat(bands, dim=-3)
+
+
+class TensorTailTransform(BaseWaveletTransform):
+    """The deferred form of a pipeline's tensor tail, ``ToTensor [-> Normalize] [-> CustomTransform]``, as ONE plugin step
+    (``build_transform(cfg, defer=True)`` folds the tail into it).  Per image it only hands the sized pixels on --
+    ``uint8 [C, H, W]`` under host sizing, a ``sizing.RawItem`` under device sizing; nothing is resized to fit a level (the
+    lifting pads with zeros, there is no ``fix_size``).  ``apply_batch`` runs the whole tail on the collated batch:
+    ``functional.sized`` then ``functional.lift_images`` (``lift_images_host`` for host tensors), bit-identical to the
+    per-image torch ops.  ``custom`` = CustomTransform's kwargs, or None for a plain ``ToTensor [-> Normalize]`` tail
+    (levels = 0: float32 ``[B, C, H, W]``)."""
+
+    def __init__(self, mean=None, std=None, custom=None, defer=True, device=None, sizing="host"):
+        custom = None if custom is None else dict(custom)
+        levels = 0 if custom is None else int(custom.get("decompose_levels", 3))
+        basis = "haar" if custom is None else custom.get("basis", "haar")
+        if basis not in _BASIS:
+            raise KeyError(basis)
+        if not defer:
+            raise ValueError("TensorTailTransform is the deferred form of the tail; with defer=False the steps run per image")
+        super().__init__(level=levels, wavelet=basis, defer=True, device=device, sizing=sizing)
+        self.ll_only = bool(custom.get("ll_only", False)) if custom else False
+        if custom is not None and not custom.get("coarse_only", True) and levels > 1:
+            what = "approx" if self.ll_only else "subbands"
+            raise NotImplementedError(f"Full {what} not implemented yet for decompose_levels > 1 ")
+        if (mean is None) != (std is None):
+            raise ValueError("Normalize needs mean and std")
+        self.mean = None if mean is None else tuple(float(v) for v in mean)
+        self.std = None if std is None else tuple(float(v) for v in std)
+        if self.std is not None and any(torch.tensor(v, dtype=torch.float32) == 0 for v in self.std):
+            raise ValueError("std evaluated to zero after conversion to torch.float32, leading to division by zero.")
+        self.custom = custom
+
+    def fix_size(self, image):
+        return image
+
+    def __call__(self, img):
+        import numpy as np
+        from .sizing import LazyImage
+        if self.sizing == "device":
+            lazy = img if isinstance(img, LazyImage) else LazyImage(img)
+            return lazy.to_item()
+        arr = np.array(img)
+        if arr.dtype != np.uint8 or arr.ndim not in (2, 3):
+            raise TypeError(f"deferred ToTensor expects an 8-bit image, got an array of shape {arr.shape} and dtype {arr.dtype}")
+        if arr.ndim == 2:
+            arr = arr[:, :, None]
+        return torch.from_numpy(np.ascontiguousarray(arr)).permute(2, 0, 1).contiguous()
+
+    def apply_batch(self, batch, channels_last=False, **kwargs):
+        batch, channels_last = Fn.sized(batch, channels_last)
+        if batch.dim() != 4:
+            raise ValueError(f"expected a 4-D batch, got shape {tuple(batch.shape)}")
+        C = batch.shape[3] if channels_last else batch.shape[1]
+        m, s = self.mean, self.std
+        if m is not None and len(m) == 1 and C > 1:              # Normalize broadcasts one value over the channels
+            m, s = m * C, s * C
+        fn = Fn.lift_images if batch.is_cuda else Fn.lift_images_host
+        return fn(batch, m, s, basis=self.wavelet, levels=self.level, ll_only=self.ll_only, channels_last=channels_last)
+
+    def __repr__(self):
+        steps = ["ToTensor()"]
+        if self.mean is not None:
+            steps.append(f"Normalize(mean={self.mean}, std={self.std})")
+        if self.custom is not None:
+            steps.append(f"CustomTransform(decompose_levels={self.level}, basis={self.wavelet}, "
+                         f"coarse_only={self.custom.get('coarse_only', True)}, ll_only={self.ll_only})")
+        return "TensorTailTransform(" + " -> ".join(steps) + ")"

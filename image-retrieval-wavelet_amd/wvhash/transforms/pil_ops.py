@@ -9,6 +9,10 @@ PIL images).  They decode and size images on the host; the arithmetic of the pat
 With ``build_transform(cfg, defer=True, sizing="device")`` the same classes receive a ``sizing.LazyImage`` and only record
 the geometry; the pixels are sized on the GPU by ``functional.size_images`` (bit-identical to Pillow, see sizing.py).
 ``ColorJitter`` (config/transform/voc_swt.yaml, cub_swt.yaml) records its drawn operations the same way.
+
+``ToTensor``, ``Normalize`` and ``RandomCrop`` (config/transform/basic.yaml, cub.yaml, cub_dwt.yaml, ...) are here too;
+``build_transform(cfg, defer=True)`` folds a trailing ``ToTensor [-> Normalize] [-> CustomTransform]`` into one batched plugin
+step (lifting.TensorTailTransform).
 """
 import math
 import numbers
@@ -116,6 +120,98 @@ class RandomResizedCrop(object):
         return f"RandomResizedCrop(size={self.size}, scale={self.scale}, ratio={self.ratio})"
 
 
+class RandomCrop(object):
+    """torchvision.transforms.RandomCrop for PIL input without padding: a random ``size`` window of the image.  The parameter
+    rule is torchvision's get_params: no draw when the image already has the size, otherwise ``torch.randint(0, h - th + 1)``
+    for the row first, then ``torch.randint(0, w - tw + 1)`` for the column, both from the torch global RNG; an image smaller
+    than the crop raises ValueError.  ``padding`` / ``pad_if_needed`` other than their defaults are refused (ValueError): no
+    config of the reference sets them.  Draw-for-draw parity with torchvision is the intent; parity unpinned: no test compares against
+    torchvision.  On a ``sizing.LazyImage`` the crop is recorded."""
+
+    def __init__(self, size, padding=None, pad_if_needed=False, fill=0, padding_mode="constant", **kwargs):
+        if padding is not None or pad_if_needed:
+            raise ValueError("RandomCrop: padding / pad_if_needed are not implemented without torchvision")
+        if isinstance(size, numbers.Number):
+            self.size = (int(size), int(size))
+        elif len(size) == 1:
+            self.size = (int(size[0]), int(size[0]))
+        elif len(size) == 2:
+            self.size = (int(size[0]), int(size[1]))
+        else:
+            raise ValueError("Please provide only two dimensions (h, w) for size.")
+
+    @staticmethod
+    def get_params(width, height, output_size):
+        """-> (top, left, h, w)"""
+        th, tw = output_size
+        if height < th or width < tw:
+            raise ValueError(f"Required crop size {(th, tw)} is larger than input image size {(height, width)}")
+        if width == tw and height == th:
+            return 0, 0, height, width
+        i = torch.randint(0, height - th + 1, size=(1,)).item()
+        j = torch.randint(0, width - tw + 1, size=(1,)).item()
+        return i, j, th, tw
+
+    def __call__(self, img):
+        width, height = img.size
+        i, j, h, w = self.get_params(width, height, self.size)
+        return img.crop((j, i, j + w, i + h))
+
+    def __repr__(self):
+        return f"RandomCrop(size={self.size})"
+
+
+class ToTensor(object):
+    """torchvision.transforms.ToTensor for 8-bit images: PIL image (or uint8 ndarray [H, W] / [H, W, C]) ->
+    ``float32 [C, H, W]``, the bytes divided by 255 (``.to(float32).div(255)``)."""
+
+    def __call__(self, pic):
+        import numpy as np
+        if isinstance(pic, LazyImage):
+            raise TypeError("ToTensor cannot run on a recorded image: build the pipeline with defer=True, which folds the tensor tail")
+        if isinstance(pic, Image.Image) and pic.mode not in ("L", "P", "RGB", "RGBA", "CMYK", "YCbCr", "HSV", "LA"):
+            raise TypeError(f"ToTensor: only 8-bit image modes are implemented without torchvision, got mode {pic.mode}")
+        arr = np.array(pic)
+        if arr.dtype != np.uint8 or arr.ndim not in (2, 3):
+            raise TypeError(f"ToTensor: expected an 8-bit image, got an array of shape {arr.shape} and dtype {arr.dtype}")
+        if arr.ndim == 2:
+            arr = arr[:, :, None]
+        return torch.from_numpy(arr).permute(2, 0, 1).contiguous().to(dtype=torch.float32).div(255)
+
+    def __repr__(self):
+        return "ToTensor()"
+
+
+class Normalize(object):
+    """torchvision.transforms.Normalize: ``(tensor - mean[c]) / std[c]`` per channel as ``sub_`` then ``div_`` in the tensor's
+    dtype (on a clone unless ``inplace``); a non-float tensor is a TypeError, a std of zero torchvision's ValueError."""
+
+    def __init__(self, mean, std, inplace=False, **kwargs):
+        self.mean, self.std, self.inplace = mean, std, inplace
+
+    def __call__(self, tensor):
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError(f"img should be Tensor Image. Got {type(tensor)}")
+        if not tensor.is_floating_point():
+            raise TypeError(f"Input tensor should be a float tensor. Got {tensor.dtype}.")
+        if tensor.ndim < 3:
+            raise ValueError(f"Expected tensor to be a tensor image of size (..., C, H, W). Got tensor.size() = {tensor.size()}")
+        if not self.inplace:
+            tensor = tensor.clone()
+        mean = torch.as_tensor(self.mean, dtype=tensor.dtype, device=tensor.device)
+        std = torch.as_tensor(self.std, dtype=tensor.dtype, device=tensor.device)
+        if (std == 0).any():
+            raise ValueError(f"std evaluated to zero after conversion to {tensor.dtype}, leading to division by zero.")
+        if mean.ndim == 1:
+            mean = mean.view(-1, 1, 1)
+        if std.ndim == 1:
+            std = std.view(-1, 1, 1)
+        return tensor.sub_(mean).div_(std)
+
+    def __repr__(self):
+        return f"Normalize(mean={self.mean}, std={self.std})"
+
+
 class RandomHorizontalFlip(object):
     """Mirror left-right when ``torch.rand(1) < p`` (torchvision's rule and draw; parity unpinned like RandomResizedCrop)."""
 
@@ -213,8 +309,16 @@ def build_transform(config, defer=False, device=None, sizing="host"):
     sizing="host" (default): the geometry steps resample, and ColorJitter enhances, with PIL in the worker.  sizing="device" (needs defer=True and a
     wavelet plugin at the end): they only record -- always this module's classes, which know how to --, the plugin
     returns a ``sizing.RawItem`` per image, ``sizing.raw_collate`` packs a batch and the GPU sizes it
-    (``functional.size_images``): same pixels bit for bit."""
+    (``functional.size_images``): same pixels bit for bit.
+    The tensor tail of the legacy configs, ``ToTensor [-> Normalize] [-> CustomTransform]`` at the END of a node, resolves
+    without torchvision too (``ToTensor`` / ``Normalize`` above, ``CustomTransform`` / ``ResizeSubBands`` of lifting.py).
+    With defer=True such a tail collapses into ONE plugin step, ``lifting.TensorTailTransform``: the workers hand on the
+    sized uint8 pixels and ``apply_batch`` runs the whole tail on the collated batch (``functional.lift_images``; a plain
+    ``ToTensor [-> Normalize]`` tail is the same call with no lifting level).  A ``ToTensor`` / ``Normalize`` /
+    ``CustomTransform`` that is NOT part of such a tail (tensor steps in front of geometry) cannot be deferred: ValueError
+    naming the step; with defer=False those nodes run per image."""
     from . import custom_transforms as ct
+    from . import lifting
     if sizing not in ("host", "device"):
         raise ValueError(f"build_transform: sizing must be 'host' or 'device', got {sizing!r}")
     if sizing == "device" and not defer:
@@ -226,19 +330,46 @@ def build_transform(config, defer=False, device=None, sizing="host"):
     if sizing == "device":
         tvt = None
     local = {"Resize": Resize, "CenterCrop": CenterCrop, "RandomResizedCrop": RandomResizedCrop,
-             "RandomHorizontalFlip": RandomHorizontalFlip, "ColorJitter": ColorJitter}
+             "RandomHorizontalFlip": RandomHorizontalFlip, "ColorJitter": ColorJitter, "RandomCrop": RandomCrop,
+             "ToTensor": ToTensor, "Normalize": Normalize}
+    items = [(name, dict(kwargs or {})) for name, kwargs in dict(config).items()]
+    extra = {"sizing": sizing} if sizing != "host" else {}
+    tail = None
+    if defer:
+        # the tensor tail: ToTensor [-> Normalize] [-> CustomTransform] and nothing behind it
+        names = [name for name, _ in items]
+        for cut in (3, 2, 1):
+            if tuple(names[-cut:]) in (("ToTensor", "Normalize", "CustomTransform"), ("ToTensor", "Normalize"), ("ToTensor", "CustomTransform"),
+                                       ("ToTensor",)):
+                folded = dict(items[-cut:])
+                norm = folded.get("Normalize") or {}
+                if norm.get("mean") is None and "Normalize" in folded:
+                    raise TypeError("Normalize needs mean and std")
+                tail = lifting.TensorTailTransform(mean=norm.get("mean"), std=norm.get("std"), custom=folded.get("CustomTransform"),
+                                                   defer=True, device=device, **extra)
+                items = items[:-cut]
+                break
+        for pos, (name, _) in enumerate(items):
+            if name in ("ToTensor", "Normalize", "CustomTransform", "ResizeSubBands"):
+                raise ValueError(f"build_transform: defer=True folds only a tensor tail ToTensor [-> Normalize] [-> CustomTransform] at the "
+                                 f"end of the node; step {pos} '{name}' of {names} is a tensor step in front of other steps and cannot "
+                                 "be deferred (build the node with defer=False)")
     steps = []
-    for name, kwargs in dict(config).items():
-        kwargs = dict(kwargs or {})
+    for name, kwargs in items:
         if hasattr(ct, name) and name.endswith("Transform"):
-            extra = {"sizing": sizing} if sizing != "host" else {}
             steps.append(getattr(ct, name)(defer=defer, device=device, **extra, **kwargs))
+        elif name in ("CustomTransform", "ResizeSubBands"):
+            if name == "CustomTransform" and device is not None:
+                kwargs.setdefault("device", device)
+            steps.append(getattr(lifting, name)(**kwargs))
         elif tvt is not None and hasattr(tvt, name):
             steps.append(getattr(tvt, name)(**kwargs))
         elif name in local:
             steps.append(local[name](**kwargs))
         else:
             raise AttributeError(f"transform '{name}' is neither a wvhash plugin nor available without torchvision")
+    if tail is not None:
+        steps.append(tail)
     if sizing == "device":
         if not steps or not isinstance(steps[-1], ct.BaseWaveletTransform):
             raise ValueError("build_transform: sizing='device' needs a wavelet plugin as the last step of the pipeline")

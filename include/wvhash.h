@@ -57,6 +57,8 @@ const char *wv_last_error(void);
  * So was the image sizing (wv_image_size, wv_image_size_cpu, wv_image_size_check, struct wv_size_stage): 82 symbols.
  * So was the colour jitter (wv_colour_jitter[_workspace_bytes], wv_colour_jitter_cpu, wv_colour_jitter_check, struct
  * wv_colour_ops): 86 symbols.
+ * So was the batched lifting tail (wv_lift_images[_workspace_bytes], wv_lift_images_cpu, wv_lift_images_check,
+ * wv_lift_out_size, wv_lift_images_tile): 92 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -144,10 +146,49 @@ int wv_dwt2d_forward(const void *in, int in_dtype, int in_layout, float *out, in
  * wavelets/haar.py:21-86, wavelets/cdf_97.py:33-133): basis 0 = haar, 1 = cdf 9/7, zero-padded lifting steps,
  * 2-D scales (1/2, 1, 1, sqrt 2).  in: float32 [planes][H][W], H and W even (the caller pads like
  * HaarLifting / Cdf97Lifting do);  ll: [planes][H/2][W/2];  hi: [planes][3][H/2][W/2] = (LH, HL, HH).
- * Bit-identical to the reference's float32 torch ops (every product and sum rounded separately, same order). */
+ * Bit-identical to the reference's float32 torch ops (every product and sum rounded separately, same order).
+ * One plane-sized fp32 workspace, two launches, all four bands of ONE level of already padded planes: the per-image
+ * building block behind HaarLifting / Cdf97Lifting.  A whole pipeline tail (ToTensor -> Normalize -> CustomTransform) on a
+ * batch is wv_lift_images below; both compile the same lifting chain (csrc/lifting.hpp). */
 size_t wv_lifting2d_workspace_bytes(int64_t planes, int H, int W);
 int wv_lifting2d_forward(const float *in, int64_t planes, int H, int W, int basis, float *ll, float *hi,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* The tensor tail of the legacy configs for a whole batch: ToTensor -> [Normalize] -> [CustomTransform(levels, basis,
+ * coarse_only=True, ll_only)] on the sized images, bit-identical to the reference's float32 torch ops.
+ * in     [B][C][H][W] (WV_LAYOUT_NCHW) or [B][H][W][C] (WV_LAYOUT_NHWC, what wv_image_size writes), tightly packed.
+ *        WV_DT_U8: each byte x of channel c becomes  t = (float)x / 255.0f  when to_tensor = 1 ((float)x when 0), then
+ *        v = (t - mean[c]) / std[c]  when mean / std are given: a true division, a subtraction and a true division, each
+ *        rounded to fp32 -- ToTensor's .div(255), Normalize's sub_ / div_.  mean, std: HOST pointers to C floats each,
+ *        both NULL = no Normalize.  WV_DT_F32: the values are used as they are (to_tensor = 0, mean = std = NULL).
+ * levels >= 1: per level the plane is taken as zero-padded at the right and bottom (haar: to even sizes, cdf 9/7: to
+ *        multiples of 4; the pad is +0.0 and comes AFTER Normalize; nothing is padded in memory), then one 2-D lifting level
+ *        as wv_lifting2d_forward defines it.  Only the approximation feeds the next level.
+ * out    float32, h = wv_lift_out_size(H, basis, levels), w likewise:
+ *        levels >= 1, ll_only = 0: [B][C][4][h][w] = (LL, LH, HL, HH) of the coarsest level
+ *        levels >= 1, ll_only = 1: [B][C][h][w]
+ *        levels  = 0             : [B][C][H][W], the conversion alone (ll_only is not looked at)
+ * wv_lift_images            one launch per level on `stream`; a non-final level stores its LL planes alone into the
+ *                           workspace (wv_lift_images_workspace_bytes: 0 for levels <= 1; a shorter one is WV_ENOMEM,
+ *                           answered before any launch).  No hidden synchronisation, no allocation, no copy.
+ * wv_lift_images_cpu        host twin (HOST pointers, single-threaded, no HIP call): the same bits.
+ * wv_lift_images_check      the one argument check of both.  WV_EINVAL: an unknown dtype / layout / basis, B < 0, C, H or
+ *                           W < 1, levels < 0, ll_only outside {0, 1}.  WV_ENOTSUP, the kernel's limits: C > 4, H or W >
+ *                           16384, levels > 16, B * C > 2^31 - 1.  Both entry points add: to_tensor outside {0, 1}, mean
+ *                           without std, to_tensor = 1 on float32 input, a std of 0 or a NaN (WV_EINVAL); Normalize on
+ *                           float32 input (WV_ENOTSUP: it is folded into the 256-entry byte table only).
+ * wv_lift_out_size          length of one axis after `levels` levels (0 for arguments the check refuses).
+ * wv_lift_images_tile       input samples per workgroup tile along H (axis 0) and W (axis 1), for tests that place sizes
+ *                           around the tile edges. */
+int wv_lift_out_size(int n, int basis, int levels);
+int wv_lift_images_tile(int axis);
+int wv_lift_images_check(int in_dtype, int in_layout, int B, int C, int H, int W, int basis, int levels, int ll_only);
+size_t wv_lift_images_workspace_bytes(int B, int C, int H, int W, int basis, int levels);
+int wv_lift_images(const void *in, int in_dtype, int in_layout, int B, int C, int H, int W, int to_tensor,
+                   const float *mean, const float *std, int basis, int levels, int ll_only, float *out, void *workspace,
+                   size_t workspace_bytes, void *stream);
+int wv_lift_images_cpu(const void *in, int in_dtype, int in_layout, int B, int C, int H, int W, int to_tensor,
+                       const float *mean, const float *std, int basis, int levels, int ll_only, float *out);
 
 /* ------------------------------------------------------------------------------------------
  * Bit packing of +-1 hash codes and multi-hot labels.
