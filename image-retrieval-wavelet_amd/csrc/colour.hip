@@ -23,14 +23,6 @@ constexpr int kThreads = 256;
 constexpr int kGroupsPerThread = 4;
 constexpr int kTileGroups = kThreads * kGroupsPerThread;
 
-// A byte behind an empty asm: packing clamped bytes with `lo | hi << 8` invites hipcc's packed-convert fusions, one of which
-// gave wrong upper bytes on gfx950 (image_size.hip: clip8_byte).  Through the asm every byte is converted on its own.
-__device__ __forceinline__ uint32_t own_byte(int v)
-{
-    asm volatile("" : "+v"(v));
-    return (uint32_t)v;
-}
-
 struct Group {
     uint8_t *p;      // first byte of the group
     int pixels;      // 1..4
@@ -158,7 +150,8 @@ extern "C" int wv_colour_jitter(uint8_t *img, const wv_colour_ops *ops, int n, i
     if (n == 0) return WV_OK;
     WV_REQUIRE(img && ops, "wv_colour_jitter: img / ops is NULL");
     WV_REQUIRE(max_h >= 1 && max_w >= 1, "wv_colour_jitter: max_h = %d, max_w = %d (both >= 1)", max_h, max_w);
-    if (max_h > kMaxSide || max_w > kMaxSide) WV_FAIL(WV_ENOTSUP, "wv_colour_jitter: max_h = %d, max_w = %d (limit %d)", max_h, max_w, kMaxSide);
+    if (max_h > wv::kMaxImageSide || max_w > wv::kMaxImageSide)
+        WV_FAIL(WV_ENOTSUP, "wv_colour_jitter: max_h = %d, max_w = %d (limit %d)", max_h, max_w, wv::kMaxImageSide);
     const size_t need = wv_colour_jitter_workspace_bytes(n);
     WV_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "wv_colour_jitter: workspace is NULL or not 8-byte aligned");
     if (workspace_bytes < need) WV_FAIL(WV_ENOMEM, "wv_colour_jitter: workspace_bytes = %zu, need %zu", workspace_bytes, need);

@@ -15,23 +15,16 @@
 #pragma once
 #include <stdint.h>
 
-#include "../../include/wvhash.h"
-
-#ifdef __HIP__
-#define WV_COL_HD __host__ __device__ inline
-#else
-#define WV_COL_HD inline
-#endif
+#include "twin.hpp"
 
 namespace wv {
 namespace col {
 
-constexpr int kMaxSide = 16384;
 constexpr int kMaxOps = 3;
 
-WV_COL_HD int luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
+WV_HD int luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
 
-WV_COL_HD int blend8(int d, int x, float f)
+WV_HD int blend8(int d, int x, float f)
 {
 #ifdef __clang__
 #pragma clang fp contract(off)
@@ -42,13 +35,13 @@ WV_COL_HD int blend8(int d, int x, float f)
     return (int)t;
 }
 
-WV_COL_HD int mean_from_sum(uint64_t sum, uint64_t count) { return (int)((2 * sum + count) / (2 * count)); }
+WV_HD int mean_from_sum(uint64_t sum, uint64_t count) { return (int)((2 * sum + count) / (2 * count)); }
 
 // n_ops of a descriptor as the loops use it: a value outside 0..3 (the check refuses it) never indexes past kind[] / factor[]
-WV_COL_HD int op_count(const wv_colour_ops &o) { return o.n_ops < 0 ? 0 : (o.n_ops > kMaxOps ? kMaxOps : o.n_ops); }
+WV_HD int op_count(const wv_colour_ops &o) { return o.n_ops < 0 ? 0 : (o.n_ops > kMaxOps ? kMaxOps : o.n_ops); }
 
 // index of the contrast operation in the chain, -1 when it has none
-WV_COL_HD int contrast_index(const wv_colour_ops &o)
+WV_HD int contrast_index(const wv_colour_ops &o)
 {
     const int n = op_count(o);
     for (int i = 0; i < n; ++i)
@@ -57,7 +50,7 @@ WV_COL_HD int contrast_index(const wv_colour_ops &o)
 }
 
 // operations [first, last) of the chain on one pixel; m = the contrast mean (unused when the range holds no contrast)
-WV_COL_HD void run_ops(const wv_colour_ops &o, int first, int last, int m, int *r, int *g, int *b)
+WV_HD void run_ops(const wv_colour_ops &o, int first, int last, int m, int *r, int *g, int *b)
 {
     for (int i = first; i < last; ++i) {
         const float f = o.factor[i];

@@ -10,26 +10,13 @@
 #include <stdio.h>
 #include <stdarg.h>
 
-#include "../../include/wvhash.h"
+#include "twin.hpp"
 
 namespace wv {
-
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 
 // Value of a kernel-selection / tuning switch: always NULL in libwvhash.so (tune_release.cpp), the environment variable of
 // that name in libwvhash_diag.so (tune_diag.cpp).
 const char *tune(const char *name);
-
-#define WV_FAIL(code, ...)          \
-    do {                            \
-        ::wv::set_error(__VA_ARGS__); \
-        return (code);              \
-    } while (0)
-
-#define WV_REQUIRE(cond, ...)                      \
-    do {                                           \
-        if (!(cond)) WV_FAIL(WV_EINVAL, __VA_ARGS__); \
-    } while (0)
 
 // Checks the launch itself (asynchronous execution errors surface at the caller's next sync).
 #define WV_CHECK_LAUNCH(what)                                                        \
@@ -50,6 +37,16 @@ constexpr int kMaxLdsBytes = 160 * 1024;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
+
+// A byte behind an empty asm, for code that packs clamped bytes with `lo | hi << 8`: hipcc fuses two adjacent clamps that are
+// packed that way into one v_ashr_pk_u8_i32, takes the upper 16 bits of its result for zero and ORs the other two bytes onto
+// it -- on gfx950 those bits keep what the register held before (seen in image_size.hip as stray bits in bytes 2 and 3 of
+// every dword of rows with an even tap count).  Through the asm every byte is shifted, clamped and converted on its own.
+__device__ __forceinline__ uint32_t own_byte(int v)
+{
+    asm volatile("" : "+v"(v));
+    return (uint32_t)v;
+}
 
 // count of set bits of `mask` strictly below this lane
 __device__ __forceinline__ int mbcnt(uint64_t mask)

@@ -9,37 +9,28 @@
 
 #include "colour.hpp"
 
-namespace wv {
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-
-#define CJ_FAIL(code, ...)            \
-    do {                              \
-        ::wv::set_error(__VA_ARGS__); \
-        return (code);                \
-    } while (0)
-
 namespace {
 
 using namespace wv::col;
+using wv::kMaxImageSide;
 
 int check_image(const wv_colour_ops &o, int i)
 {
-    if (o.h < 1) CJ_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: h = %d (must be >= 1)", i, o.h);
-    if (o.w < 1) CJ_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: w = %d (must be >= 1)", i, o.w);
-    if (o.h > kMaxSide) CJ_FAIL(WV_ENOTSUP, "wv_colour_jitter: image %d: h = %d (limit %d)", i, o.h, kMaxSide);
-    if (o.w > kMaxSide) CJ_FAIL(WV_ENOTSUP, "wv_colour_jitter: image %d: w = %d (limit %d)", i, o.w, kMaxSide);
+    if (o.h < 1) WV_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: h = %d (must be >= 1)", i, o.h);
+    if (o.w < 1) WV_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: w = %d (must be >= 1)", i, o.w);
+    if (o.h > kMaxImageSide) WV_FAIL(WV_ENOTSUP, "wv_colour_jitter: image %d: h = %d (limit %d)", i, o.h, kMaxImageSide);
+    if (o.w > kMaxImageSide) WV_FAIL(WV_ENOTSUP, "wv_colour_jitter: image %d: w = %d (limit %d)", i, o.w, kMaxImageSide);
     if ((int64_t)o.row_bytes < 3 * (int64_t)o.w)
-        CJ_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: row_bytes = %d is shorter than a row of w = %d pixels", i, o.row_bytes, o.w);
-    if (o.offset < 0) CJ_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: offset = %lld is negative", i, (long long)o.offset);
-    if (o.n_ops < 0 || o.n_ops > kMaxOps) CJ_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: n_ops = %d (0 .. %d)", i, o.n_ops, kMaxOps);
+        WV_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: row_bytes = %d is shorter than a row of w = %d pixels", i, o.row_bytes, o.w);
+    if (o.offset < 0) WV_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: offset = %lld is negative", i, (long long)o.offset);
+    if (o.n_ops < 0 || o.n_ops > kMaxOps) WV_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: n_ops = %d (0 .. %d)", i, o.n_ops, kMaxOps);
     for (int k = 0; k < o.n_ops; ++k) {
         if (o.kind[k] != WV_COLOUR_BRIGHTNESS && o.kind[k] != WV_COLOUR_CONTRAST && o.kind[k] != WV_COLOUR_SATURATION)
-            CJ_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: kind[%d] = %d (0 = brightness, 1 = contrast, 2 = saturation)", i, k, o.kind[k]);
+            WV_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: kind[%d] = %d (0 = brightness, 1 = contrast, 2 = saturation)", i, k, o.kind[k]);
         for (int j = 0; j < k; ++j)
-            if (o.kind[j] == o.kind[k]) CJ_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: kind[%d] = %d is listed twice (kind[%d])", i, k, o.kind[k], j);
+            if (o.kind[j] == o.kind[k]) WV_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: kind[%d] = %d is listed twice (kind[%d])", i, k, o.kind[k], j);
         if (!isfinite(o.factor[k]) || o.factor[k] < 0.0f)
-            CJ_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: factor[%d] = %g (finite and >= 0)", i, k, (double)o.factor[k]);
+            WV_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: factor[%d] = %g (finite and >= 0)", i, k, (double)o.factor[k]);
     }
     return WV_OK;
 }
@@ -82,23 +73,17 @@ void run_image(uint8_t *img, const wv_colour_ops &o)
 
 extern "C" int wv_colour_jitter_check(const wv_colour_ops *ops, int n)
 {
-    if (n < 0) CJ_FAIL(WV_EINVAL, "wv_colour_jitter: n = %d is negative", n);
+    if (n < 0) WV_FAIL(WV_EINVAL, "wv_colour_jitter: n = %d is negative", n);
     if (n == 0) return WV_OK;
-    if (!ops) CJ_FAIL(WV_EINVAL, "wv_colour_jitter: ops is NULL");
+    if (!ops) WV_FAIL(WV_EINVAL, "wv_colour_jitter: ops is NULL");
     for (int i = 0; i < n; ++i) {
         const int rc = check_image(ops[i], i);
         if (rc != WV_OK) return rc;
     }
-    // the n images must not overlap: sorted by first byte, each must end before the next begins
-    std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return ops[a].offset < ops[b].offset; });
-    for (int j = 1; j < n; ++j) {
-        const int a = order[j - 1], b = order[j];
-        if (image_end(ops[a]) > ops[b].offset)
-            CJ_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: offset = %lld lies inside image %d (ends at %lld)", b, (long long)ops[b].offset, a,
-                    (long long)image_end(ops[a]));
-    }
+    int a, b;                                                   // the n images must not overlap
+    if (wv::ranges_overlap(n, [&](int i) { return ops[i].offset; }, [&](int i) { return image_end(ops[i]); }, &a, &b))
+        WV_FAIL(WV_EINVAL, "wv_colour_jitter: image %d: offset = %lld lies inside image %d (ends at %lld)", b, (long long)ops[b].offset, a,
+                (long long)image_end(ops[a]));
     return WV_OK;
 }
 
@@ -107,7 +92,7 @@ extern "C" int wv_colour_jitter_cpu(uint8_t *img, const wv_colour_ops *ops, int 
     const int rc = wv_colour_jitter_check(ops, n);
     if (rc != WV_OK) return rc;
     if (n == 0) return WV_OK;
-    if (!img) CJ_FAIL(WV_EINVAL, "wv_colour_jitter_cpu: img is NULL");
+    if (!img) WV_FAIL(WV_EINVAL, "wv_colour_jitter_cpu: img is NULL");
     for (int i = 0; i < n; ++i) run_image(img, ops[i]);
     return WV_OK;
 }

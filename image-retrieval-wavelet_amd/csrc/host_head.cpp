@@ -22,22 +22,8 @@
 #include <immintrin.h>
 #endif
 
-#include "../../include/wvhash.h"
+#include "twin.hpp"
 #include "head_args.hpp"
-
-namespace wv {
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-
-#define HH_FAIL(code, ...)            \
-    do {                              \
-        ::wv::set_error(__VA_ARGS__); \
-        return (code);                \
-    } while (0)
-#define HH_REQUIRE(cond, ...)                         \
-    do {                                              \
-        if (!(cond)) HH_FAIL(WV_EINVAL, __VA_ARGS__); \
-    } while (0)
 
 namespace {
 
@@ -125,11 +111,11 @@ std::vector<float> bf16_copy(const float *x, size_t n)
 // linear(), so nothing else changes.  what: the entry point's name in error texts.
 int pool_cpu(const wv_head_params *p, const void *feats_any, int feat_dtype, int B, float *out, bool bf16, const char *what)
 {
-    HH_REQUIRE(p && feats_any && out, "%s: null buffer", what);
+    WV_REQUIRE(p && feats_any && out, "%s: null buffer", what);
     const int E = p->embed_dim, H = p->num_heads, Nq = p->num_queries, S = p->num_tokens;
-    HH_REQUIRE(E >= 8 && E % 8 == 0 && H >= 1 && E % H == 0 && Nq >= 1 && S >= 1 && S <= 64 && B >= 0,
+    WV_REQUIRE(E >= 8 && E % 8 == 0 && H >= 1 && E % H == 0 && Nq >= 1 && S >= 1 && S <= 64 && B >= 0,
                "%s: bad configuration E=%d heads=%d Nq=%d S=%d B=%d", what, E, H, Nq, S, B);
-    HH_REQUIRE(p->q_eff && p->in_proj_w && p->in_proj_b && p->attn_out_w && p->attn_out_b && p->norm1_w && p->norm1_b &&
+    WV_REQUIRE(p->q_eff && p->in_proj_w && p->in_proj_b && p->attn_out_w && p->attn_out_b && p->norm1_w && p->norm1_b &&
                    p->mlp0_w && p->mlp0_b && p->mlp2_w && p->mlp2_b && p->out_w && p->out_b && p->norm2_w && p->norm2_b,
                "%s: null parameter", what);
     if (B == 0) return WV_OK;
@@ -283,12 +269,12 @@ extern "C" int wv_band_attn_maps_cpu(const wv_head_params *p, const float *feats
                                      float *scores, float *attn_out)
 {
     char why[256];
-    if (const int rc = ::wv::head_attn_args_refusal(p, B, "band_attn_maps_cpu", why, sizeof(why))) HH_FAIL(rc, "%s", why);
-    HH_REQUIRE(probs || probs_mean || scores || attn_out, "band_attn_maps_cpu: no output asked for");
-    HH_REQUIRE(layout == WV_TOKENS_SBE || layout == WV_TOKENS_BSE, "band_attn_maps_cpu: layout=%d (WV_TOKENS_SBE or WV_TOKENS_BSE)",
+    if (const int rc = ::wv::head_attn_args_refusal(p, B, "band_attn_maps_cpu", why, sizeof(why))) WV_FAIL(rc, "%s", why);
+    WV_REQUIRE(probs || probs_mean || scores || attn_out, "band_attn_maps_cpu: no output asked for");
+    WV_REQUIRE(layout == WV_TOKENS_SBE || layout == WV_TOKENS_BSE, "band_attn_maps_cpu: layout=%d (WV_TOKENS_SBE or WV_TOKENS_BSE)",
                layout);
     if (B == 0) return WV_OK;
-    HH_REQUIRE(feats, "band_attn_maps_cpu: null buffer");
+    WV_REQUIRE(feats, "band_attn_maps_cpu: null buffer");
     return maps_cpu(p, feats, layout, B, probs, probs_mean, scores, attn_out);
 }
 
@@ -299,9 +285,9 @@ extern "C" int wv_band_attn_pool_cpu(const wv_head_params *p, const float *feats
 
 extern "C" int wv_band_attn_pool_bf16_cpu(const wv_head_params *p, const void *feats, int feat_dtype, int B, float *out)
 {
-    HH_REQUIRE(feat_dtype == WV_DT_F32 || feat_dtype == WV_DT_BF16, "band_attn_pool_bf16_cpu: feat_dtype=%d (WV_DT_F32 or WV_DT_BF16)",
+    WV_REQUIRE(feat_dtype == WV_DT_F32 || feat_dtype == WV_DT_BF16, "band_attn_pool_bf16_cpu: feat_dtype=%d (WV_DT_F32 or WV_DT_BF16)",
                feat_dtype);
-    HH_REQUIRE(!p || p->embed_dim % 32 == 0, "band_attn_pool_bf16_cpu: embed_dim=%d must be a multiple of 32", p->embed_dim);
+    WV_REQUIRE(!p || p->embed_dim % 32 == 0, "band_attn_pool_bf16_cpu: embed_dim=%d must be a multiple of 32", p->embed_dim);
     return pool_cpu(p, feats, feat_dtype, B, out, true, "band_attn_pool_bf16_cpu");
 }
 
@@ -309,9 +295,9 @@ extern "C" int wv_hash_tail_cpu(const float *fused, int B, int E, const float *h
                                 const float *bn_b, const float *bn_mean, const float *bn_var, float bn_eps, int nbits,
                                 float *logits_out, float *codes_out, uint64_t *packed_out)
 {
-    HH_REQUIRE(fused && hash_w, "hash_tail_cpu: null buffer");
-    HH_REQUIRE(B >= 0 && E >= 8 && E % 8 == 0 && nbits >= 1, "hash_tail_cpu: bad shape B=%d E=%d nbits=%d", B, E, nbits);
-    HH_REQUIRE(!bn_w || (bn_b && bn_mean && bn_var), "hash_tail_cpu: incomplete BatchNorm parameters");
+    WV_REQUIRE(fused && hash_w, "hash_tail_cpu: null buffer");
+    WV_REQUIRE(B >= 0 && E >= 8 && E % 8 == 0 && nbits >= 1, "hash_tail_cpu: bad shape B=%d E=%d nbits=%d", B, E, nbits);
+    WV_REQUIRE(!bn_w || (bn_b && bn_mean && bn_var), "hash_tail_cpu: incomplete BatchNorm parameters");
     const int words = (nbits + 63) / 64;
     std::vector<float> logit((size_t)nbits);
     for (int b = 0; b < B; ++b) {

@@ -10,26 +10,18 @@
 
 #include "image_size.hpp"
 
-namespace wv {
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-
-#define IS_FAIL(code, ...)            \
-    do {                              \
-        ::wv::set_error(__VA_ARGS__); \
-        return (code);                \
-    } while (0)
-
 namespace {
 
 using namespace wv::isz;
+using wv::kMaxImageSide;
 
 int check_stage(const wv_size_stage &s, int i)
 {
 #define IS_SIDE(f)                                                                                           \
     do {                                                                                                     \
-        if (s.f < 1) IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: " #f " = %d (must be >= 1)", i, (int)s.f);  \
-        if (s.f > kMaxSide) IS_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: " #f " = %d (limit %d)", i, (int)s.f, kMaxSide); \
+        if (s.f < 1) WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: " #f " = %d (must be >= 1)", i, (int)s.f);  \
+        if (s.f > kMaxImageSide)                                                                             \
+            WV_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: " #f " = %d (limit %d)", i, (int)s.f, kMaxImageSide); \
     } while (0)
     IS_SIDE(src_h);
     IS_SIDE(src_w);
@@ -41,26 +33,28 @@ int check_stage(const wv_size_stage &s, int i)
     IS_SIDE(out_w);
 #undef IS_SIDE
     if (s.crop_y < 0 || s.crop_y > s.src_h - s.crop_h)
-        IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: crop_y = %d with crop_h = %d leaves src_h = %d", i, s.crop_y, s.crop_h, s.src_h);
+        WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: crop_y = %d with crop_h = %d leaves src_h = %d", i, s.crop_y, s.crop_h, s.src_h);
     if (s.crop_x < 0 || s.crop_x > s.src_w - s.crop_w)
-        IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: crop_x = %d with crop_w = %d leaves src_w = %d", i, s.crop_x, s.crop_w, s.src_w);
+        WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: crop_x = %d with crop_w = %d leaves src_w = %d", i, s.crop_x, s.crop_w, s.src_w);
     if (s.filter != WV_RESAMPLE_BILINEAR && s.filter != WV_RESAMPLE_BICUBIC)
-        IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: filter = %d (2 = bilinear, 3 = bicubic)", i, s.filter);
-    if (s.flip != 0 && s.flip != 1) IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: flip = %d (0 or 1)", i, s.flip);
+        WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: filter = %d (2 = bilinear, 3 = bicubic)", i, s.filter);
+    if (s.flip != 0 && s.flip != 1) WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: flip = %d (0 or 1)", i, s.flip);
     if ((int64_t)s.src_row_bytes < 3 * (int64_t)s.src_w)
-        IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: src_row_bytes = %d is shorter than a row of src_w = %d pixels", i, s.src_row_bytes, s.src_w);
+        WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: src_row_bytes = %d is shorter than a row of src_w = %d pixels", i, s.src_row_bytes, s.src_w);
     if ((int64_t)s.dst_row_bytes < 3 * (int64_t)s.out_w)
-        IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: dst_row_bytes = %d is shorter than a row of out_w = %d pixels", i, s.dst_row_bytes, s.out_w);
-    if (s.src_offset < 0) IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: src_offset = %lld is negative", i, (long long)s.src_offset);
-    if (s.dst_offset < 0) IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: dst_offset = %lld is negative", i, (long long)s.dst_offset);
-    if (s.win_y < -kMaxSide || s.win_y > kMaxSide) IS_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: win_y = %d (limit +-%d)", i, s.win_y, kMaxSide);
-    if (s.win_x < -kMaxSide || s.win_x > kMaxSide) IS_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: win_x = %d (limit +-%d)", i, s.win_x, kMaxSide);
+        WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: dst_row_bytes = %d is shorter than a row of out_w = %d pixels", i, s.dst_row_bytes, s.out_w);
+    if (s.src_offset < 0) WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: src_offset = %lld is negative", i, (long long)s.src_offset);
+    if (s.dst_offset < 0) WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: dst_offset = %lld is negative", i, (long long)s.dst_offset);
+    if (s.win_y < -kMaxImageSide || s.win_y > kMaxImageSide)
+        WV_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: win_y = %d (limit +-%d)", i, s.win_y, kMaxImageSide);
+    if (s.win_x < -kMaxImageSide || s.win_x > kMaxImageSide)
+        WV_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: win_x = %d (limit +-%d)", i, s.win_x, kMaxImageSide);
     // the limit on the scale bounds the taps of a coefficient row (kMaxKsize); an axis of no more samples than that is inside
     // it at any scale: its rows cannot have more taps than it has samples
     if ((int64_t)s.crop_h > (int64_t)kMaxDownscale * s.res_h && s.crop_h > kMaxKsize)
-        IS_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: crop_h = %d to res_h = %d is a down-scale above %d", i, s.crop_h, s.res_h, kMaxDownscale);
+        WV_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: crop_h = %d to res_h = %d is a down-scale above %d", i, s.crop_h, s.res_h, kMaxDownscale);
     if ((int64_t)s.crop_w > (int64_t)kMaxDownscale * s.res_w && s.crop_w > kMaxKsize)
-        IS_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: crop_w = %d to res_w = %d is a down-scale above %d", i, s.crop_w, s.res_w, kMaxDownscale);
+        WV_FAIL(WV_ENOTSUP, "wv_image_size: stage %d: crop_w = %d to res_w = %d is a down-scale above %d", i, s.crop_w, s.res_w, kMaxDownscale);
     return WV_OK;
 }
 
@@ -134,23 +128,17 @@ void run_stage(const uint8_t *src, uint8_t *dst, const wv_size_stage &s)
 
 extern "C" int wv_image_size_check(const wv_size_stage *stages, int n)
 {
-    if (n < 0) IS_FAIL(WV_EINVAL, "wv_image_size: n = %d is negative", n);
+    if (n < 0) WV_FAIL(WV_EINVAL, "wv_image_size: n = %d is negative", n);
     if (n == 0) return WV_OK;
-    if (!stages) IS_FAIL(WV_EINVAL, "wv_image_size: stages is NULL");
+    if (!stages) WV_FAIL(WV_EINVAL, "wv_image_size: stages is NULL");
     for (int i = 0; i < n; ++i) {
         const int rc = check_stage(stages[i], i);
         if (rc != WV_OK) return rc;
     }
-    // the destinations of the n images must not overlap: sorted by first byte, each must end before the next begins
-    std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return stages[a].dst_offset < stages[b].dst_offset; });
-    for (int j = 1; j < n; ++j) {
-        const int a = order[j - 1], b = order[j];
-        if (dst_end(stages[a]) > stages[b].dst_offset)
-            IS_FAIL(WV_EINVAL, "wv_image_size: stage %d: dst_offset = %lld lies inside the destination of stage %d (ends at %lld)", b,
-                    (long long)stages[b].dst_offset, a, (long long)dst_end(stages[a]));
-    }
+    int a, b;                                                   // the destinations of the n images must not overlap
+    if (wv::ranges_overlap(n, [&](int i) { return stages[i].dst_offset; }, [&](int i) { return dst_end(stages[i]); }, &a, &b))
+        WV_FAIL(WV_EINVAL, "wv_image_size: stage %d: dst_offset = %lld lies inside the destination of stage %d (ends at %lld)", b,
+                (long long)stages[b].dst_offset, a, (long long)dst_end(stages[a]));
     return WV_OK;
 }
 
@@ -159,7 +147,7 @@ extern "C" int wv_image_size_cpu(const uint8_t *src, uint8_t *dst, const wv_size
     const int rc = wv_image_size_check(stages, n);
     if (rc != WV_OK) return rc;
     if (n == 0) return WV_OK;
-    if (!src || !dst) IS_FAIL(WV_EINVAL, "wv_image_size_cpu: src / dst is NULL");
+    if (!src || !dst) WV_FAIL(WV_EINVAL, "wv_image_size_cpu: src / dst is NULL");
     for (int i = 0; i < n; ++i) run_stage(src, dst, stages[i]);
     return WV_OK;
 }

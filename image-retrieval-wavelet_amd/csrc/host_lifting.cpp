@@ -10,19 +10,10 @@
 
 #include "lifting.hpp"
 
-namespace wv {
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-
-#define LF_FAIL(code, ...)            \
-    do {                              \
-        ::wv::set_error(__VA_ARGS__); \
-        return (code);                \
-    } while (0)
-
 namespace {
 
 using namespace wv::lift;
+using wv::kMaxImageSide;
 
 // one level of one plane: cur [h][w] (zero beyond, up to the padded size) -> ll, lh, hl, hh [nh][nw]; a NULL band is not formed
 template <int BASIS>
@@ -65,17 +56,17 @@ namespace lift {
 
 int convert_args(const char *who, int in_dtype, int C, int to_tensor, const float *mean, const float *std, Convert *cv)
 {
-    if (to_tensor != 0 && to_tensor != 1) LF_FAIL(WV_EINVAL, "%s: to_tensor = %d (0 or 1)", who, to_tensor);
-    if ((mean == nullptr) != (std == nullptr)) LF_FAIL(WV_EINVAL, "%s: mean and std come together (both NULL = no Normalize)", who);
-    if (to_tensor && in_dtype != WV_DT_U8) LF_FAIL(WV_EINVAL, "%s: to_tensor = 1 scales 8-bit images, in_dtype = %d is not WV_DT_U8", who, in_dtype);
+    if (to_tensor != 0 && to_tensor != 1) WV_FAIL(WV_EINVAL, "%s: to_tensor = %d (0 or 1)", who, to_tensor);
+    if ((mean == nullptr) != (std == nullptr)) WV_FAIL(WV_EINVAL, "%s: mean and std come together (both NULL = no Normalize)", who);
+    if (to_tensor && in_dtype != WV_DT_U8) WV_FAIL(WV_EINVAL, "%s: to_tensor = 1 scales 8-bit images, in_dtype = %d is not WV_DT_U8", who, in_dtype);
     if (mean && in_dtype != WV_DT_U8)
-        LF_FAIL(WV_ENOTSUP, "%s: Normalize is folded into the 8-bit conversion table only; normalise float32 input before the call", who);
+        WV_FAIL(WV_ENOTSUP, "%s: Normalize is folded into the 8-bit conversion table only; normalise float32 input before the call", who);
     memset(cv, 0, sizeof(*cv));
     cv->to_tensor = to_tensor;
     cv->norm = mean != nullptr;
     for (int c = 0; mean && c < C && c < kMaxChannels; ++c) {
-        if (!(mean[c] == mean[c]) || !(std[c] == std[c])) LF_FAIL(WV_EINVAL, "%s: mean[%d] / std[%d] is NaN", who, c, c);
-        if (std[c] == 0.0f) LF_FAIL(WV_EINVAL, "%s: std[%d] = 0 leads to division by zero", who, c);
+        if (!(mean[c] == mean[c]) || !(std[c] == std[c])) WV_FAIL(WV_EINVAL, "%s: mean[%d] / std[%d] is NaN", who, c, c);
+        if (std[c] == 0.0f) WV_FAIL(WV_EINVAL, "%s: std[%d] = 0 leads to division by zero", who, c);
         cv->mean[c] = mean[c];
         cv->std[c] = std[c];
     }
@@ -95,21 +86,21 @@ extern "C" int wv_lift_images_tile(int axis) { return axis == 0 ? 2 * kTilePairs
 
 extern "C" int wv_lift_images_check(int in_dtype, int in_layout, int B, int C, int H, int W, int basis, int levels, int ll_only)
 {
-    if (in_dtype != WV_DT_U8 && in_dtype != WV_DT_F32) LF_FAIL(WV_EINVAL, "wv_lift_images: in_dtype = %d (WV_DT_U8 or WV_DT_F32)", in_dtype);
+    if (in_dtype != WV_DT_U8 && in_dtype != WV_DT_F32) WV_FAIL(WV_EINVAL, "wv_lift_images: in_dtype = %d (WV_DT_U8 or WV_DT_F32)", in_dtype);
     if (in_layout != WV_LAYOUT_NCHW && in_layout != WV_LAYOUT_NHWC)
-        LF_FAIL(WV_EINVAL, "wv_lift_images: in_layout = %d (WV_LAYOUT_NCHW or WV_LAYOUT_NHWC)", in_layout);
-    if (B < 0) LF_FAIL(WV_EINVAL, "wv_lift_images: B = %d is negative", B);
-    if (C < 1) LF_FAIL(WV_EINVAL, "wv_lift_images: C = %d (must be >= 1)", C);
-    if (H < 1) LF_FAIL(WV_EINVAL, "wv_lift_images: H = %d (must be >= 1)", H);
-    if (W < 1) LF_FAIL(WV_EINVAL, "wv_lift_images: W = %d (must be >= 1)", W);
-    if (basis != kHaar && basis != kCdf97) LF_FAIL(WV_EINVAL, "wv_lift_images: basis = %d (0 = haar, 1 = cdf97)", basis);
-    if (levels < 0) LF_FAIL(WV_EINVAL, "wv_lift_images: levels = %d is negative", levels);
-    if (ll_only != 0 && ll_only != 1) LF_FAIL(WV_EINVAL, "wv_lift_images: ll_only = %d (0 or 1)", ll_only);
-    if (C > kMaxChannels) LF_FAIL(WV_ENOTSUP, "wv_lift_images: C = %d (limit %d)", C, kMaxChannels);
-    if (H > kMaxSide) LF_FAIL(WV_ENOTSUP, "wv_lift_images: H = %d (limit %d)", H, kMaxSide);
-    if (W > kMaxSide) LF_FAIL(WV_ENOTSUP, "wv_lift_images: W = %d (limit %d)", W, kMaxSide);
-    if (levels > kMaxLevels) LF_FAIL(WV_ENOTSUP, "wv_lift_images: levels = %d (limit %d)", levels, kMaxLevels);
-    if ((int64_t)B * C > INT32_MAX) LF_FAIL(WV_ENOTSUP, "wv_lift_images: B * C = %lld planes (limit 2^31 - 1)", (long long)B * C);
+        WV_FAIL(WV_EINVAL, "wv_lift_images: in_layout = %d (WV_LAYOUT_NCHW or WV_LAYOUT_NHWC)", in_layout);
+    if (B < 0) WV_FAIL(WV_EINVAL, "wv_lift_images: B = %d is negative", B);
+    if (C < 1) WV_FAIL(WV_EINVAL, "wv_lift_images: C = %d (must be >= 1)", C);
+    if (H < 1) WV_FAIL(WV_EINVAL, "wv_lift_images: H = %d (must be >= 1)", H);
+    if (W < 1) WV_FAIL(WV_EINVAL, "wv_lift_images: W = %d (must be >= 1)", W);
+    if (basis != kHaar && basis != kCdf97) WV_FAIL(WV_EINVAL, "wv_lift_images: basis = %d (0 = haar, 1 = cdf97)", basis);
+    if (levels < 0) WV_FAIL(WV_EINVAL, "wv_lift_images: levels = %d is negative", levels);
+    if (ll_only != 0 && ll_only != 1) WV_FAIL(WV_EINVAL, "wv_lift_images: ll_only = %d (0 or 1)", ll_only);
+    if (C > kMaxChannels) WV_FAIL(WV_ENOTSUP, "wv_lift_images: C = %d (limit %d)", C, kMaxChannels);
+    if (H > kMaxImageSide) WV_FAIL(WV_ENOTSUP, "wv_lift_images: H = %d (limit %d)", H, kMaxImageSide);
+    if (W > kMaxImageSide) WV_FAIL(WV_ENOTSUP, "wv_lift_images: W = %d (limit %d)", W, kMaxImageSide);
+    if (levels > kMaxLevels) WV_FAIL(WV_ENOTSUP, "wv_lift_images: levels = %d (limit %d)", levels, kMaxLevels);
+    if ((int64_t)B * C > INT32_MAX) WV_FAIL(WV_ENOTSUP, "wv_lift_images: B * C = %lld planes (limit 2^31 - 1)", (long long)B * C);
     return WV_OK;
 }
 
@@ -122,7 +113,7 @@ extern "C" int wv_lift_images_cpu(const void *in, int in_dtype, int in_layout, i
     rc = convert_args("wv_lift_images_cpu", in_dtype, C, to_tensor, mean, std, &cv);
     if (rc != WV_OK) return rc;
     if (B == 0) return WV_OK;
-    if (!in || !out) LF_FAIL(WV_EINVAL, "wv_lift_images_cpu: in / out is NULL");
+    if (!in || !out) WV_FAIL(WV_EINVAL, "wv_lift_images_cpu: in / out is NULL");
 
     std::vector<float> table((size_t)256 * C);
     for (int c = 0; c < C; ++c)

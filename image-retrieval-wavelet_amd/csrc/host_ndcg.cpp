@@ -41,8 +41,8 @@ inline int overlap(const uint64_t *ql, const uint64_t *dl, int lwords)
 // w[p] = 1 / log2(p + 2): the only logarithm and the only division of the metric, made once
 extern "C" int wv_ndcg_weights(double *w, int64_t k)
 {
-    if (!w) WV_NDCG_REFUSE(WV_EINVAL, "ndcg_weights: null buffer");
-    if (k < 0) WV_NDCG_REFUSE(WV_EINVAL, "ndcg_weights: k=%lld", (long long)k);
+    if (!w) WV_FAIL(WV_EINVAL, "ndcg_weights: null buffer");
+    if (k < 0) WV_FAIL(WV_EINVAL, "ndcg_weights: k=%lld", (long long)k);
     for (int64_t p = 0; p < k; ++p) w[p] = 1.0 / log2((double)(p + 2));
     return WV_OK;
 }

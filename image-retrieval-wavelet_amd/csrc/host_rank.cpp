@@ -16,21 +16,7 @@
 
 #include <vector>
 
-#include "../../include/wvhash.h"
-
-namespace wv {
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-
-#define HR_FAIL(code, ...)            \
-    do {                              \
-        ::wv::set_error(__VA_ARGS__); \
-        return (code);                \
-    } while (0)
-#define HR_REQUIRE(cond, ...)                         \
-    do {                                              \
-        if (!(cond)) HR_FAIL(WV_EINVAL, __VA_ARGS__); \
-    } while (0)
+#include "twin.hpp"
 
 namespace {
 
@@ -91,10 +77,10 @@ inline double sum_in_kernel_order(const double (&acc)[256])
 extern "C" int wv_pack_bits_cpu(const float *src, int64_t ld_src, uint64_t *packed, int64_t rows, int nbits, int mode,
                                 int32_t *bad_flag)
 {
-    HR_REQUIRE(src && packed, "pack_bits_cpu: null buffer");
-    HR_REQUIRE(rows >= 0 && nbits >= 1 && ld_src >= nbits, "pack_bits_cpu: bad shape rows=%lld nbits=%d ld=%lld", (long long)rows,
+    WV_REQUIRE(src && packed, "pack_bits_cpu: null buffer");
+    WV_REQUIRE(rows >= 0 && nbits >= 1 && ld_src >= nbits, "pack_bits_cpu: bad shape rows=%lld nbits=%d ld=%lld", (long long)rows,
                nbits, (long long)ld_src);
-    HR_REQUIRE(mode == 0 || mode == 1, "pack_bits_cpu: mode %d (0 = codes, 1 = labels)", mode);
+    WV_REQUIRE(mode == 0 || mode == 1, "pack_bits_cpu: mode %d (0 = codes, 1 = labels)", mode);
     const int words = (nbits + 63) / 64;
     bool bad = false;
     for (int64_t r = 0; r < rows; ++r) {
@@ -116,8 +102,8 @@ extern "C" int wv_pack_bits_cpu(const float *src, int64_t ld_src, uint64_t *pack
 
 extern "C" int wv_bit_counts_cpu(const uint64_t *packed, int64_t rows, int nbits, uint32_t *counts)
 {
-    HR_REQUIRE(packed && counts, "bit_counts_cpu: null buffer");
-    HR_REQUIRE(rows >= 0 && nbits >= 1, "bit_counts_cpu: bad shape");
+    WV_REQUIRE(packed && counts, "bit_counts_cpu: null buffer");
+    WV_REQUIRE(rows >= 0 && nbits >= 1, "bit_counts_cpu: bad shape");
     const int words = (nbits + 63) / 64;
     memset(counts, 0, sizeof(uint32_t) * (size_t)nbits);
     for (int64_t r = 0; r < rows; ++r)
@@ -128,10 +114,10 @@ extern "C" int wv_bit_counts_cpu(const uint64_t *packed, int64_t rows, int nbits
 extern "C" int wv_hamming_dist_cpu(const uint64_t *q, const uint64_t *db, uint8_t *dist, int64_t ld_dist, int Q, int64_t N,
                                    int words)
 {
-    HR_REQUIRE(q && db && dist, "hamming_dist_cpu: null buffer");
-    HR_REQUIRE(Q >= 0 && N >= 0 && ld_dist >= N, "hamming_dist_cpu: bad shape Q=%d N=%lld ld=%lld", Q, (long long)N,
+    WV_REQUIRE(q && db && dist, "hamming_dist_cpu: null buffer");
+    WV_REQUIRE(Q >= 0 && N >= 0 && ld_dist >= N, "hamming_dist_cpu: bad shape Q=%d N=%lld ld=%lld", Q, (long long)N,
                (long long)ld_dist);
-    HR_REQUIRE(words >= 1 && words <= 3, "hamming_dist_cpu: %d words (uint8 distances need <= 255 bits)", words);
+    WV_REQUIRE(words >= 1 && words <= 3, "hamming_dist_cpu: %d words (uint8 distances need <= 255 bits)", words);
     for (int qi = 0; qi < Q; ++qi) dist_row(q + (int64_t)qi * words, db, N, words, dist + (int64_t)qi * ld_dist);
     return WV_OK;
 }
@@ -141,10 +127,10 @@ extern "C" int wv_hamming_dist_cpu(const uint64_t *q, const uint64_t *db, uint8_
 extern "C" int wv_hamming_topk_cpu(const uint64_t *q, const uint64_t *db, int32_t *idx, uint8_t *dist, int Q, int64_t N,
                                    int nbits, int k, int64_t idx_offset)
 {
-    HR_REQUIRE(q && db && idx, "hamming_topk_cpu: null buffer");
-    HR_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_topk_cpu: nbits=%d (supported: 1..128)", nbits);
-    HR_REQUIRE(Q >= 0 && N >= 1 && k >= 1 && k <= N, "hamming_topk_cpu: bad shape Q=%d N=%lld k=%d", Q, (long long)N, k);
-    HR_REQUIRE(N + idx_offset <= 0x7fffffffLL, "hamming_topk_cpu: indices exceed int32");
+    WV_REQUIRE(q && db && idx, "hamming_topk_cpu: null buffer");
+    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_topk_cpu: nbits=%d (supported: 1..128)", nbits);
+    WV_REQUIRE(Q >= 0 && N >= 1 && k >= 1 && k <= N, "hamming_topk_cpu: bad shape Q=%d N=%lld k=%d", Q, (long long)N, k);
+    WV_REQUIRE(N + idx_offset <= 0x7fffffffLL, "hamming_topk_cpu: indices exceed int32");
     const int words = (nbits + 63) / 64, nbins = nbits + 1;
     std::vector<uint8_t> d((size_t)N);
     std::vector<int64_t> start((size_t)nbins + 1);
@@ -171,8 +157,8 @@ extern "C" int wv_hamming_topk_cpu(const uint64_t *q, const uint64_t *db, int32_
 extern "C" int wv_map_at_k_cpu(const int32_t *idx, int64_t ld, int Q, int k, const uint64_t *qlab, const uint64_t *dblab,
                                int lwords, float *ap, int32_t *nrel)
 {
-    HR_REQUIRE(idx && qlab && dblab && ap, "map_at_k_cpu: null buffer");
-    HR_REQUIRE(Q >= 0 && k >= 1 && ld >= k && lwords >= 1, "map_at_k_cpu: bad shape Q=%d k=%d ld=%lld lwords=%d", Q, k,
+    WV_REQUIRE(idx && qlab && dblab && ap, "map_at_k_cpu: null buffer");
+    WV_REQUIRE(Q >= 0 && k >= 1 && ld >= k && lwords >= 1, "map_at_k_cpu: bad shape Q=%d k=%d ld=%lld lwords=%d", Q, k,
                (long long)ld, lwords);
     for (int qi = 0; qi < Q; ++qi) {
         const int32_t *list = idx + (int64_t)qi * ld;
@@ -199,14 +185,14 @@ extern "C" int wv_map_at_k_cpu(const int32_t *idx, int64_t ld, int Q, int k, con
 extern "C" int wv_map_at_ks_cpu(const int32_t *idx, int64_t ld, int Q, const int *ks, int nk, const uint64_t *qlab,
                                 const uint64_t *dblab, int lwords, float *ap, int32_t *nrel)
 {
-    HR_REQUIRE(idx && qlab && dblab && ap, "map_at_ks_cpu: null buffer");
-    HR_REQUIRE(Q >= 0 && ld >= 1 && lwords >= 1, "map_at_ks_cpu: bad shape Q=%d ld=%lld lwords=%d", Q, (long long)ld, lwords);
-    HR_REQUIRE(ks, "map_at_ks_cpu: null cut-off list");
-    HR_REQUIRE(nk >= 1 && nk <= WV_MAX_CUTOFFS, "map_at_ks_cpu: %d cut-offs (supported: 1..%d)", nk, WV_MAX_CUTOFFS);
-    HR_REQUIRE(ks[0] >= 1, "map_at_ks_cpu: cut-off %d must be >= 1", ks[0]);
+    WV_REQUIRE(idx && qlab && dblab && ap, "map_at_ks_cpu: null buffer");
+    WV_REQUIRE(Q >= 0 && ld >= 1 && lwords >= 1, "map_at_ks_cpu: bad shape Q=%d ld=%lld lwords=%d", Q, (long long)ld, lwords);
+    WV_REQUIRE(ks, "map_at_ks_cpu: null cut-off list");
+    WV_REQUIRE(nk >= 1 && nk <= WV_MAX_CUTOFFS, "map_at_ks_cpu: %d cut-offs (supported: 1..%d)", nk, WV_MAX_CUTOFFS);
+    WV_REQUIRE(ks[0] >= 1, "map_at_ks_cpu: cut-off %d must be >= 1", ks[0]);
     for (int i = 1; i < nk; ++i)
-        HR_REQUIRE(ks[i] > ks[i - 1], "map_at_ks_cpu: cut-offs must be strictly ascending (ks[%d]=%d after %d)", i, ks[i], ks[i - 1]);
-    HR_REQUIRE(ks[nk - 1] <= ld, "map_at_ks_cpu: largest cut-off %d must be <= ld=%lld", ks[nk - 1], (long long)ld);
+        WV_REQUIRE(ks[i] > ks[i - 1], "map_at_ks_cpu: cut-offs must be strictly ascending (ks[%d]=%d after %d)", i, ks[i], ks[i - 1]);
+    WV_REQUIRE(ks[nk - 1] <= ld, "map_at_ks_cpu: largest cut-off %d must be <= ld=%lld", ks[nk - 1], (long long)ld);
     for (int qi = 0; qi < Q; ++qi) {
         const int32_t *list = idx + (int64_t)qi * ld;
         const uint64_t *ql = qlab + (int64_t)qi * lwords;
@@ -234,8 +220,8 @@ extern "C" int wv_map_at_ks_cpu(const int32_t *idx, int64_t ld, int Q, const int
 extern "C" int wv_hit_prefix_cpu(const int32_t *idx, int Q, int k, const uint64_t *qlab, const uint64_t *dblab, int lwords,
                                  uint32_t *hits)
 {
-    HR_REQUIRE(idx && qlab && dblab && hits, "hit_prefix_cpu: null buffer");
-    HR_REQUIRE(Q >= 0 && k >= 1 && lwords >= 1, "hit_prefix_cpu: bad shape Q=%d k=%d lwords=%d", Q, k, lwords);
+    WV_REQUIRE(idx && qlab && dblab && hits, "hit_prefix_cpu: null buffer");
+    WV_REQUIRE(Q >= 0 && k >= 1 && lwords >= 1, "hit_prefix_cpu: bad shape Q=%d k=%d lwords=%d", Q, k, lwords);
     for (int qi = 0; qi < Q; ++qi) {
         const int32_t *list = idx + (int64_t)qi * k;
         const uint64_t *ql = qlab + (int64_t)qi * lwords;
@@ -254,10 +240,10 @@ extern "C" int wv_hit_prefix_cpu(const int32_t *idx, int Q, int k, const uint64_
 extern "C" int wv_hamming_radius_hist_cpu(const uint64_t *q, const uint64_t *db, const uint64_t *qlab, const uint64_t *dblab, int lwords,
                                           int Q, int64_t N, int nbits, uint32_t *cum, uint32_t *cumrel)
 {
-    HR_REQUIRE(q && db && qlab && dblab && cum && cumrel, "hamming_radius_hist_cpu: null buffer");
-    HR_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_radius_hist_cpu: nbits=%d (supported: 1..128)", nbits);
-    HR_REQUIRE(lwords == 1 || lwords == 2, "hamming_radius_hist_cpu: lwords=%d (supported: 1, 2)", lwords);
-    HR_REQUIRE(Q >= 0 && N >= 0 && N <= 0xffffffffLL, "hamming_radius_hist_cpu: bad shape Q=%d N=%lld", Q, (long long)N);
+    WV_REQUIRE(q && db && qlab && dblab && cum && cumrel, "hamming_radius_hist_cpu: null buffer");
+    WV_REQUIRE(nbits >= 1 && nbits <= 128, "hamming_radius_hist_cpu: nbits=%d (supported: 1..128)", nbits);
+    WV_REQUIRE(lwords == 1 || lwords == 2, "hamming_radius_hist_cpu: lwords=%d (supported: 1, 2)", lwords);
+    WV_REQUIRE(Q >= 0 && N >= 0 && N <= 0xffffffffLL, "hamming_radius_hist_cpu: bad shape Q=%d N=%lld", Q, (long long)N);
     const int words = (nbits + 63) / 64, ld = nbits + 2;
     std::vector<uint8_t> d((size_t)N);
     for (int qi = 0; qi < Q; ++qi) {

@@ -19,21 +19,7 @@
 
 #include <vector>
 
-#include "../../include/wvhash.h"
-
-namespace wv {
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-}
-
-#define HT_FAIL(code, ...)            \
-    do {                              \
-        ::wv::set_error(__VA_ARGS__); \
-        return (code);                \
-    } while (0)
-#define HT_REQUIRE(cond, ...)                         \
-    do {                                              \
-        if (!(cond)) HT_FAIL(WV_EINVAL, __VA_ARGS__); \
-    } while (0)
+#include "twin.hpp"
 
 namespace {
 
@@ -258,10 +244,10 @@ void dwt_axis(const float *src, float *dlo, float *dhi, int h, int w, int axis, 
 int check_common(const void *in, const void *out, int B, int C, int H, int W, int in_dtype, int in_layout,
                  const char *what)
 {
-    HT_REQUIRE(in && out, "%s: null buffer", what);
-    HT_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "%s: bad shape B=%d C=%d H=%d W=%d", what, B, C, H, W);
-    HT_REQUIRE(in_dtype == WV_DT_U8 || in_dtype == WV_DT_F32, "%s: input dtype %d", what, in_dtype);
-    HT_REQUIRE(in_layout == WV_LAYOUT_NCHW || in_layout == WV_LAYOUT_NHWC, "%s: bad layout %d", what, in_layout);
+    WV_REQUIRE(in && out, "%s: null buffer", what);
+    WV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "%s: bad shape B=%d C=%d H=%d W=%d", what, B, C, H, W);
+    WV_REQUIRE(in_dtype == WV_DT_U8 || in_dtype == WV_DT_F32, "%s: input dtype %d", what, in_dtype);
+    WV_REQUIRE(in_layout == WV_LAYOUT_NCHW || in_layout == WV_LAYOUT_NHWC, "%s: bad layout %d", what, in_layout);
     return WV_OK;
 }
 
@@ -271,9 +257,9 @@ extern "C" int wv_swt2d_forward_cpu(const void *in, int in_dtype, int in_layout,
                                     int W, int level, const float *dec_lo, const float *dec_hi, int flen)
 {
     if (int rc = check_common(in, out, B, C, H, W, in_dtype, in_layout, "swt (host)")) return rc;
-    HT_REQUIRE(dec_lo && dec_hi && flen >= 1 && flen <= 32, "swt (host): 1..32 filter taps, got %d", flen);
-    HT_REQUIRE(level >= 1 && level <= 12, "swt (host): level %d out of range", level);
-    HT_REQUIRE((H % (1 << level)) == 0 && (W % (1 << level)) == 0,
+    WV_REQUIRE(dec_lo && dec_hi && flen >= 1 && flen <= 32, "swt (host): 1..32 filter taps, got %d", flen);
+    WV_REQUIRE(level >= 1 && level <= 12, "swt (host): level %d out of range", level);
+    WV_REQUIRE((H % (1 << level)) == 0 && (W % (1 << level)) == 0,
                "swt: H=%d, W=%d must be multiples of 2^level=%d (PyWavelets raises ValueError here)", H, W, 1 << level);
     Taps t{};
     t.L = flen;
@@ -282,7 +268,7 @@ extern "C" int wv_swt2d_forward_cpu(const void *in, int in_dtype, int in_layout,
         if (cpu_has_fma()) swt_all_fma(in, in_dtype, in_layout, out, B, C, H, W, level, t);
         else swt_all_generic(in, in_dtype, in_layout, out, B, C, H, W, level, t);
     } catch (const std::bad_alloc &) {
-        HT_FAIL(WV_ENOMEM, "swt (host): out of memory for the %dx%d scratch planes", H, W);
+        WV_FAIL(WV_ENOMEM, "swt (host): out of memory for the %dx%d scratch planes", H, W);
     }
     return WV_OK;
 }
@@ -291,7 +277,7 @@ extern "C" int wv_rawstack_forward_cpu(const void *in, int in_dtype, int in_layo
                                        int W, int copies)
 {
     if (int rc = check_common(in, out, B, C, H, W, in_dtype, in_layout, "rawstack (host)")) return rc;
-    HT_REQUIRE(copies > 0, "rawstack (host): copies must be positive");
+    WV_REQUIRE(copies > 0, "rawstack (host): copies must be positive");
     const size_t hw = (size_t)H * W;
     for (int b = 0; b < B; ++b)
         for (int c = 0; c < C; ++c) {
@@ -306,8 +292,8 @@ extern "C" int wv_dwt2d_forward_cpu(const void *in, int in_dtype, int in_layout,
                                     int W, int level, const float *dec_lo, const float *dec_hi, int flen)
 {
     if (int rc = check_common(in, out, B, C, H, W, in_dtype, in_layout, "dwt (host)")) return rc;
-    HT_REQUIRE(dec_lo && dec_hi && flen >= 2 && flen <= 32, "dwt (host): %d taps (supported: 2..32)", flen);
-    HT_REQUIRE(level >= 1 && level <= 12, "dwt (host): level %d out of range", level);
+    WV_REQUIRE(dec_lo && dec_hi && flen >= 2 && flen <= 32, "dwt (host): %d taps (supported: 2..32)", flen);
+    WV_REQUIRE(level >= 1 && level <= 12, "dwt (host): level %d out of range", level);
     Taps t{};
     t.L = flen;
     for (int i = 0; i < flen; ++i) { t.lo[i] = dec_lo[i]; t.hi[i] = dec_hi[i]; }
@@ -337,7 +323,7 @@ extern "C" int wv_dwt2d_forward_cpu(const void *in, int in_dtype, int in_layout,
                 }
             }
     } catch (const std::bad_alloc &) {
-        HT_FAIL(WV_ENOMEM, "dwt (host): out of memory");
+        WV_FAIL(WV_ENOMEM, "dwt (host): out of memory");
     }
     return WV_OK;
 }

@@ -23,16 +23,8 @@ using namespace isz;
 
 constexpr int kThreads = 256;
 
-// clip8 behind an empty asm: hipcc fuses two adjacent clip8 results that are packed with `lo | hi << 8` into one
-// v_ashr_pk_u8_i32, takes the upper 16 bits of its result for zero and ORs the other two bytes onto it -- on gfx950 those
-// bits keep what the register held before (seen as stray bits in bytes 2 and 3 of every dword of rows with an even tap
-// count).  Through the asm every byte is shifted and clamped on its own.
-__device__ __forceinline__ uint32_t clip8_byte(int32_t acc)
-{
-    int v = clip8(acc);
-    asm volatile("" : "+v"(v));
-    return (uint32_t)v;
-}
+// clip8 as a byte of its own (common.hpp: own_byte), safe to pack with its neighbours
+__device__ __forceinline__ uint32_t clip8_byte(int32_t acc) { return own_byte(clip8(acc)); }
 
 __device__ __forceinline__ int ceil_log2(int v) { return v > 1 ? 32 - __builtin_clz((unsigned)(v - 1)) : 0; }
 
@@ -154,8 +146,8 @@ extern "C" int wv_image_size(const uint8_t *src, uint8_t *dst, const wv_size_sta
     WV_REQUIRE(src && dst && stages, "wv_image_size: src / dst / stages is NULL");
     WV_REQUIRE(max_out_h >= 1 && max_out_w >= 1 && max_ksize >= 1, "wv_image_size: max_out_h = %d, max_out_w = %d, max_ksize = %d (all >= 1)",
                max_out_h, max_out_w, max_ksize);
-    if (max_out_h > kMaxSide || max_out_w > kMaxSide)
-        WV_FAIL(WV_ENOTSUP, "wv_image_size: max_out_h = %d, max_out_w = %d (limit %d)", max_out_h, max_out_w, kMaxSide);
+    if (max_out_h > wv::kMaxImageSide || max_out_w > wv::kMaxImageSide)
+        WV_FAIL(WV_ENOTSUP, "wv_image_size: max_out_h = %d, max_out_w = %d (limit %d)", max_out_h, max_out_w, wv::kMaxImageSide);
     if (max_ksize > kMaxKsize) WV_FAIL(WV_ENOTSUP, "wv_image_size: max_ksize = %d (limit %d: a down-scale of %d)", max_ksize, kMaxKsize, kMaxDownscale);
     // LDS: what the largest tile needs at these tap counts, inside [kMinLds, kMaxLds]; every image then plans its own tile
     // under that budget, never smaller than the tile of (max_ksize, max_ksize), which sizes the grid

@@ -15,23 +15,16 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/wvhash.h"
-
-#ifdef __HIP__
-#define WV_ISZ_HD __host__ __device__ inline
-#else
-#define WV_ISZ_HD inline
-#endif
+#include "twin.hpp"
 
 namespace wv {
 namespace isz {
 
 constexpr int kPrecisionBits = 22;
-constexpr int kMaxSide = 16384;
 constexpr int kMaxDownscale = 64;
 constexpr int kMaxKsize = 2 * (2 * kMaxDownscale) + 1;   // bicubic at 64x: support 128; what the limit on the scale protects
 
-WV_ISZ_HD double filter_value(int filter, double t)
+WV_HD double filter_value(int filter, double t)
 {
     if (t < 0.0) t = -t;
     if (filter == WV_RESAMPLE_BILINEAR) return t < 1.0 ? 1.0 - t : 0.0;
@@ -43,7 +36,7 @@ WV_ISZ_HD double filter_value(int filter, double t)
 
 // Taps a coefficient row of this axis can have: Pillow's ksize, but never more than the axis has samples (the bounds clamp
 // at inS); 1 for an axis that is not resampled.
-WV_ISZ_HD int axis_ksize(int inS, int outS, int filter)
+WV_HD int axis_ksize(int inS, int outS, int filter)
 {
     if (inS == outS) return 1;
     double fs = (double)inS / (double)outS;
@@ -54,7 +47,7 @@ WV_ISZ_HD int axis_ksize(int inS, int outS, int filter)
 }
 
 // First source index and tap count of output index xx.  Both are non-decreasing in xx.
-WV_ISZ_HD void axis_bounds(int inS, int outS, int filter, int xx, int *xmin_out, int *n_out)
+WV_HD void axis_bounds(int inS, int outS, int filter, int xx, int *xmin_out, int *n_out)
 {
     if (inS == outS) {
         *xmin_out = xx;
@@ -75,7 +68,7 @@ WV_ISZ_HD void axis_bounds(int inS, int outS, int filter, int xx, int *xmin_out,
 
 // The fixed-point coefficient row of output index xx into k[0 .. n); returns n, *xmin_out = first source index.
 // The weights are evaluated twice (sum, then quotient) instead of being stored: the same values both times.
-WV_ISZ_HD int axis_coeffs(int inS, int outS, int filter, int xx, int32_t *k, int *xmin_out)
+WV_HD int axis_coeffs(int inS, int outS, int filter, int xx, int32_t *k, int *xmin_out)
 {
     int xmin, n;
     axis_bounds(inS, outS, filter, xx, &xmin, &n);
@@ -99,7 +92,7 @@ WV_ISZ_HD int axis_coeffs(int inS, int outS, int filter, int xx, int32_t *k, int
     return n;
 }
 
-WV_ISZ_HD int clip8(int32_t acc)
+WV_HD int clip8(int32_t acc)
 {
     const int v = acc >> kPrecisionBits;   // arithmetic shift
     return v < 0 ? 0 : (v > 255 ? 255 : v);
@@ -116,18 +109,18 @@ struct TilePlan {
     int span_cap;   // source rows the intermediate can hold
 };
 
-WV_ISZ_HD int pitch_of(int cols) { return (cols * 3 + 3) & ~3; }
+WV_HD int pitch_of(int cols) { return (cols * 3 + 3) & ~3; }
 
 // Source rows that `rows` consecutive output rows can need: (rows - 1) * scale + 2 * support + 1, with
 // scale <= max(1, (ksize - 1) / 2) and 2 * support <= ksize - 1 (ksize = 2 * ceil(support) + 1), one spare.  A tap count
 // clamped to the axis length (axis_ksize) keeps the bound: no span is longer than the axis, and ksize + 1 is.
-WV_ISZ_HD int span_bound(int rows, int ksize_v)
+WV_HD int span_bound(int rows, int ksize_v)
 {
     const int sb = (ksize_v - 1) / 2 > 1 ? (ksize_v - 1) / 2 : 1;
     return (rows - 1) * sb + ksize_v + 1;
 }
 
-WV_ISZ_HD size_t lds_need(int rows, int cols, int ksize_h, int ksize_v)
+WV_HD size_t lds_need(int rows, int cols, int ksize_h, int ksize_v)
 {
     return (size_t)span_bound(rows, ksize_v) * pitch_of(cols) + (size_t)cols * (ksize_h + 2) * 4 + (size_t)rows * (ksize_v + 2) * 4;
 }
@@ -135,7 +128,7 @@ WV_ISZ_HD size_t lds_need(int rows, int cols, int ksize_h, int ksize_v)
 constexpr int kTileChain = 11;
 
 // (16,256) (8,256) (8,128) (4,128) (4,64) (2,64) (2,32) (1,32) (1,16) (1,8) (1,4)
-WV_ISZ_HD void tile_candidate(int i, int *rows, int *cols)
+WV_HD void tile_candidate(int i, int *rows, int *cols)
 {
     const int r = 16 >> ((i + 1) / 2);
     *rows = r > 1 ? r : 1;
@@ -143,7 +136,7 @@ WV_ISZ_HD void tile_candidate(int i, int *rows, int *cols)
 }
 
 // rows = 0: nothing fits (never for ksize <= kMaxKsize and lds_bytes >= kMinLds)
-WV_ISZ_HD TilePlan tile_plan(int ksize_h, int ksize_v, size_t lds_bytes)
+WV_HD TilePlan tile_plan(int ksize_h, int ksize_v, size_t lds_bytes)
 {
     TilePlan p = {0, 0, 0};
     for (int i = 0; i < kTileChain; ++i) {

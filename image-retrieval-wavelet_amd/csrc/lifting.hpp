@@ -14,19 +14,12 @@
 #pragma once
 #include <stdint.h>
 
-#include "../../include/wvhash.h"
-
-#ifdef __HIP__
-#define WV_LIFT_HD __host__ __device__ inline
-#else
-#define WV_LIFT_HD inline
-#endif
+#include "twin.hpp"
 
 namespace wv {
 namespace lift {
 
 constexpr int kHaar = 0, kCdf97 = 1;
-constexpr int kMaxSide = 16384;     // H, W of wv_lift_images
 constexpr int kMaxChannels = 4;     // C of wv_lift_images: the kernel stages a tile's bytes of all channels and their tables in LDS
 constexpr int kMaxLevels = 16;
 // wv_lift_images' tile: kTilePairsH x kTilePairsW output samples of every band = 2x that in input samples (+ halo for cdf 9/7)
@@ -55,10 +48,10 @@ inline Consts consts(int basis)
 }
 
 // length of one axis as a level sees it (HaarLifting pads to even, Cdf97Lifting to a multiple of 4, with zeros at the end)
-WV_LIFT_HD int padded(int n, int basis) { return basis == kHaar ? n + (n & 1) : (n + 3) & ~3; }
+WV_HD int padded(int n, int basis) { return basis == kHaar ? n + (n & 1) : (n + 3) & ~3; }
 
 // length of one axis after `levels` levels
-WV_LIFT_HD int out_size(int n, int basis, int levels)
+WV_HD int out_size(int n, int basis, int levels)
 {
     for (int l = 0; l < levels; ++l) n = padded(n, basis) / 2;
     return n;
@@ -69,7 +62,7 @@ WV_LIFT_HD int out_size(int n, int basis, int levels)
 // share their intermediates: every intermediate is formed once, by the same operations in the same order whatever N is, so
 // the results do not depend on N.  (Pairs at or beyond n come out as whatever the zero rule yields; callers drop them.)
 template <int BASIS, int N, class Ev, class Od>
-WV_LIFT_HD void pairs(Ev ev, Od od, int n, int i, const Consts &c, float (&s)[N], float (&d)[N])
+WV_HD void pairs(Ev ev, Od od, int n, int i, const Consts &c, float (&s)[N], float (&d)[N])
 {
 #ifdef __clang__
 #pragma clang fp contract(off)
@@ -119,7 +112,7 @@ WV_LIFT_HD void pairs(Ev ev, Od od, int n, int i, const Consts &c, float (&s)[N]
 
 // one pair
 template <int BASIS, class Ev, class Od>
-WV_LIFT_HD void pair(Ev ev, Od od, int n, int i, const Consts &c, float &s, float &d)
+WV_HD void pair(Ev ev, Od od, int n, int i, const Consts &c, float &s, float &d)
 {
     float s1[1], d1[1];
     pairs<BASIS, 1>(ev, od, n, i, c, s1, d1);
@@ -136,7 +129,7 @@ struct Convert {
 // Both divisions must be IEEE-correct on the device as on the host: lifting_batched.o is built with
 // -fhip-fp32-correctly-rounded-divide-sqrt spelled out (csrc/Makefile); a reciprocal-multiply division would differ in the
 // last bit for constants no test uses.
-WV_LIFT_HD float convert_byte(const Convert &cv, int c, int x)
+WV_HD float convert_byte(const Convert &cv, int c, int x)
 {
     float t = (float)x;
     if (cv.to_tensor) t = t / 255.0f;

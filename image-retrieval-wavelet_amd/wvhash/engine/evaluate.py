@@ -100,7 +100,7 @@ class GlobalEmbeddingSpaceTester:
         # a plugin built with sizing="device" yields RawItems (pixels as decoded + recorded geometry): packed by raw_collate
         from ..transforms.custom_transforms import find_wavelet_transform
         tf = find_wavelet_transform(dataset)
-        collate = raw_collate if getattr(tf, "sizing", "host") == "device" else None
+        collate = raw_collate if tf is not None and tf.sizing == "device" else None
         dl = DataLoader(dataset, batch_size=self.batch_size, num_workers=self.dataloader_num_workers,
                         shuffle=False, drop_last=False, pin_memory=True, collate_fn=collate)
         return self.compute_all_embeddings(dl, trunk_model, embedder_model)

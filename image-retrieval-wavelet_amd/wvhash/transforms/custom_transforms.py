@@ -21,8 +21,20 @@ takes the collated ``sizing.RawBatch``: sized on the GPU (``functional.size_imag
 import numpy as np
 import torch
 from PIL import Image
+from torch.utils.data import get_worker_info
 
 from . import functional as F
+from .sizing import LazyImage
+
+
+def _use_host(device, tensor=None):
+    """True when a per-image call must not touch the GPU: explicit device='cpu', or a DataLoader worker process (which cannot
+    use the parent's GPU context).  A tensor that already lives on the GPU stays there."""
+    if tensor is not None and tensor.is_cuda:
+        return False
+    if device is not None and torch.device(device).type == "cpu":
+        return True
+    return get_worker_info() is not None
 
 
 class BaseWaveletTransform(object):
@@ -66,16 +78,10 @@ class BaseWaveletTransform(object):
         tensors the host twin.  A sizing.RawBatch (sizing="device") is sized first, where it lives."""
         raise NotImplementedError
 
-    def _use_host(self):
-        """True when __call__ must not touch the GPU: explicit device='cpu', or a DataLoader worker process."""
-        if self.device is not None and torch.device(self.device).type == "cpu":
-            return True
-        from torch.utils.data import get_worker_info
-        return get_worker_info() is not None
-
     def __call__(self, img):
+        """The worker-side entry of every plugin: under device sizing the recorded image (fix_size included) becomes a
+        RawItem; otherwise the pixels (_to_u8_hwc) are handed on as uint8 [C, H, W] when deferred, transformed when not."""
         if self.sizing == "device":
-            from .sizing import LazyImage
             lazy = img if isinstance(img, LazyImage) else LazyImage(img)
             return self.fix_size(lazy).to_item()
         arr = self._to_u8_hwc(img)
@@ -88,7 +94,7 @@ class BaseWaveletTransform(object):
         else:  # the reference computes astype(float32) / 255 for any dtype
             x = torch.from_numpy(arr.astype(np.float32) / 255.0)
         x = x.unsqueeze(0)
-        if self._use_host():
+        if _use_host(self.device):
             return self.apply_batch(x, channels_last=True)[0]
         from .. import _lib
         try:

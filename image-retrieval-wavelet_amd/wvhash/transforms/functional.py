@@ -4,7 +4,10 @@ import ctypes
 import torch
 
 from .. import _lib
+from .sizing import COLOURS, STAGES, RawBatch
 from .wavelets import get_filters
+
+LIFT_BASIS = {"haar": 0, "cdf97": 1}
 
 
 def _layout_and_shape(x, channels_last):
@@ -17,6 +20,24 @@ def _layout_and_shape(x, channels_last):
     return _lib.WV_LAYOUT_NCHW, B, C, H, W
 
 
+def _batch(x, channels_last, what, on_gpu, note):
+    """The preamble of every wrapper below -> (x contiguous, layout, B, C, H, W); x must live where `what` runs."""
+    if x.is_cuda != on_gpu:
+        raise ValueError(f"{what}: input must live on the GPU{note}" if on_gpu else f"{what}: the host twin takes host tensors ({note})")
+    x = x.contiguous()
+    return (x,) + _layout_and_shape(x, channels_last)
+
+
+_HOST_NOTE = "use the device function for GPU tensors"
+
+
+def _swt_size(H, W, level):
+    if H % (1 << level) or W % (1 << level):
+        # PyWavelets' message for swt2 on a bad size
+        raise ValueError(f"Length of data must be even along the transform axis / divisible by 2**level; "
+                         f"got {H}x{W} at level {level}")
+
+
 def _in_dtype(x):
     if x.dtype == torch.uint8:
         return _lib.WV_DT_U8
@@ -26,15 +47,13 @@ def _in_dtype(x):
 
 
 def _size_launches(raw_batch, call, work, colour_call):
-    from .sizing import COLOUR_WORDS, STAGE_WORDS
-    base = raw_batch.desc.data_ptr()
-    colour_launches = getattr(raw_batch, "colour_launches", ())
+    colour_launches = raw_batch.colour_launches
     for s, (first, count, max_h, max_w, max_k) in enumerate(raw_batch.launches):
         src = raw_batch.data if s == 0 else work          # later stages read what earlier ones wrote
-        call(_lib.ptr(src), _lib.ptr(work), ctypes.c_void_p(base + first * STAGE_WORDS * 4), count, max_h, max_w, max_k)
+        call(_lib.ptr(src), _lib.ptr(work), STAGES.address(raw_batch.desc, first), count, max_h, max_w, max_k)
         if s < len(colour_launches) and colour_launches[s][1]:
             first, count, max_h, max_w = colour_launches[s]  # the colour chains of what this stage wrote, in place
-            colour_call(_lib.ptr(work), ctypes.c_void_p(raw_batch.colour.data_ptr() + first * COLOUR_WORDS * 4), count, max_h, max_w)
+            colour_call(_lib.ptr(work), COLOURS.address(raw_batch.colour, first), count, max_h, max_w)
     B, H, W = raw_batch.out_shape
     return work[:B * H * W * 3].view(B, H, W, 3)
 
@@ -50,7 +69,7 @@ def size_images(raw_batch):
         raise ValueError("size_images: the batch must live on the GPU (size_images_host is the host twin)")
     if raw_batch.desc.dtype != torch.int32 or not raw_batch.desc.is_contiguous() or not raw_batch.data.is_contiguous():
         raise ValueError("size_images: descriptor tensor must be contiguous int32, data contiguous uint8")
-    colour = getattr(raw_batch, "colour", None)
+    colour = raw_batch.colour
     if colour is not None and (colour.dtype != torch.int32 or not colour.is_contiguous() or colour.device != raw_batch.device):
         raise ValueError("size_images: colour descriptor tensor must be contiguous int32 on the batch's device")
     work = torch.empty(raw_batch.work_bytes, dtype=torch.uint8, device=raw_batch.device)
@@ -87,7 +106,6 @@ def size_images_host(raw_batch):
 def sized(batch, channels_last):
     """(batch, channels_last) with a sizing.RawBatch replaced by its sized uint8 [B, H, W, 3] images (on the GPU when it
     lives there, by the host twin otherwise); tensors pass through."""
-    from .sizing import RawBatch
     if isinstance(batch, RawBatch):
         return (size_images(batch) if batch.is_cuda else size_images_host(batch)), True
     return batch, channels_last
@@ -105,10 +123,7 @@ def swt2d(x, wavelet="haar", level=1, channels_last=False, out_dtype=torch.float
     view and the sub-band tensor is never copied a second time.
     """
     lib = _lib.require_gpu()
-    if not x.is_cuda:
-        raise ValueError("swt2d: input must live on the GPU (swt2d_host is the host twin)")
-    x = x.contiguous()
-    layout, B, C, H, W = _layout_and_shape(x, channels_last)
+    x, layout, B, C, H, W = _batch(x, channels_last, "swt2d", True, " (swt2d_host is the host twin)")
     lo, hi = get_filters(wavelet)
     if out_dtype == torch.float32:
         odt = _lib.WV_DT_F32
@@ -123,10 +138,7 @@ def swt2d(x, wavelet="haar", level=1, channels_last=False, out_dtype=torch.float
         raise ValueError(f"swt2d: `out` must be a contiguous {list(shape)} tensor of out_dtype on the input's device")
     if B == 0:
         return out
-    if H % (1 << level) or W % (1 << level):
-        # PyWavelets' message for swt2 on a bad size
-        raise ValueError(f"Length of data must be even along the transform axis / divisible by 2**level; "
-                         f"got {H}x{W} at level {level}")
+    _swt_size(H, W, level)
     ws_bytes = lib.wv_swt2d_workspace_bytes(B, C, H, W, level, len(lo))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
     flo, fhi = _lib.host_floats(lo), _lib.host_floats(hi)
@@ -190,10 +202,7 @@ def dwt2d(x, wavelet="haar", level=1, channels_last=False):
     """Batch of images on the GPU -> [B, C, 4, H', W'] coarsest-level bands of the decimated DWT
     (``pywt.wavedec2(..., mode='symmetric')``, DWTTransform at custom_transforms.py:197-201)."""
     lib = _lib.require_gpu()
-    if not x.is_cuda:
-        raise ValueError("dwt2d: input must live on the GPU (no CPU path in the product)")
-    x = x.contiguous()
-    layout, B, C, H, W = _layout_and_shape(x, channels_last)
+    x, layout, B, C, H, W = _batch(x, channels_last, "dwt2d", True, " (no CPU path in the product)")
     lo, hi = get_filters(wavelet)
     Hn, Wn = lib.wv_dwt_out_len(H, len(lo), level), lib.wv_dwt_out_len(W, len(lo), level)
     out = torch.empty((B, C, 4, Hn, Wn), dtype=torch.float32, device=x.device)
@@ -212,10 +221,7 @@ def dwt2d(x, wavelet="haar", level=1, channels_last=False):
 def rawstack(x, copies=4, channels_last=False):
     """[B,C,H,W] -> [B,C,copies,H,W] identical planes (RawStackTransform, :172-188)."""
     lib = _lib.require_gpu()
-    if not x.is_cuda:
-        raise ValueError("rawstack: input must live on the GPU")
-    x = x.contiguous()
-    layout, B, C, H, W = _layout_and_shape(x, channels_last)
+    x, layout, B, C, H, W = _batch(x, channels_last, "rawstack", True, "")
     out = torch.empty((B, C, copies, H, W), dtype=torch.float32, device=x.device)
     if B == 0:
         return out
@@ -226,22 +232,18 @@ def rawstack(x, copies=4, channels_last=False):
     return out
 
 
-_LIFT_BASIS = {"haar": 0, "cdf97": 1}
-
-
-def _lift_args(x, channels_last, mean, std, basis, levels, ll_only, what):
+def _lift_args(x, channels_last, mean, std, basis, levels, ll_only, what, on_gpu, note):
     """-> (x contiguous, C-ABI arguments between `in` and `out`, output shape).  The argument check is the library's."""
-    if basis not in _LIFT_BASIS:
+    x, layout, B, C, H, W = _batch(x, channels_last, what, on_gpu, note)
+    if basis not in LIFT_BASIS:
         raise ValueError(f"{what}: basis must be 'haar' or 'cdf97', got {basis!r}")
-    x = x.contiguous()
-    layout, B, C, H, W = _layout_and_shape(x, channels_last)
     dt = _in_dtype(x)
     if (mean is None) != (std is None):
         raise ValueError(f"{what}: mean and std come together")
     if mean is not None and (len(mean) != C or len(std) != C):
         raise ValueError(f"{what}: mean / std need one value per channel ({C}), got {len(mean)} / {len(std)}")
     lib = _lib.load()
-    b, levels, ll_only = _LIFT_BASIS[basis], int(levels), int(bool(ll_only))
+    b, levels, ll_only = LIFT_BASIS[basis], int(levels), int(bool(ll_only))
     _lib.check(lib.wv_lift_images_check(dt, layout, B, C, H, W, b, levels, ll_only), "wv_lift_images_check")
     h, w = (lib.wv_lift_out_size(H, b, levels), lib.wv_lift_out_size(W, b, levels)) if levels else (H, W)
     shape = (B, C, h, w) if levels == 0 or ll_only else (B, C, 4, h, w)
@@ -258,9 +260,8 @@ def lift_images(x, mean=None, std=None, basis="haar", levels=1, ll_only=False, c
     or float32, used as it is (mean / std must be None).  -> float32 [B,C,4,h,w] = (LL, LH, HL, HH) of the coarsest level,
     [B,C,h,w] with ll_only, [B,C,H,W] for levels = 0 (the conversion alone)."""
     lib = _lib.require_gpu()
-    if not x.is_cuda:
-        raise ValueError("lift_images: input must live on the GPU (lift_images_host is the host twin)")
-    x, args, shape = _lift_args(x, channels_last, mean, std, basis, levels, ll_only, "lift_images")
+    x, args, shape = _lift_args(x, channels_last, mean, std, basis, levels, ll_only, "lift_images", True,
+                                " (lift_images_host is the host twin)")
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
     if shape[0] == 0:
         return out
@@ -275,9 +276,8 @@ def lift_images(x, mean=None, std=None, basis="haar", levels=1, ll_only=False, c
 def lift_images_host(x, mean=None, std=None, basis="haar", levels=1, ll_only=False, channels_last=False):
     """Host twin of lift_images (wv_lift_images_cpu): host tensors in, the same bits out."""
     lib = _lib.load()
-    if x.is_cuda:
-        raise ValueError("lift_images_host: the host twin takes host tensors (lift_images is the device function)")
-    x, args, shape = _lift_args(x, channels_last, mean, std, basis, levels, ll_only, "lift_images_host")
+    x, args, shape = _lift_args(x, channels_last, mean, std, basis, levels, ll_only, "lift_images_host", False,
+                                "lift_images is the device function")
     out = torch.empty(shape, dtype=torch.float32)
     if shape[0] == 0:
         return out
@@ -289,25 +289,15 @@ def lift_images_host(x, mean=None, std=None, basis="haar", levels=1, ll_only=Fal
 # Host twins (wv_*_forward_cpu): what the plugins' __call__ runs inside forked DataLoader workers, where the
 # reference runs pywt (flikr_coco.py:59-60 -> custom_transforms.py:145-157) and the GPU is out of reach.
 # Host tensors in, host tensors out; single-threaded native code, no HIP call.
-def _host_args(x, channels_last, what):
-    if x.is_cuda:
-        raise ValueError(f"{what}: the host twin takes host tensors (use the device function for GPU tensors)")
-    x = x.contiguous()
-    layout, B, C, H, W = _layout_and_shape(x, channels_last)
-    return x, layout, B, C, H, W
-
-
 def swt2d_host(x, wavelet="haar", level=1, channels_last=False):
     """Host twin of swt2d: [B,C,H,W] (or [B,H,W,C]) uint8 / float32 on the CPU -> float32 [B,C,4,H,W]."""
     lib = _lib.load()
-    x, layout, B, C, H, W = _host_args(x, channels_last, "swt2d_host")
+    x, layout, B, C, H, W = _batch(x, channels_last, "swt2d_host", False, _HOST_NOTE)
     lo, hi = get_filters(wavelet)
     out = torch.empty((B, C, 4, H, W), dtype=torch.float32)
     if B == 0:
         return out
-    if H % (1 << level) or W % (1 << level):
-        raise ValueError(f"Length of data must be even along the transform axis / divisible by 2**level; "
-                         f"got {H}x{W} at level {level}")
+    _swt_size(H, W, level)
     rc = lib.wv_swt2d_forward_cpu(_lib.ptr(x), _in_dtype(x), layout, _lib.ptr(out), B, C, H, W, level,
                                   _lib.host_floats(lo), _lib.host_floats(hi), len(lo))
     _lib.check(rc, "wv_swt2d_forward_cpu")
@@ -317,7 +307,7 @@ def swt2d_host(x, wavelet="haar", level=1, channels_last=False):
 def dwt2d_host(x, wavelet="haar", level=1, channels_last=False):
     """Host twin of dwt2d -> float32 [B,C,4,H',W']."""
     lib = _lib.load()
-    x, layout, B, C, H, W = _host_args(x, channels_last, "dwt2d_host")
+    x, layout, B, C, H, W = _batch(x, channels_last, "dwt2d_host", False, _HOST_NOTE)
     lo, hi = get_filters(wavelet)
     Hn, Wn = lib.wv_dwt_out_len(H, len(lo), level), lib.wv_dwt_out_len(W, len(lo), level)
     out = torch.empty((B, C, 4, Hn, Wn), dtype=torch.float32)
@@ -332,7 +322,7 @@ def dwt2d_host(x, wavelet="haar", level=1, channels_last=False):
 def rawstack_host(x, copies=4, channels_last=False):
     """Host twin of rawstack -> float32 [B,C,copies,H,W]."""
     lib = _lib.load()
-    x, layout, B, C, H, W = _host_args(x, channels_last, "rawstack_host")
+    x, layout, B, C, H, W = _batch(x, channels_last, "rawstack_host", False, _HOST_NOTE)
     out = torch.empty((B, C, copies, H, W), dtype=torch.float32)
     if B == 0:
         return out

@@ -1,11 +1,12 @@
 """Legacy lifting-scheme transforms with the reference's names and call conventions
 (/root/reference/main/transforms/custom_transforms.py:14-117): ``HaarLifting``, ``Cdf97Lifting``, ``ResizeSubBands``,
-``CustomTransform(decompose_levels, basis, coarse_only, ll_only)``.  The lifting arithmetic runs in libwvhash
-(``wv_lifting2d_forward``, bit-identical to the reference's float32 torch ops); padding and the level cascade are host
-logic.  Inputs are float tensors ``[C, H, W]`` or ``[N, C, H, W]`` (what ToTensor / Normalize hand over); a CPU tensor is
-moved to the GPU for the call and the result comes back on its original device, so the classes also work as a
-per-image transform in a ``num_workers=0`` pipeline.  With ``device="cpu"``, or inside a DataLoader worker, ``CustomTransform``
-takes the library's host twin instead (``wv_lift_images_cpu``: same bits, no GPU touched).
+``CustomTransform(decompose_levels, basis, coarse_only, ll_only)``.  The lifting arithmetic runs in libwvhash, bit-identical
+to the reference's float32 torch ops: the lifting modules pad on the host and run one ``wv_lifting2d_forward`` per level,
+``CustomTransform`` is one ``wv_lift_images`` call over the planes.  Inputs are float tensors ``[C, H, W]`` or ``[N, C, H, W]``
+(what ToTensor / Normalize hand over); a CPU tensor is moved to the GPU for the call and the result comes back on its
+original device, so the classes also work as a per-image transform in a ``num_workers=0`` pipeline.  With ``device="cpu"``, or
+inside a DataLoader worker, ``CustomTransform`` takes the library's host twin instead (``wv_lift_images_cpu``: same bits, no
+GPU touched).
 
 The batched form is ``TensorTailTransform``: the whole tensor tail ``ToTensor [-> Normalize] [-> CustomTransform]`` of a
 deferred pipeline as one plugin step whose ``apply_batch`` is one ``wv_lift_images`` call on the sized uint8 batch.
@@ -13,15 +14,14 @@ deferred pipeline as one plugin step whose ``apply_batch`` is one ``wv_lift_imag
 import ctypes
 from collections.abc import Sequence
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
 from . import functional as Fn
-from .custom_transforms import BaseWaveletTransform
-
-_BASIS = {"haar": 0, "cdf97": 1}
+from .custom_transforms import BaseWaveletTransform, _use_host
 
 
 def lifting2d(x, basis):
@@ -41,7 +41,7 @@ def lifting2d(x, basis):
     ws_bytes = lib.wv_lifting2d_workspace_bytes(planes, H, W)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        rc = lib.wv_lifting2d_forward(_lib.ptr(x), planes, H, W, _BASIS[basis], _lib.ptr(ll), _lib.ptr(hi), _lib.ptr(ws),
+        rc = lib.wv_lifting2d_forward(_lib.ptr(x), planes, H, W, Fn.LIFT_BASIS[basis], _lib.ptr(ll), _lib.ptr(hi), _lib.ptr(ws),
                                       ctypes.c_size_t(ws_bytes), _lib.stream_ptr())
         _lib.check(rc, "wv_lifting2d_forward")
     return ll, hi
@@ -123,6 +123,11 @@ class ResizeSubBands(nn.Module):
 WAVELET_DICT = {"haar": HaarLifting, "cdf97": Cdf97Lifting}
 
 
+def _refuse_unstackable(levels, coarse_only, ll_only):
+    if not coarse_only and levels > 1:      # levels have different sizes: nothing to stack (the reference raises as well)
+        raise NotImplementedError(f"Full {'approx' if ll_only else 'subbands'} not implemented yet for decompose_levels > 1 ")
+
+
 class CustomTransform:
     """Tensor-side lifting DWT of the legacy CNN configs (custom_transforms.py:90-117).  Output by option pair:
 
@@ -141,37 +146,18 @@ class CustomTransform:
         self.decompose_levels, self.basis, self.device = decompose_levels, basis, device
         self.coarse_only, self.ll_only = coarse_only, ll_only
 
-    def _use_host(self, img):
-        """A host tensor with device='cpu', or inside a DataLoader worker (which cannot use the parent's GPU context): the
-        library's host twin."""
-        if img.is_cuda:
-            return False
-        if self.device is not None and torch.device(self.device).type == "cpu":
-            return True
-        from torch.utils.data import get_worker_info
-        return get_worker_info() is not None
-
-    def _check_stackable(self):
-        if not self.coarse_only and self.decompose_levels > 1:   # levels have different sizes: nothing to stack (the reference raises as well)
-            what = "approx" if self.ll_only else "subbands"
-            raise NotImplementedError(f"Full {what} not implemented yet for decompose_levels > 1 ")
-
     def __call__(self, img):
-        if self._use_host(img):
-            self._check_stackable()                 # one level: every option pair is the coarsest level's bands
-            *lead, H, W = img.shape
-            planes = img.float().reshape(-1, 1, H, W)
-            out = Fn.lift_images_host(planes, basis=self.basis, levels=self.decompose_levels, ll_only=self.ll_only)
-            return out.reshape(*lead, *out.shape[2:])
-        approx, details = self.dwt(img)
-        if self.coarse_only:
-            top = approx[-1]
-            return top if self.ll_only else torch.cat([top.unsqueeze(-3), details[-1]], dim=-3)
-        if self.decompose_levels > 1:      # levels have different sizes: nothing to stack (the reference raises as well)
-            what = "approx" if self.ll_only else "subbands"
-            raise NotImplementedError(f"Full {what} not implemented yet for decompose_levels > 1 ")
-        bands = list(approx) if self.ll_only else [a.unsqueeze(-3) for a in approx] + list(details)
-        return torch.cat(bands, dim=-3)
+        # what is left is stackable, and then every option pair is the coarsest level's bands
+        _refuse_unstackable(self.decompose_levels, self.coarse_only, self.ll_only)
+        *lead, H, W = img.shape
+        planes = img.float().reshape(-1, 1, H, W)
+        kwargs = dict(basis=self.basis, levels=self.decompose_levels, ll_only=self.ll_only)
+        if _use_host(self.device, img):
+            out = Fn.lift_images_host(planes, **kwargs)
+        else:
+            _lib.require_gpu()
+            out = Fn.lift_images(planes if planes.is_cuda else planes.cuda(), **kwargs).to(img.device)
+        return out.reshape(*lead, *out.shape[2:])
 
 
 class TensorTailTransform(BaseWaveletTransform):
@@ -187,15 +173,13 @@ class TensorTailTransform(BaseWaveletTransform):
         custom = None if custom is None else dict(custom)
         levels = 0 if custom is None else int(custom.get("decompose_levels", 3))
         basis = "haar" if custom is None else custom.get("basis", "haar")
-        if basis not in _BASIS:
+        if basis not in Fn.LIFT_BASIS:
             raise KeyError(basis)
         if not defer:
             raise ValueError("TensorTailTransform is the deferred form of the tail; with defer=False the steps run per image")
         super().__init__(level=levels, wavelet=basis, defer=True, device=device, sizing=sizing)
         self.ll_only = bool(custom.get("ll_only", False)) if custom else False
-        if custom is not None and not custom.get("coarse_only", True) and levels > 1:
-            what = "approx" if self.ll_only else "subbands"
-            raise NotImplementedError(f"Full {what} not implemented yet for decompose_levels > 1 ")
+        _refuse_unstackable(levels, custom is None or custom.get("coarse_only", True), self.ll_only)
         if (mean is None) != (std is None):
             raise ValueError("Normalize needs mean and std")
         self.mean = None if mean is None else tuple(float(v) for v in mean)
@@ -207,18 +191,11 @@ class TensorTailTransform(BaseWaveletTransform):
     def fix_size(self, image):
         return image
 
-    def __call__(self, img):
-        import numpy as np
-        from .sizing import LazyImage
-        if self.sizing == "device":
-            lazy = img if isinstance(img, LazyImage) else LazyImage(img)
-            return lazy.to_item()
+    def _to_u8_hwc(self, img):
         arr = np.array(img)
         if arr.dtype != np.uint8 or arr.ndim not in (2, 3):
             raise TypeError(f"deferred ToTensor expects an 8-bit image, got an array of shape {arr.shape} and dtype {arr.dtype}")
-        if arr.ndim == 2:
-            arr = arr[:, :, None]
-        return torch.from_numpy(np.ascontiguousarray(arr)).permute(2, 0, 1).contiguous()
+        return np.ascontiguousarray(arr if arr.ndim == 3 else arr[:, :, None])
 
     def apply_batch(self, batch, channels_last=False, **kwargs):
         batch, channels_last = Fn.sized(batch, channels_last)

@@ -37,13 +37,38 @@ from PIL import Image, ImageEnhance
 
 from .. import _lib
 
-STAGE_WORDS = ctypes.sizeof(_lib.SizeStage) // 4           # 20 int32 words per descriptor
-STAGE_DTYPE = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8")] + [(n, "<i4") for n, _ in _lib.SizeStage._fields_[2:]])
-assert STAGE_DTYPE.itemsize == ctypes.sizeof(_lib.SizeStage) == 80
-COLOUR_WORDS = ctypes.sizeof(_lib.ColourOps) // 4          # 12 32-bit words per descriptor
-COLOUR_DTYPE = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("row_bytes", "<i4"), ("n_ops", "<i4"),
-                         ("kind", "<i4", (3,)), ("factor", "<f4", (3,))])
-assert COLOUR_DTYPE.itemsize == ctypes.sizeof(_lib.ColourOps) == 48
+
+class _Table(object):
+    """One descriptor table of the C ABI: the numpy dtype of a record, its 32-bit words, the name of its ``*_check`` symbol."""
+
+    def __init__(self, dtype, struct, check_name):
+        self.dtype, self.words, self.check_name = np.dtype(dtype), ctypes.sizeof(struct) // 4, check_name
+        assert self.dtype.itemsize == ctypes.sizeof(struct)
+
+    def check(self, rec):
+        """The table's check on host records -> return code (0, WV_EINVAL or WV_ENOTSUP); the message is wv_last_error()."""
+        rec = np.ascontiguousarray(rec)
+        return getattr(_lib.load(), self.check_name)(ctypes.c_void_p(rec.ctypes.data), len(rec))
+
+    def require(self, rec):
+        """The same check, raising: the descriptors pass on the host copy, the device entry points cannot read them."""
+        _lib.check(self.check(rec), self.check_name)
+
+    def tensor(self, chunks):
+        """Record arrays -> one int32 [records, words] tensor (bit patterns)."""
+        return torch.from_numpy(np.concatenate(chunks).view(np.int32).reshape(-1, self.words).copy())
+
+    def address(self, tensor, first):
+        """Where record `first` of such a tensor lies."""
+        return ctypes.c_void_p(tensor.data_ptr() + first * self.words * 4)
+
+
+STAGES = _Table([("src_offset", "<i8"), ("dst_offset", "<i8")] + [(n, "<i4") for n, _ in _lib.SizeStage._fields_[2:]],
+                _lib.SizeStage, "wv_image_size_check")                        # wv_size_stage: 80 bytes
+COLOURS = _Table([("offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("row_bytes", "<i4"), ("n_ops", "<i4"), ("kind", "<i4", (3,)),
+                  ("factor", "<f4", (3,))], _lib.ColourOps, "wv_colour_jitter_check")   # wv_colour_ops: 48 bytes
+STAGE_DTYPE, STAGE_WORDS, check_records = STAGES.dtype, STAGES.words, STAGES.check
+COLOUR_DTYPE, COLOUR_WORDS, check_colour_records = COLOURS.dtype, COLOURS.words, COLOURS.check
 COLOUR_KINDS = {"brightness": _lib.WV_COLOUR_BRIGHTNESS, "contrast": _lib.WV_COLOUR_CONTRAST,
                 "saturation": _lib.WV_COLOUR_SATURATION}
 _ENHANCERS = {"brightness": ImageEnhance.Brightness, "contrast": ImageEnhance.Contrast, "saturation": ImageEnhance.Color}
@@ -84,19 +109,23 @@ class NotRecordable(ValueError):
     """The call log describes something the stages cannot express (to_item sizes such an image with PIL)."""
 
 
+def _fresh_stage(w, h):
+    """A stage that shows a w x h image as it is."""
+    return {"src_w": w, "src_h": h, "crop": [0, 0, w, h], "res": None, "win": [0, 0, w, h], "flip": 0,
+            "filter": _lib.WV_RESAMPLE_BILINEAR, "colour": []}
+
+
+def _shown(st):
+    """(w, h) of the image the stage's window looks at: the resampled one, the crop where nothing is resampled."""
+    rw, rh = st["res"] if st["res"] is not None else st["crop"][2:]
+    return rw, rh
+
+
 def stages_from_ops(width, height, ops):
     """The call log of a LazyImage -> list of stage dicts (sizes only, offsets and row pitches are the packer's).  A stage's
     "colour" is its chain [(kind name, factor), ...] in running order."""
     stages, cur = [], None
     w, h = width, height
-
-    def fresh():
-        return {"src_w": w, "src_h": h, "crop": [0, 0, w, h], "res": None, "win": [0, 0, w, h], "flip": 0,
-                "filter": _lib.WV_RESAMPLE_BILINEAR, "colour": []}
-
-    def shown(st):
-        rw, rh = st["res"] if st["res"] is not None else st["crop"][2:]
-        return rw, rh
 
     for op in ops:
         if op[0] == "resize":
@@ -104,13 +133,13 @@ def stages_from_ops(width, height, ops):
             if (nw, nh) == (w, h):
                 continue                                    # Pillow returns a copy: nothing is resampled
             if cur is None:
-                cur = fresh()
-            rw, rh = shown(cur)
+                cur = _fresh_stage(w, h)
+            rw, rh = _shown(cur)
             x, y, ww, wh = cur["win"]
             padded = x < 0 or y < 0 or x + ww > rw or y + wh > rh
             if cur["res"] is not None or cur["flip"] or padded or cur["colour"]:
                 stages.append(cur)
-                cur = fresh()
+                cur = _fresh_stage(w, h)
                 x, y, ww, wh = cur["win"]
             cx, cy = cur["crop"][:2]
             cur["crop"] = [cx + x, cy + y, ww, wh]          # the window of an unresampled stage is a crop
@@ -119,26 +148,26 @@ def stages_from_ops(width, height, ops):
         elif op[0] == "crop":
             x, y, cw, ch = op[1]
             if cur is None:
-                cur = fresh()
+                cur = _fresh_stage(w, h)
             wx, wy, ww, wh = cur["win"]
             if cur["colour"]:
                 stages.append(cur)                          # the contrast mean belongs to the image before the crop
-                cur = fresh()
-            elif (x < 0 or y < 0 or x + cw > ww or y + ch > wh) and [wx, wy, ww, wh] != [0, 0, *shown(cur)]:
+                cur = _fresh_stage(w, h)
+            elif (x < 0 or y < 0 or x + cw > ww or y + ch > wh) and [wx, wy, ww, wh] != [0, 0, *_shown(cur)]:
                 stages.append(cur)                          # the zero pad is relative to the window, not to the image
-                cur = fresh()
+                cur = _fresh_stage(w, h)
             if cur["flip"]:
                 x = cur["win"][2] - x - cw
             cur["win"] = [cur["win"][0] + x, cur["win"][1] + y, cw, ch]
             w, h = cw, ch
         elif op[0] == "mirror":
             if cur is None:
-                cur = fresh()
+                cur = _fresh_stage(w, h)
             cur["flip"] ^= 1
         elif op[0] == "colour":
             kind, factor = op[1], op[2]
             if cur is None:
-                cur = fresh()
+                cur = _fresh_stage(w, h)
             if kind not in COLOUR_KINDS:
                 raise NotRecordable(f"colour operation {kind!r} is not one of the kernel's")
             if any(k == kind for k, _ in cur["colour"]):
@@ -154,7 +183,7 @@ def stages_from_ops(width, height, ops):
 def _records(stages):
     rec = np.zeros(len(stages), dtype=STAGE_DTYPE)
     for r, st in zip(rec, stages):
-        rw, rh = st["res"] if st["res"] is not None else st["crop"][2:]
+        rw, rh = _shown(st)
         r["src_h"], r["src_w"], r["src_row_bytes"] = st["src_h"], st["src_w"], 3 * st["src_w"]
         r["crop_x"], r["crop_y"], r["crop_w"], r["crop_h"] = st["crop"]
         r["res_h"], r["res_w"] = rh, rw
@@ -172,18 +201,6 @@ def _colour_records(stages):
         for i, (kind, factor) in enumerate(st["colour"]):
             r["kind"][i], r["factor"][i] = COLOUR_KINDS[kind], factor
     return rec
-
-
-def check_colour_records(rec):
-    """wv_colour_jitter_check on host descriptors -> return code; the message is wv_last_error()."""
-    rec = np.ascontiguousarray(rec)
-    return _lib.load().wv_colour_jitter_check(ctypes.c_void_p(rec.ctypes.data), len(rec))
-
-
-def check_records(rec):
-    """wv_image_size_check on host descriptors -> return code (0, WV_EINVAL or WV_ENOTSUP); the message is wv_last_error()."""
-    rec = np.ascontiguousarray(rec)
-    return _lib.load().wv_image_size_check(ctypes.c_void_p(rec.ctypes.data), len(rec))
 
 
 class LazyImage(object):
@@ -249,17 +266,15 @@ class LazyImage(object):
         if stages is not None:
             rec, col = _records(stages), _colour_records(stages)
             rc = 0
-            for i in range(len(rec)):                       # one record per launch: each on its own
-                rc = rc or check_records(rec[i:i + 1])
-            what = "wv_image_size_check"
-            if rc == 0:
-                what = "wv_colour_jitter_check"
-                for i in range(len(col)):
-                    rc = rc or check_colour_records(col[i:i + 1])
+            for table, r in ((STAGES, rec), (COLOURS, col)):
+                for i in range(len(r)):                     # one record per launch: each on its own
+                    rc = rc or table.check(r[i:i + 1])
+                if rc != 0:
+                    break
             if rc == 0:
                 return RawItem(torch.from_numpy(np.array(self.img)), rec, col if col["n_ops"].any() else None)
             if rc != _lib.WV_ENOTSUP:
-                _lib.check(rc, what)
+                _lib.check(rc, table.check_name)
         arr = np.array(self.materialize())                  # outside the kernel: PIL in the worker, as sizing="host" does
         if arr.ndim != 3 or arr.shape[2] < 3 or arr.dtype != np.uint8:
             raise ValueError(f"expected an 8-bit RGB image (H, W, 3), got array of shape {arr.shape} and dtype {arr.dtype}")
@@ -325,9 +340,29 @@ class RawBatch(object):
         return self._moved(lambda t: t.to(device, non_blocking=non_blocking))
 
 
-def _identity_record(h, w):
-    return _records([{"src_w": w, "src_h": h, "crop": [0, 0, w, h], "res": None, "win": [0, 0, w, h], "flip": 0,
-                      "filter": _lib.WV_RESAMPLE_BILINEAR, "colour": []}])
+def _grouped(table, groups, maxima):
+    """groups[s]: the records of stage index s, a list of one-record arrays -> (the table's tensor of all of them, stage
+    index by stage index; one launch tuple per stage index: (first record, records, one maximum per entry of `maxima` -- a
+    field name, or a function of the group's records), all zero behind `first` where the group is empty).  Every group
+    passes the table's check here, on the host copy.  No record at all: (None, ())."""
+    if not any(groups):
+        return None, ()
+    launches, first, chunks = [], 0, []
+    for group in groups:
+        if not group:
+            launches.append((first, 0) + (0,) * len(maxima))
+            continue
+        g = np.concatenate(group)
+        table.require(g)
+        launches.append((first, len(g)) + tuple(int(g[m].max()) if isinstance(m, str) else m(g) for m in maxima))
+        first += len(g)
+        chunks.append(g)
+    return table.tensor(chunks), launches
+
+
+def _max_ksize(g):
+    return max(max(ksize(int(r["crop_w"]), int(r["res_w"]), int(r["filter"])),
+                   ksize(int(r["crop_h"]), int(r["res_h"]), int(r["filter"]))) for r in g)
 
 
 def pack(items):
@@ -340,7 +375,7 @@ def pack(items):
         if it.out_hw != (H, W):
             raise ValueError(f"raw_collate: images of one batch must be sized alike, got {it.out_hw} and {(H, W)}")
     B = len(items)
-    recs = [it.stages if len(it.stages) else _identity_record(*it.out_hw) for it in items]
+    recs = [it.stages if len(it.stages) else _records([_fresh_stage(*it.out_hw[::-1])]) for it in items]
     data_off, total = [], 0
     for it in items:
         data_off.append(total)
@@ -364,38 +399,13 @@ def pack(items):
                 per_stage.append([])
                 colour_per_stage.append([])
             per_stage[s].append(r)
-            col = getattr(items[i], "colour", None)
+            col = items[i].colour
             if col is not None and len(items[i].stages) and int(col["n_ops"][s]):
                 c = col[s:s + 1].copy()                     # the image the stage wrote: same place, same pitch
                 c["offset"], c["h"], c["w"], c["row_bytes"] = r["dst_offset"], r["out_h"], r["out_w"], r["dst_row_bytes"]
                 colour_per_stage[s].append(c)
-    launches, first, chunks = [], 0, []
-    for group in per_stage:
-        g = np.concatenate(group)
-        rc = check_records(g)
-        if rc != 0:
-            _lib.check(rc, "wv_image_size_check")
-        ks = max(max(ksize(int(r["crop_w"]), int(r["res_w"]), int(r["filter"])),
-                     ksize(int(r["crop_h"]), int(r["res_h"]), int(r["filter"]))) for r in g)
-        launches.append((first, len(g), int(g["out_h"].max()), int(g["out_w"].max()), ks))
-        first += len(g)
-        chunks.append(g)
-    desc = torch.from_numpy(np.concatenate(chunks).view(np.int32).reshape(-1, STAGE_WORDS).copy())
-    if not any(colour_per_stage):
-        return RawBatch(data, desc, launches, (B, H, W), work)
-    colour_launches, first, chunks = [], 0, []
-    for group in colour_per_stage:
-        if not group:
-            colour_launches.append((first, 0, 0, 0))
-            continue
-        g = np.concatenate(group)
-        rc = check_colour_records(g)
-        if rc != 0:
-            _lib.check(rc, "wv_colour_jitter_check")
-        colour_launches.append((first, len(g), int(g["h"].max()), int(g["w"].max())))
-        first += len(g)
-        chunks.append(g)
-    colour = torch.from_numpy(np.concatenate(chunks).view(np.int32).reshape(-1, COLOUR_WORDS).copy())
+    desc, launches = _grouped(STAGES, per_stage, ("out_h", "out_w", _max_ksize))
+    colour, colour_launches = _grouped(COLOURS, colour_per_stage, ("h", "w"))
     return RawBatch(data, desc, launches, (B, H, W), work, colour, colour_launches)
 
 

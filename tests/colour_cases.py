@@ -108,6 +108,53 @@ def run_cpu(lib, cases, dtype):
     return buf, rec
 
 
+EVAL_NODE = {"Resize": {"size": 256}, "CenterCrop": {"size": 224}, "SWTTransform": {"level": 1, "wavelet": "haar"}}
+
+
+def raw_batches():
+    """{name: RawBatch} of tests/golden/raw_batch_golden.npz: the VOC train node over five images (two stage indices, a
+    colour table), a plain eval node (no colour table), and a recordable image beside one whose log is not (two brightness
+    operations on one stage: PIL in the worker, an identity record in the batch)."""
+    import torch
+    from wvhash.transforms import build_transform, sizing
+    out = {}
+    tf = build_transform(voc_node(), defer=True, sizing="device")
+    torch.manual_seed(5)
+    out["voc"] = sizing.raw_collate([tf(Image.fromarray(image(*SIZES[i % 3], 60 + i))) for i in range(5)])
+    tf = build_transform(EVAL_NODE, defer=True, sizing="device")
+    out["eval"] = sizing.raw_collate([tf(Image.fromarray(image(w, h, 70 + w))) for w, h in ((61, 45), (45, 61), (50, 50))])
+    a, b = (sizing.LazyImage(Image.fromarray(image(61, 45, 80 + i))) for i in range(2))
+    a = a.resize((40, 30), Image.BICUBIC).colour("contrast", 0.75).transpose(Image.FLIP_LEFT_RIGHT)
+    b = b.colour("brightness", 1.25).colour("brightness", 0.75).resize((40, 30), Image.BILINEAR)
+    out["mixed"] = sizing.raw_collate([a.to_item(), b.to_item()])
+    return out
+
+
+def raw_batch_arrays(batches, data_limit=1 << 16):
+    """The batches as the arrays the golden file holds: `data` itself up to `data_limit` bytes, its SHA-256 beyond.  The
+    bytes between two images (16-byte alignment) are never written by the packer: they are zeroed here."""
+    import hashlib
+    from wvhash.transforms import sizing
+    out = {}
+    for name, rb in batches.items():
+        live = np.zeros(rb.data.numel(), bool)
+        for r in rb.desc.numpy().view(sizing.STAGE_DTYPE).reshape(-1)[:rb.launches[0][1]]:   # stage index 0 reads `data`
+            live[int(r["src_offset"]):int(r["src_offset"]) + int(r["src_h"]) * int(r["src_row_bytes"])] = True
+        data = np.where(live, rb.data.numpy(), 0).astype(np.uint8)
+        if data.size <= data_limit:
+            out[f"{name}_data"] = data
+        else:
+            out[f"{name}_data_sha256"] = np.array(hashlib.sha256(data.tobytes()).hexdigest())
+        out[f"{name}_desc"] = rb.desc.numpy()
+        out[f"{name}_colour"] = rb.colour.numpy() if rb.colour is not None else np.zeros((0, 12), np.int32)
+        out[f"{name}_has_colour"] = np.array(rb.colour is not None)
+        out[f"{name}_launches"] = np.array(rb.launches, np.int64).reshape(-1, 5)
+        out[f"{name}_colour_launches"] = np.array(rb.colour_launches, np.int64).reshape(-1, 4)
+        out[f"{name}_out_shape"] = np.array(rb.out_shape, np.int64)
+        out[f"{name}_work_bytes"] = np.array(rb.work_bytes, np.int64)
+    return out
+
+
 _ALL_COLOURS = None
 
 

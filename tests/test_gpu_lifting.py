@@ -41,6 +41,23 @@ def test_custom_transform_matches_oracle_and_keeps_the_callers_device(basis, lev
     assert ll.is_cuda and np.array_equal(ll.cpu().numpy(), lifting_np.custom_transform(x.numpy(), levels, basis, ll_only=True))
 
 
+def test_custom_transform_equals_the_composition_of_the_lifting_modules():
+    """CustomTransform's one batched call (wv_lift_images) returns the bits of the level cascade: zero pad, one
+    wv_lifting2d_forward per level (HaarLifting / Cdf97Lifting), the coarsest approximation stacked on its details.  Both
+    sides of both inputs are odd or no multiple of 4: every level pads."""
+    from wvhash.transforms import Cdf97Lifting, CustomTransform, HaarLifting
+    for basis, levels in [(b, n) for b in ("haar", "cdf97") for n in (1, 3)]:
+        for seed, shape in enumerate([(2, 3, 37, 50), (3, 19, 26)]):
+            x = torch.randn(shape, generator=torch.Generator().manual_seed(20 + seed))
+            approx, details = (HaarLifting if basis == "haar" else Cdf97Lifting)(n_levels=levels)(x.cuda())
+            full = CustomTransform(levels, basis)(x.cuda())
+            ll = CustomTransform(levels, basis, ll_only=True)(x.cuda())
+            assert full.is_cuda and torch.equal(full, torch.cat([approx[-1].unsqueeze(-3), details[-1]], -3)), (basis, levels, shape)
+            assert ll.is_cuda and torch.equal(ll, approx[-1]), (basis, levels, shape)
+            on_cpu = CustomTransform(levels, basis, device="cuda")(x)
+            assert not on_cpu.is_cuda and torch.equal(on_cpu, full.cpu()), (basis, levels, shape)
+
+
 def test_full_subbands_level1_and_errors_and_resize():
     from wvhash import _lib
     from wvhash.transforms import CustomTransform, ResizeSubBands

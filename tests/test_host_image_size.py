@@ -197,6 +197,21 @@ def test_raw_batch_collates_dict_items_and_moves_as_one():
     assert torch.equal(size_images_host(moved), size_images_host(rb)) and moved.launches == rb.launches
 
 
+def test_packed_batches_equal_the_stored_ones_byte_for_byte(golden_dir):
+    """raw_collate packs what it packed when tests/golden/raw_batch_golden.npz was written: every array and every tuple of
+    a VOC train batch (two stage indices, a colour table), an eval batch (no colour table) and a batch that mixes a recorded
+    image with one sized by PIL in the worker (identity record)."""
+    import colour_cases
+    g = np.load(os.path.join(golden_dir, "raw_batch_golden.npz"))
+    batches = colour_cases.raw_batches()
+    got = colour_cases.raw_batch_arrays(batches)
+    assert sorted(got) == sorted(g.files)
+    for key in g.files:
+        assert got[key].dtype == g[key].dtype and got[key].shape == g[key].shape and np.array_equal(got[key], g[key]), key
+    assert "voc_data_sha256" in g.files and "mixed_data" in g.files and bool(g["voc_has_colour"]) and not bool(g["eval_has_colour"])
+    assert len(batches["mixed"].launches) == 1 and batches["mixed"].colour_launches == ((0, 1, 30, 40),)
+
+
 class _Items(torch.utils.data.Dataset):
     def __init__(self, tf):
         self.tf = tf
