@@ -152,6 +152,32 @@ HT_INLINE void swt_plane(const float *x, float *out, int H, int W, int n, const 
     }
 }
 
+// plane x [H][W] -> out [H][W] = band `band` (0..3 = cA, cH, cV, cD) of level n: swt_plane with the last level's one row
+// filter and one column filter, every output by the same passes (same taps, same order) as its element of swt_plane
+template <bool FMA>
+HT_INLINE void swt_plane_band(const float *x, float *out, int band, int H, int W, int n, const Taps &t, Scratch &s)
+{
+    Taps row = t, col = t;                       // pass_rows / pass_cols apply `.lo` when given no second plane
+    if (band >= 2) memcpy(row.lo, t.hi, sizeof row.lo);
+    if (band & 1) memcpy(col.lo, t.hi, sizeof col.lo);
+    float *cur = s.a.data(), *nxt = s.b.data(), *rsel = s.c.data();
+    const float *src = x;
+    for (int l = 1; l < n; ++l) {
+        pass_rows<FMA>(src, cur, nullptr, H, W, t, 1 << (l - 1), s.pad.data());
+        src = cur;
+        float *tmp = cur; cur = nxt; nxt = tmp;
+    }
+    pass_rows<FMA>(src, rsel, nullptr, H, W, row, 1 << (n - 1), s.pad.data());
+    const float *p = rsel;
+    float *u = s.a.data(), *v = s.b.data();
+    for (int l = 1; l < n; ++l) {
+        pass_cols<FMA>(p, u, nullptr, H, W, t, 1 << (l - 1));
+        p = u;
+        float *tmp = u; u = v; v = tmp;
+    }
+    pass_cols<FMA>(p, out, nullptr, H, W, col, 1 << (n - 1));
+}
+
 HT_INLINE void load_plane(const void *in, int in_dtype, int in_layout, int b, int c, int C, int H, int W, float *dst)
 {
     const size_t hw = (size_t)H * W;
@@ -189,6 +215,34 @@ HT_INLINE void swt_all(const void *in, int in_dtype, int in_layout, float *out, 
             load_plane(in, in_dtype, in_layout, b, c, C, H, W, x.data());
             swt_plane<FMA>(x.data(), out + ((size_t)b * C + c) * 4 * hw, H, W, n, t, s);
         }
+}
+
+template <bool FMA>
+HT_INLINE void swt_band_all(const void *in, int in_dtype, int in_layout, float *out, int band, int B, int C, int H, int W,
+                            int n, const Taps &t)
+{
+    const size_t hw = (size_t)H * W;
+    Scratch s;
+    s.a.resize(hw); s.b.resize(hw); s.c.resize(hw);
+    s.pad.resize((size_t)W + (size_t)t.L * (1u << (n - 1)) * 2 + 8);
+    std::vector<float> x(hw);
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < C; ++c) {
+            load_plane(in, in_dtype, in_layout, b, c, C, H, W, x.data());
+            swt_plane_band<FMA>(x.data(), out + ((size_t)b * C + c) * hw, band, H, W, n, t, s);
+        }
+}
+
+__attribute__((target("avx2,fma"))) void swt_band_all_fma(const void *in, int in_dtype, int in_layout, float *out,
+                                                          int band, int B, int C, int H, int W, int n, const Taps &t)
+{
+    swt_band_all<true>(in, in_dtype, in_layout, out, band, B, C, H, W, n, t);
+}
+
+void swt_band_all_generic(const void *in, int in_dtype, int in_layout, float *out, int band, int B, int C, int H, int W,
+                          int n, const Taps &t)
+{
+    swt_band_all<false>(in, in_dtype, in_layout, out, band, B, C, H, W, n, t);
 }
 
 __attribute__((target("avx2,fma"))) void swt_all_fma(const void *in, int in_dtype, int in_layout, float *out, int B,
@@ -267,6 +321,27 @@ extern "C" int wv_swt2d_forward_cpu(const void *in, int in_dtype, int in_layout,
     try {
         if (cpu_has_fma()) swt_all_fma(in, in_dtype, in_layout, out, B, C, H, W, level, t);
         else swt_all_generic(in, in_dtype, in_layout, out, B, C, H, W, level, t);
+    } catch (const std::bad_alloc &) {
+        WV_FAIL(WV_ENOMEM, "swt (host): out of memory for the %dx%d scratch planes", H, W);
+    }
+    return WV_OK;
+}
+
+extern "C" int wv_swt2d_band_forward_cpu(const void *in, int in_dtype, int in_layout, float *out, int band, int B, int C,
+                                         int H, int W, int level, const float *dec_lo, const float *dec_hi, int flen)
+{
+    if (int rc = check_common(in, out, B, C, H, W, in_dtype, in_layout, "swt (host)")) return rc;
+    WV_REQUIRE(dec_lo && dec_hi && flen >= 1 && flen <= 32, "swt (host): 1..32 filter taps, got %d", flen);
+    WV_REQUIRE(level >= 1 && level <= 12, "swt (host): level %d out of range", level);
+    WV_REQUIRE((H % (1 << level)) == 0 && (W % (1 << level)) == 0,
+               "swt: H=%d, W=%d must be multiples of 2^level=%d (PyWavelets raises ValueError here)", H, W, 1 << level);
+    WV_REQUIRE(band >= 0 && band <= 3, "swt (host): band %d (0..3 = cA, cH, cV, cD)", band);
+    Taps t{};
+    t.L = flen;
+    for (int i = 0; i < flen; ++i) { t.lo[i] = dec_lo[i]; t.hi[i] = dec_hi[i]; }
+    try {
+        if (cpu_has_fma()) swt_band_all_fma(in, in_dtype, in_layout, out, band, B, C, H, W, level, t);
+        else swt_band_all_generic(in, in_dtype, in_layout, out, band, B, C, H, W, level, t);
     } catch (const std::bad_alloc &) {
         WV_FAIL(WV_ENOMEM, "swt (host): out of memory for the %dx%d scratch planes", H, W);
     }

@@ -613,6 +613,22 @@ extern "C" int wv_swt2d_forward_ex(const void *in, int in_dtype, int in_layout, 
     return swt_slide_launch(s, in, out, dec_lo, dec_hi, (hipStream_t)stream, WV_BANDS_OUTER, band_stride);
 }
 
+extern "C" int wv_swt2d_band_forward(const void *in, int in_dtype, int in_layout, void *out, int out_dtype, int band,
+                                     int B, int C, int H, int W, int level, const float *dec_lo, const float *dec_hi,
+                                     int flen, void *stream)
+{
+    const int rc = validate_swt_args(in, in_dtype, in_layout, out, out_dtype, B, C, H, W, level, dec_lo, dec_hi, flen);
+    if (rc != WV_OK) return rc;
+    WV_REQUIRE(band >= 0 && band <= 3, "swt: band %d (0..3 = cA, cH, cV, cD)", band);
+    // one band exists in the sliding kernel's scheme only (the shapes of the hot path); the caller slices the four-band
+    // result for anything else
+    const SwtShape s{B, C, H, W, level, flen, in_dtype, out_dtype, in_layout};
+    char why[160];
+    if (!slide_fits(s, why, sizeof why))
+        WV_FAIL(WV_ENOTSUP, "swt: single-band output is implemented by the sliding kernel only, which does not take %s", why);
+    return swt_band_launch(s, in, out, band, dec_lo, dec_hi, (hipStream_t)stream);
+}
+
 extern "C" int wv_rawstack_forward(const void *in, int in_dtype, int in_layout, void *out,
                                    int out_dtype, int B, int C, int H, int W, int copies,
                                    void *stream)

@@ -19,15 +19,6 @@
 
 namespace wv {
 
-// The one configuration every (taps, levels) instantiation uses: runs of R columns, TH rows per step, NT threads per
-// role (W <= NT), MINW workgroups per CU.
-constexpr int kSlideR = 16, kSlideTH = 16, kSlideNT = 256, kSlideMinW = 4;
-constexpr int kPitchPad = 4;      // LDS ring pitch = nrun * R + 4 floats
-// A/B on MI355X in one session, db2 level 3, 2048 images: consumer (column) waves at raised issue priority: 1.148 ms vs
-// 1.19 ms at equal priority (they are the critical role)
-constexpr int kConsumerPrio = 2;
-constexpr int kXcds = 8;          // workgroup w runs on XCD w % 8 (hardware round-robin)
-
 struct SlideGeom {
     int B, C, H, W;
     int P;          // ring pitch in floats
@@ -43,129 +34,6 @@ struct SlideGeom {
     unsigned long long *stamps;   // diagnostic build only
 };
 
-// Streaming form of the cascade for pass V: a thread keeps, per column, the last (L-1)*2^(l-1)
-// inputs of every level l in registers ("tails", HALO values in all), so each step costs exactly
-// L MACs per level per new row -- no halo recompute -- and emits outputs delayed by HALO rows.
-// The arithmetic per output is identical to Cascade (same taps, same order).
-// It runs on (row-lo, row-hi) PAIRS: the two row-filtered planes go through identical arithmetic, so the
-// consumer keeps them as 2-vectors and every multiply-add becomes one v_pk_fma_f32 -- half the instructions a
-// wave has to issue for the same (bitwise identical) result.  The LDS ring holds the planes interleaved.
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ f32x2 fma_s(float s, f32x2 x, f32x2 a)
-{
-    const f32x2 sv = {s, s};
-    return __builtin_elementwise_fma(sv, x, a);
-}
-
-template <int L, int NLEV, int N>
-struct VStep {
-    using T = f32x2;
-    static constexpr int HALO = (L - 1) * ((1 << NLEV) - 1);
-    // levels LEV .. NLEV-1: cur[] holds N new level-LEV inputs on entry, N new level-NLEV inputs on exit
-    template <int LEV>
-    static __device__ __forceinline__ void lower(T (&cur)[N], T (&tail)[HALO], const float (&lo)[L])
-    {
-        if constexpr (LEV < NLEV) {
-            constexpr int S = 1 << (LEV - 1), TT = (L - 1) * S, OFF = (L - 1) * (S - 1);
-            T seq[TT + N];
-#pragma unroll
-            for (int i = 0; i < TT; ++i) seq[i] = tail[OFF + i];
-#pragma unroll
-            for (int i = 0; i < N; ++i) seq[TT + i] = cur[i];
-#pragma unroll
-            for (int t = 0; t < N; ++t) {
-                T a = lo[0] * seq[t + S * (L - 1)];
-#pragma unroll
-                for (int m = 1; m < L; ++m) a = fma_s(lo[m], seq[t + S * (L - 1 - m)], a);
-                cur[t] = a;
-            }
-#pragma unroll
-            for (int i = 0; i < TT; ++i) tail[OFF + i] = seq[N + i];
-            lower<LEV + 1>(cur, tail, lo);
-        }
-    }
-    // last level: seq = tail ++ cur; out(t) for t < N; tail updated
-    template <typename Emit>
-    static __device__ __forceinline__ void last(const T (&cur)[N], T (&tail)[HALO], const float (&lo)[L],
-                                                const float (&hi)[L], Emit emit)
-    {
-        constexpr int S = 1 << (NLEV - 1), TT = (L - 1) * S, OFF = (L - 1) * (S - 1);
-        T seq[TT + N];
-#pragma unroll
-        for (int i = 0; i < TT; ++i) seq[i] = tail[OFF + i];
-#pragma unroll
-        for (int i = 0; i < N; ++i) seq[TT + i] = cur[i];
-#pragma unroll
-        for (int t = 0; t < N; ++t) {
-            T a = lo[0] * seq[t + S * (L - 1)], d = hi[0] * seq[t + S * (L - 1)];
-#pragma unroll
-            for (int m = 1; m < L; ++m) {
-                a = fma_s(lo[m], seq[t + S * (L - 1 - m)], a);
-                d = fma_s(hi[m], seq[t + S * (L - 1 - m)], d);
-            }
-            emit(t, a, d);
-        }
-#pragma unroll
-        for (int i = 0; i < TT; ++i) tail[OFF + i] = seq[N + i];
-    }
-    // warm-up: only refresh the last level's tail
-    static __device__ __forceinline__ void prime_last(const T (&cur)[N], T (&tail)[HALO])
-    {
-        constexpr int S = 1 << (NLEV - 1), TT = (L - 1) * S, OFF = (L - 1) * (S - 1);
-        T seq[TT + N];
-#pragma unroll
-        for (int i = 0; i < TT; ++i) seq[i] = tail[OFF + i];
-#pragma unroll
-        for (int i = 0; i < N; ++i) seq[TT + i] = cur[i];
-#pragma unroll
-        for (int i = 0; i < TT; ++i) tail[OFF + i] = seq[N + i];
-    }
-};
-
-// LAYOUT: 0 = NCHW, 1 = NHWC with C == 3.  One aligned 4-pixel group of channel c, raw.
-template <typename InT, int LAYOUT>
-struct SRaw {
-    uint32_t d[sizeof(InT) == 1 ? (LAYOUT == 1 ? 3 : 1) : 4];
-};
-
-// `img` = uniform base of the (b) image [NHWC] or of the (b, c) plane [NCHW]; off = lane offset in elements
-template <typename InT, int LAYOUT>
-__device__ __forceinline__ SRaw<InT, LAYOUT> s_fetch4(const InT *__restrict__ img, uint32_t pix, int c)
-{
-    SRaw<InT, LAYOUT> r;
-    if constexpr (sizeof(InT) == 1) {
-        if constexpr (LAYOUT == 0) {
-            r.d[0] = *reinterpret_cast<const uint32_t *>(img + pix);
-        } else {
-            const uint32_t *p = reinterpret_cast<const uint32_t *>(img + pix * 3u);
-            r.d[0] = p[0]; r.d[1] = p[1]; r.d[2] = p[2];
-        }
-    } else {
-        float4 v;
-        if constexpr (LAYOUT == 0) {
-            v = *reinterpret_cast<const float4 *>(img + pix);
-        } else {
-            const InT *p = img + pix * 3u + c;
-            v = make_float4(p[0], p[3], p[6], p[9]);
-        }
-        r.d[0] = __float_as_uint(v.x); r.d[1] = __float_as_uint(v.y);
-        r.d[2] = __float_as_uint(v.z); r.d[3] = __float_as_uint(v.w);
-    }
-    return r;
-}
-
-template <typename InT, int LAYOUT>
-__device__ __forceinline__ float4 s_convert4(const SRaw<InT, LAYOUT> &r, int c)
-{
-    if constexpr (sizeof(InT) == 1) {
-        if constexpr (LAYOUT == 1) return rgb4_to_unit(r.d[0], r.d[1], r.d[2], c);
-        else return u8x4_to_unit(r.d[0]);
-    } else {
-        return make_float4(__uint_as_float(r.d[0]), __uint_as_float(r.d[1]), __uint_as_float(r.d[2]),
-                           __uint_as_float(r.d[3]));
-    }
-}
-
 // Producer / consumer split inside one workgroup of 2 * NH threads:
 //   waves [NH/64, 2*NH/64)  "H waves": fetch the TH input rows of chunk k+1, filter them along x in
 //                           registers (all levels) and write lo / hi into LDS buffer (k+1) & 1
@@ -178,24 +46,6 @@ __device__ __forceinline__ float4 s_convert4(const SRaw<InT, LAYOUT> &r, int c)
 // STAMP = true is a diagnostic build (WV_SWT_STAMPS=1): per-wave s_memtime totals of the three segments of
 // each role go to g.stamps (never read by the kernel, never part of an output).
 #define WV_STAMP(var) do { if constexpr (STAMP) { __builtin_amdgcn_sched_barrier(0); var = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); } } while (0)
-// Store through "SGPR base + 32-bit lane offset" addressing (global_store ... saddr): the row pointer is
-// wave-uniform, so no per-store 64-bit vector address arithmetic is needed.  hipcc builds the address in
-// VGPRs for this pattern, hence the explicit instruction.  Only V waves store and they issue no vector
-// loads in their loop, so the compiler's vmcnt bookkeeping is unaffected.
-__device__ __forceinline__ void store_row(float *row_uniform, uint32_t byte_off, float v)
-{
-#ifdef WV_SWT_NOSTORE   // diagnostic build: arithmetic only (the store survives only for a value that never occurs)
-    if (__float_as_uint(v) == byte_off * 0x9E3779B1u + 0x7fc12345u)
-        *reinterpret_cast<float *>(reinterpret_cast<char *>(row_uniform) + byte_off) = v;
-    return;
-#endif
-    asm volatile("global_store_dword %0, %1, %2" : : "v"(byte_off), "v"(v), "s"(row_uniform) : "memory");
-}
-__device__ __forceinline__ void store_row(__hip_bfloat16 *row_uniform, uint32_t byte_off, __hip_bfloat16 v)
-{
-    *reinterpret_cast<__hip_bfloat16 *>(reinterpret_cast<char *>(row_uniform) + byte_off) = v;
-}
-
 template <int L, int NLEV, int R, int TH, int NH, int MINW, typename InT, int LAYOUT, bool BF16, bool STAMP = false>
 __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restrict__ in, void *__restrict__ out,
                                                             SlideGeom g, Taps<L> taps)
@@ -440,20 +290,6 @@ __global__ __launch_bounds__(2 * NH, MINW) void k_swt_slide(const InT *__restric
 // the consumers hold its rows in registers): bit-identical output, 1.22 ms and 1.16 ms against 1.08 ms for this kernel
 // (2048 images, back to back) -- polling waves and the shorter per-stage batches cost more than the barrier wait they
 // remove, which the second workgroup of the CU was already filling.  Removed; see DESIGN.md section 5.
-
-// LDS ring of width W: runs per row, pitch, bytes.  The planner (slide_fits) and the launch use this one computation.
-struct SlideRing {
-    int nrun, P;
-    size_t lds;
-};
-static SlideRing slide_ring(int W)
-{
-    SlideRing r;
-    r.nrun = (int)ceil_div(W, kSlideR);
-    r.P = r.nrun * kSlideR + kPitchPad;                         // multiple of 4; rows hold whole runs
-    r.lds = (size_t)2 * 2 * kSlideTH * r.P * sizeof(float);     // 2 buffers x 2 planes
-    return r;
-}
 
 // (taps, levels) with a sliding instantiation (swt_slide_launch): the shipped configs (haar L1 = c0, db2 L3 = c1), the other
 // levels of the 2- and 4-tap wavelets, and level 1 of the 8- and 10-tap wavelets the studies sweep (db4, bior4.4).

@@ -81,8 +81,10 @@ SIGNATURES = {
     "wv_swt2d_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "wv_swt2d_forward": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _fp, _fp, _i, _vp, _sz, _vp]),
     "wv_swt2d_forward_ex": (_i, [_vp, _i, _i, _vp, _i, _i, _i64, _i, _i, _i, _i, _i, _fp, _fp, _i, _vp, _sz, _vp]),
+    "wv_swt2d_band_forward": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _i, _vp]),
     "wv_rawstack_forward": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "wv_swt2d_forward_cpu": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _fp, _fp, _i]),
+    "wv_swt2d_band_forward_cpu": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _fp, _fp, _i]),
     "wv_rawstack_forward_cpu": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i]),
     "wv_dwt2d_forward_cpu": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _fp, _fp, _i]),
     "wv_pack_bits_cpu": (_i, [_vp, _i64, _vp, _i64, _i, _i, _vp]),

@@ -94,33 +94,64 @@ class _WaveletHashingBase(nn.Module):
         from ..transforms import SWTTransform
         return self.bind_transform(SWTTransform(level=level, wavelet=wavelet, defer=True))
 
-    def _band_major(self, x):
-        """-> [4, B, 3, H, W] (band-major; a view whenever the memory already lies that way).  A sizing.RawBatch (the
-        collated batch of a sizing="device" pipeline) is sized on the GPU first; its images are [B, H, W, 3]."""
+    def _raw_view(self, x):
+        """-> (x, channels_last): a sizing.RawBatch (the collated batch of a sizing="device" pipeline) sized on the GPU --
+        its images are [B, H, W, 3] -- and the [B,3,H,W] view of sized [B,H,W,3] images turned back, to be read in place."""
         from ..transforms.sizing import RawBatch
-        channels_last = False
         if isinstance(x, RawBatch):
-            x, channels_last = TF.size_images(x), True
-        elif x.dim() == 4 and x.shape[1] == 3 and not x.is_contiguous() and x.permute(0, 2, 3, 1).is_contiguous():
-            x, channels_last = x.permute(0, 2, 3, 1), True       # [B,3,H,W] view of sized [B,H,W,3] images: read in place
-        if x.dim() == 5:
-            return x.permute(2, 0, 1, 3, 4)
-        if x.dim() != 4:
-            raise ValueError(f"expected [B,3,4,H,W] sub-bands or a [B,3,H,W] image batch, got {tuple(x.shape)}")
-        tf = self._bound_transform
-        if tf is None:
+            return TF.size_images(x), True
+        if x.dim() == 4 and x.shape[1] == 3 and not x.is_contiguous() and x.permute(0, 2, 3, 1).is_contiguous():
+            return x.permute(0, 2, 3, 1), True
+        return x, False
+
+    def _transform_for_raw(self):
+        if self._bound_transform is None:
             raise RuntimeError(
                 "this model received a raw [B,3,H,W] image batch (a deferred transform's output) but no transform "
                 "is bound to it: call model.bind_transform(dataset.transform) (wvhash.engine.evaluate does) or "
                 "model.set_wavelet(level, wavelet); the wavelet is never guessed")
+        return self._bound_transform
+
+    @staticmethod
+    def _band_dtype():
+        """Under bf16 autocast the backbone's first op casts its input to bf16 anyway: the kernels emit bf16 directly."""
+        bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+        return torch.bfloat16 if bf16 else torch.float32
+
+    def _band_major(self, x):
+        """-> [4, B, 3, H, W] (band-major; a view whenever the memory already lies that way)."""
+        x, channels_last = self._raw_view(x)
+        if x.dim() == 5:
+            return x.permute(2, 0, 1, 3, 4)
+        if x.dim() != 4:
+            raise ValueError(f"expected [B,3,4,H,W] sub-bands or a [B,3,H,W] image batch, got {tuple(x.shape)}")
+        tf = self._transform_for_raw()
         from ..transforms import SWTTransform
         if isinstance(tf, SWTTransform):
-            # written band-major by the kernel: the band split below is a view, the sub-bands exist once in HBM.
-            # Under bf16 autocast the backbone's first op casts its input to bf16 anyway: emit bf16 directly.
-            bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+            # written band-major by the kernel: the band split below is a view, the sub-bands exist once in HBM
             return TF.swt2d(x, tf.wavelet, tf.level, band_major=True, channels_last=channels_last,
-                            out_dtype=torch.bfloat16 if bf16 else torch.float32)
+                            out_dtype=self._band_dtype())
         return tf.apply_batch(x, channels_last=channels_last).permute(2, 0, 1, 3, 4)
+
+    def _band(self, x, index, float_images=False):
+        """-> [B, 3, H, W]: band `index` of the input, what a single-band model feeds its backbone.  A 5-D sub-band
+        tensor gives the reference's view ``x[:, :, index]`` (detail_tester.py:36,100); a raw image batch goes through the
+        bound transform's ``apply_band`` -- for SWTTransform the single-band kernel, which computes that band alone.
+        ``float_images``: a float 4-D batch with no bound transform is already what the backbone reads (SingleBandNet's
+        ``if x.dim() == 5``); a raw uint8 batch never is."""
+        from ..transforms.sizing import RawBatch
+        if not isinstance(x, RawBatch):
+            if x.dim() == 5:
+                return x[:, :, index]
+            if x.dim() != 4:
+                raise ValueError(f"expected [B,3,4,H,W] sub-bands or a [B,3,H,W] image batch, got {tuple(x.shape)}")
+            if float_images and self._bound_transform is None and x.is_floating_point():
+                return x
+        tf = self._transform_for_raw()
+        channels_last = False
+        if not isinstance(x, RawBatch):          # apply_band sizes a RawBatch itself, as apply_batch does
+            x, channels_last = self._raw_view(x)
+        return tf.apply_band(x, index, channels_last=channels_last, out_dtype=self._band_dtype())
 
     def _tail(self, fused_embedding):
         host = not fused_embedding.is_cuda and getattr(self, "host_twin", False)      # explicit: model.host_twin = True

@@ -78,6 +78,12 @@ class BaseWaveletTransform(object):
         tensors the host twin.  A sizing.RawBatch (sizing="device") is sized first, where it lives."""
         raise NotImplementedError
 
+    def apply_band(self, batch, band, channels_last=False, out_dtype=torch.float32):
+        """One band of apply_batch as an image batch [B, 3, H', W']: what a single-band model reads
+        (detail_tester.py:36,100 ``x[:, :, detail_index]``).  The generic form transforms and slices; SWTTransform
+        computes the one band."""
+        return self.apply_batch(batch, channels_last=channels_last)[:, :, band].to(out_dtype).contiguous()
+
     def __call__(self, img):
         """The worker-side entry of every plugin: under device sizing the recorded image (fix_size included) becomes a
         RawItem; otherwise the pixels (_to_u8_hwc) are handed on as uint8 [C, H, W] when deferred, transformed when not."""
@@ -139,6 +145,12 @@ class SWTTransform(BaseWaveletTransform):
         if not batch.is_cuda:
             return F.swt2d_host(batch, self.wavelet, self.level, channels_last=channels_last)
         return F.swt2d(batch, self.wavelet, self.level, channels_last=channels_last, **kwargs)
+
+    def apply_band(self, batch, band, channels_last=False, out_dtype=torch.float32):
+        batch, channels_last = F.sized(batch, channels_last)
+        if not batch.is_cuda:
+            return F.swt2d_band_host(batch, self.wavelet, self.level, band, channels_last=channels_last).to(out_dtype)
+        return F.swt2d_band(batch, self.wavelet, self.level, band, channels_last=channels_last, out_dtype=out_dtype)
 
     def __repr__(self):
         return f"SWTTransform(shape='C,S,H,W', wavelet={self.wavelet}, level={self.level})"

@@ -125,12 +125,7 @@ def swt2d(x, wavelet="haar", level=1, channels_last=False, out_dtype=torch.float
     lib = _lib.require_gpu()
     x, layout, B, C, H, W = _batch(x, channels_last, "swt2d", True, " (swt2d_host is the host twin)")
     lo, hi = get_filters(wavelet)
-    if out_dtype == torch.float32:
-        odt = _lib.WV_DT_F32
-    elif out_dtype == torch.bfloat16:
-        odt = _lib.WV_DT_BF16
-    else:
-        raise TypeError("out_dtype must be float32 or bfloat16")
+    odt = _out_dtype(out_dtype)
     shape = (4, B, C, H, W) if band_major else (B, C, 4, H, W)
     if out is None:
         out = torch.empty(shape, dtype=out_dtype, device=x.device)
@@ -159,6 +154,48 @@ def swt2d(x, wavelet="haar", level=1, channels_last=False, out_dtype=torch.float
                                           b1 - b0, C, H, W, level, flo, fhi, len(lo), _lib.ptr(ws),
                                           ctypes.c_size_t(ws_bytes), _lib.stream_ptr())
                 _lib.check(rc, "wv_swt2d_forward")
+    return out
+
+
+def _out_dtype(out_dtype):
+    if out_dtype == torch.float32:
+        return _lib.WV_DT_F32
+    if out_dtype == torch.bfloat16:
+        return _lib.WV_DT_BF16
+    raise TypeError("out_dtype must be float32 or bfloat16")
+
+
+def swt2d_band(x, wavelet="haar", level=1, band=0, channels_last=False, out_dtype=torch.float32, out=None):
+    """Batch of images on the GPU -> [B, C, H, W]: band `band` (0..3 = cA, cH, cV, cD) of the level-`level` SWT, the
+    tensor a single-band model reads (detail_tester.py:36,100 ``x[:, :, detail_index]``), bit-identical to
+    ``swt2d(...)[:, :, band]``.  On the sliding kernel's shapes only that band is computed and written
+    (wv_swt2d_band_forward); any other shape is the four-band transform and a slice."""
+    lib = _lib.require_gpu()
+    x, layout, B, C, H, W = _batch(x, channels_last, "swt2d_band", True, " (swt2d_band_host is the host twin)")
+    lo, hi = get_filters(wavelet)
+    odt = _out_dtype(out_dtype)
+    band = int(band)
+    if not 0 <= band <= 3:
+        raise ValueError(f"swt2d_band: band must be 0..3 (cA, cH, cV, cD), got {band}")
+    shape = (B, C, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"swt2d_band: `out` must be a contiguous {list(shape)} tensor of out_dtype on the input's device")
+    if B == 0:
+        return out
+    _swt_size(H, W, level)
+    flo, fhi = _lib.host_floats(lo), _lib.host_floats(hi)
+    with torch.cuda.device(x.device):
+        for b0 in range(0, B, 65535):
+            b1 = min(B, b0 + 65535)
+            rc = lib.wv_swt2d_band_forward(_lib.ptr(x[b0:b1]), _in_dtype(x), layout, _lib.ptr(out[b0:b1]), odt, band,
+                                           b1 - b0, C, H, W, level, flo, fhi, len(lo), _lib.stream_ptr())
+            if rc == _lib.WV_ENOTSUP:     # shape outside the sliding kernel -> all four bands, sliced once
+                inner = swt2d(x, wavelet, level, channels_last=channels_last, out_dtype=out_dtype)
+                out.copy_(inner[:, :, band])
+                return out
+            _lib.check(rc, "wv_swt2d_band_forward")
     return out
 
 
@@ -301,6 +338,25 @@ def swt2d_host(x, wavelet="haar", level=1, channels_last=False):
     rc = lib.wv_swt2d_forward_cpu(_lib.ptr(x), _in_dtype(x), layout, _lib.ptr(out), B, C, H, W, level,
                                   _lib.host_floats(lo), _lib.host_floats(hi), len(lo))
     _lib.check(rc, "wv_swt2d_forward_cpu")
+    return out
+
+
+def swt2d_band_host(x, wavelet="haar", level=1, band=0, channels_last=False):
+    """Host twin of swt2d_band (wv_swt2d_band_forward_cpu) -> float32 [B,C,H,W], bit-identical to
+    ``swt2d_host(...)[:, :, band]``."""
+    lib = _lib.load()
+    x, layout, B, C, H, W = _batch(x, channels_last, "swt2d_band_host", False, _HOST_NOTE)
+    lo, hi = get_filters(wavelet)
+    band = int(band)
+    if not 0 <= band <= 3:
+        raise ValueError(f"swt2d_band_host: band must be 0..3 (cA, cH, cV, cD), got {band}")
+    out = torch.empty((B, C, H, W), dtype=torch.float32)
+    if B == 0:
+        return out
+    _swt_size(H, W, level)
+    rc = lib.wv_swt2d_band_forward_cpu(_lib.ptr(x), _in_dtype(x), layout, _lib.ptr(out), band, B, C, H, W, level,
+                                       _lib.host_floats(lo), _lib.host_floats(hi), len(lo))
+    _lib.check(rc, "wv_swt2d_band_forward_cpu")
     return out
 
 

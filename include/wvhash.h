@@ -59,6 +59,7 @@ const char *wv_last_error(void);
  * wv_colour_ops): 86 symbols.
  * So was the batched lifting tail (wv_lift_images[_workspace_bytes], wv_lift_images_cpu, wv_lift_images_check,
  * wv_lift_out_size, wv_lift_images_tile): 92 symbols.
+ * So was the single-band SWT (wv_swt2d_band_forward, wv_swt2d_band_forward_cpu): 94 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -92,6 +93,18 @@ int wv_swt2d_forward_ex(const void *in, int in_dtype, int in_layout, void *out, 
                         int64_t band_stride, int B, int C, int H, int W, int level, const float *dec_lo,
                         const float *dec_hi, int flen, void *workspace, size_t workspace_bytes, void *stream);
 
+/* One band of the same transform as a plain image batch: what a single-band model reads
+ *   (main/models/detail_tester.py:36,100: x[:, :, detail_index, :, :]) without the other three bands being
+ *   computed or written.
+ * band: 0..3 = cA, cH, cV, cD -- the order wv_swt2d_forward writes, the reference's detail_index.
+ * out : [B][C][H][W], f32 or bf16.  Every element equals the same element of wv_swt2d_forward's band bit for bit.
+ * Implemented for the shapes of the sliding kernel (the hot path) only: any other shape returns WV_ENOTSUP, the
+ * message quoting the rule the shape breaks, and the caller slices wv_swt2d_forward's result.  No workspace.
+ * Arguments are checked on the host before anything touches the GPU: band outside 0..3 -> WV_EINVAL. */
+int wv_swt2d_band_forward(const void *in, int in_dtype, int in_layout, void *out, int out_dtype, int band,
+                          int B, int C, int H, int W, int level, const float *dec_lo, const float *dec_hi,
+                          int flen, void *stream);
+
 /* RawStackTransform (custom_transforms.py:172-188): `copies` identical planes per channel.
  * out: [B][C][copies][H][W]. */
 int wv_rawstack_forward(const void *in, int in_dtype, int in_layout, void *out, int out_dtype,
@@ -108,6 +121,10 @@ int wv_rawstack_forward(const void *in, int in_dtype, int in_layout, void *out, 
  * ------------------------------------------------------------------------------------------ */
 int wv_swt2d_forward_cpu(const void *in, int in_dtype, int in_layout, float *out, int B, int C, int H, int W,
                          int level, const float *dec_lo, const float *dec_hi, int flen);
+/* Host twin of wv_swt2d_band_forward: out is float32 [B][C][H][W]; every shape wv_swt2d_forward_cpu covers, each
+ * element equal to the same element of its band bit for bit. */
+int wv_swt2d_band_forward_cpu(const void *in, int in_dtype, int in_layout, float *out, int band,
+                              int B, int C, int H, int W, int level, const float *dec_lo, const float *dec_hi, int flen);
 int wv_rawstack_forward_cpu(const void *in, int in_dtype, int in_layout, float *out, int B, int C, int H, int W,
                             int copies);
 int wv_dwt2d_forward_cpu(const void *in, int in_dtype, int in_layout, float *out, int B, int C, int H, int W,
