@@ -96,6 +96,7 @@ extern "C" int wv_dwt2d_forward(const void *in, int in_dtype, int in_layout, flo
     WV_REQUIRE(level >= 1 && level <= 12, "dwt: level %d out of range", level);
     WV_REQUIRE(flen >= 2 && flen <= 32, "dwt: %d taps (supported: 2..32)", flen);
     WV_REQUIRE(in_dtype == WV_DT_U8 || in_dtype == WV_DT_F32, "dwt: input dtype %d", in_dtype);
+    WV_REQUIRE(in_layout == WV_LAYOUT_NCHW || in_layout == WV_LAYOUT_NHWC, "dwt: bad layout %d", in_layout);
     const size_t need = wv_dwt2d_workspace_bytes(B, C, H, W, level, flen);
     if (!workspace || workspace_bytes < need) WV_FAIL(WV_ENOMEM, "dwt: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;

@@ -636,6 +636,7 @@ extern "C" int wv_rawstack_forward(const void *in, int in_dtype, int in_layout, 
     WV_REQUIRE(in && out, "rawstack: null buffer");
     WV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && copies > 0, "rawstack: bad shape");
     WV_REQUIRE(out_dtype == WV_DT_F32, "rawstack: only f32 output");
+    WV_REQUIRE(in_layout == WV_LAYOUT_NCHW || in_layout == WV_LAYOUT_NHWC, "rawstack: bad layout %d", in_layout);
     hipStream_t st = (hipStream_t)stream;
     const size_t total = (size_t)B * C * H * W;
     const int grid = grid_for(total);

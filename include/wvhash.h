@@ -106,7 +106,7 @@ int wv_swt2d_band_forward(const void *in, int in_dtype, int in_layout, void *out
                           int flen, void *stream);
 
 /* RawStackTransform (custom_transforms.py:172-188): `copies` identical planes per channel.
- * out: [B][C][copies][H][W]. */
+ * out: [B][C][copies][H][W].  in_layout other than WV_LAYOUT_NCHW / WV_LAYOUT_NHWC -> WV_EINVAL, before any launch. */
 int wv_rawstack_forward(const void *in, int in_dtype, int in_layout, void *out, int out_dtype,
                         int B, int C, int H, int W, int copies, void *stream);
 
@@ -152,7 +152,9 @@ int wv_hit_prefix_cpu(const int32_t *idx, int Q, int k, const uint64_t *qlab, co
 
 /* Decimated multi-level 2-D DWT (DWTTransform, custom_transforms.py:191-205 -> pywt.wavedec2, mode
  * 'symmetric'): the four bands (cA, cH, cV, cD) of the coarsest level.
- * out: float32 [B][C][4][Hn][Wn] with Hn = wv_dwt_out_len(H, flen, level) (each level: floor((n + flen - 1) / 2)). */
+ * out: float32 [B][C][4][Hn][Wn] with Hn = wv_dwt_out_len(H, flen, level) (each level: floor((n + flen - 1) / 2)).
+ * Arguments are checked on the host before any launch: level outside 1..12, flen outside 2..32, an unknown dtype or
+ * layout -> WV_EINVAL; a workspace smaller than wv_dwt2d_workspace_bytes reports -> WV_ENOMEM. */
 int wv_dwt_out_len(int n, int flen, int level);
 size_t wv_dwt2d_workspace_bytes(int B, int C, int H, int W, int level, int flen);
 int wv_dwt2d_forward(const void *in, int in_dtype, int in_layout, float *out, int B, int C, int H, int W,

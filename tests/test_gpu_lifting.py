@@ -58,6 +58,22 @@ def test_custom_transform_equals_the_composition_of_the_lifting_modules():
             assert not on_cpu.is_cuda and torch.equal(on_cpu, full.cpu()), (basis, levels, shape)
 
 
+def test_lifting_stride_loops_serve_what_the_capped_grid_leaves():
+    """[9, 2048, 2048]: 9 * 1024 * 2048 = 18.9M pairs per pass against the 65536 x 256 = 16,777,216 threads k_lift_rows and
+    k_lift_cols are capped at.  Planes 0..7 fill the first round exactly, so plane 8 is served by the second alone.  The
+    first, the last of the first round and plane 8 against the oracle, bit for bit."""
+    from wvhash.transforms import HaarLifting
+    P, H, W = 9, 2048, 2048
+    assert (P - 1) * (H // 2) * W == (1 << 16) * 256
+    x = torch.randn((P, H, W), generator=torch.Generator().manual_seed(31))
+    approx, details = HaarLifting(n_levels=1)(x.cuda())
+    full = torch.cat([approx[-1].unsqueeze(-3), details[-1]], -3)
+    assert full.is_cuda and tuple(full.shape) == (P, 4, H // 2, W // 2)
+    for p in (0, 7, 8):
+        ref = lifting_np.custom_transform(x[p].numpy(), 1, "haar")
+        assert np.array_equal(full[p].cpu().numpy().view(np.int32), ref.view(np.int32)), p
+
+
 def test_full_subbands_level1_and_errors_and_resize():
     from wvhash import _lib
     from wvhash.transforms import CustomTransform, ResizeSubBands

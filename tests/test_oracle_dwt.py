@@ -1,10 +1,47 @@
 """CPU: the numpy restatement of DWTTransform's arithmetic (pywt.wavedec2, mode 'symmetric';
-reference custom_transforms.py:197-201) against analytic known answers.  Parity unpinned against
-PyWavelets itself (not installed here, no fixtures in the reference)."""
+reference custom_transforms.py:197-201) against analytic known answers, and against the float64 reference of
+tests/dwt_cases.py, which writes PyWavelets' documented definition of the 'symmetric' decimating convolution with numpy's
+pad / convolve and no index arithmetic.  Parity with that documented definition is pinned; parity with PyWavelets'
+executed output stays unpinned (it is not a dependency, and the reference holds no fixtures of it)."""
 import numpy as np
 import pytest
 
+import dwt_cases as D
 from oracle import swt_np
+
+PIN_TAPS = {2: "haar", 4: "db2", 8: "db4", 10: "bior4.4", 20: "db10", 32: "rand32"}
+PIN_SIZES = list(range(1, 24)) + [37, 64]        # every n < F for all but the 32 taps (there: 1..23), where the reflection repeats
+
+
+def _pin_tol(ref):
+    return 1e-12 * max(1.0, float(np.abs(ref).max()))
+
+
+@pytest.mark.parametrize("F", sorted(PIN_TAPS))
+def test_dwt_axis_float64_is_the_pad_and_convolve_definition(F):
+    rng = np.random.default_rng(F)
+    lo, hi = (t.astype(np.float64) for t in D.taps32(PIN_TAPS[F]))
+    assert len(lo) == F
+    for n in PIN_SIZES:
+        for axis, shape in ((0, (n, 3)), (1, (2, n))):
+            x = rng.uniform(-1, 1, shape)
+            for f in (lo, hi):
+                got, ref = swt_np.dwt_axis(x, f, axis, np.float64), D.ref_axis(x, f, axis)
+                assert got.shape == ref.shape and got.shape[axis] == (n + F - 1) // 2, (F, n, axis)
+                assert np.abs(got - ref).max() <= _pin_tol(ref), (F, n, axis)
+
+
+@pytest.mark.parametrize("F", sorted(PIN_TAPS))
+def test_wavedec2_coarsest_float64_is_the_pad_and_convolve_definition(F):
+    rng = np.random.default_rng(100 + F)
+    taps = D.taps32(PIN_TAPS[F])
+    for k, (h, w) in enumerate(zip(PIN_SIZES, PIN_SIZES[::-1])):
+        x = rng.uniform(-1, 1, (h, w))
+        for level in ((1, 3) if k % 4 == 0 else (1,)):
+            got = swt_np.wavedec2_coarsest(x, taps, level, np.float64)
+            ref = np.stack(D.ref_wavedec2(x, taps, level))
+            assert got.shape == ref.shape == (4, D.out_len(h, F, level), D.out_len(w, F, level)), (F, h, w, level)
+            assert np.abs(got - ref).max() <= _pin_tol(ref), (F, h, w, level)
 
 
 def test_haar_is_2x2_block_transform():
