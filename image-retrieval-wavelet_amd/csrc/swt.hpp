@@ -1,6 +1,8 @@
-// 2-D SWT: the device helpers its kernels share and the host interface of each implementation.
+// 2-D SWT: the device helpers all its kernels share (cascades, wrapping, pixel conversion), the table of instantiated
+// (taps, levels) and the host interface of each implementation.
 //   swt_slide.hip : sliding-window persistent kernel, full-width rows (the hot path)
 //   swt_band.hip  : the same scheme for ONE band written as a plain image batch (single-band models)
+//   swt_slide.hpp : the body of that scheme, which only those two include (roles, plane schedule, launch rule)
 //   swt_fused.hip : register-fused two-pass kernel over tiles
 //   swt.hip       : tiled 2n-pass LDS kernel, generic per-level kernels, the planner and the entry points
 #pragma once
@@ -44,46 +46,6 @@ struct Cascade {
         float a = f[0] * v[i + S * (L - 1)];
 #pragma unroll
         for (int m = 1; m < L; ++m) a = fmaf(f[m], v[i + S * (L - 1 - m)], a);
-        return a;
-    }
-};
-
-// The same cascade for a line cut into runs of R outputs, one run per lane, when every lane of the wave runs it together.
-// The stencil is one-sided -- level l output i reads inputs i .. i + (L-1)*2^(l-1) -- so a run OWNS outputs 0 .. R-1 of
-// every level below the last and takes the (L-1)*2^l values the next level reads past them from the run to its right
-// (ds_bpermute through `right`, a lane byte address): every level value is computed once per line instead of once per
-// run that reads it.  w[] holds R + L-1 inputs on entry; lower() leaves the R + (L-1)*2^(NLEV-1) inputs of the last
-// level.  Each output keeps the taps and their order of Cascade, so it keeps its bits.
-template <int L, int NLEV, int R>
-struct RunCascade {
-    static constexpr int NPIX = R + (L - 1);
-    static constexpr int NW = R + (L - 1) * (1 << (NLEV - 1));
-    static_assert((L - 1) * (1 << (NLEV - 1)) < R, "a level's halo must come from one neighbouring run");
-
-    template <int LEV>
-    static __device__ __forceinline__ void lower(float (&w)[NW], const float (&lo)[L], int right)
-    {
-        if constexpr (LEV < NLEV) {
-            constexpr int S = 1 << (LEV - 1);
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                float a = lo[0] * w[i + S * (L - 1)];
-#pragma unroll
-                for (int m = 1; m < L; ++m) a = fmaf(lo[m], w[i + S * (L - 1 - m)], a);
-                w[i] = a;
-            }
-#pragma unroll
-            for (int i = 0; i < 2 * S * (L - 1); ++i)
-                w[R + i] = __int_as_float(__builtin_amdgcn_ds_bpermute(right, __float_as_int(w[i])));
-            lower<LEV + 1>(w, lo, right);
-        }
-    }
-    static __device__ __forceinline__ float last(const float (&w)[NW], const float (&f)[L], int i)
-    {
-        constexpr int S = 1 << (NLEV - 1);
-        float a = f[0] * w[i + S * (L - 1)];
-#pragma unroll
-        for (int m = 1; m < L; ++m) a = fmaf(f[m], w[i + S * (L - 1 - m)], a);
         return a;
     }
 };
@@ -136,181 +98,6 @@ __device__ __forceinline__ float4 rgb4_to_unit(uint32_t d0, uint32_t d1, uint32_
                        u8_to_unit(ubyte<1>(s2)));
 }
 
-// ------------------------------------------------------------------------------- sliding kernels
-// What k_swt_slide (swt_slide.hip, four bands) and k_swt_band (swt_band.hip, one band) share.
-// The one configuration every (taps, levels) instantiation uses: runs of R columns, TH rows per step, NT threads per
-// role (W <= NT), MINW workgroups per CU.
-constexpr int kSlideR = 16, kSlideTH = 16, kSlideNT = 256, kSlideMinW = 4;
-constexpr int kPitchPad = 4;      // LDS ring pitch = nrun * R + 4 floats
-// A/B on MI355X in one session, db2 level 3, 2048 images: consumer (column) waves at raised issue priority: 1.148 ms vs
-// 1.19 ms at equal priority (they are the critical role)
-constexpr int kConsumerPrio = 2;
-constexpr int kXcds = 8;          // workgroup w runs on XCD w % 8 (hardware round-robin)
-
-// Streaming form of the cascade for pass V: a thread keeps, per column, the last (L-1)*2^(l-1)
-// inputs of every level l in registers ("tails", HALO values in all), so each step costs exactly
-// L MACs per level per new row -- no halo recompute -- and emits outputs delayed by HALO rows.
-// The arithmetic per output is identical to Cascade (same taps, same order).
-// It runs on (row-lo, row-hi) PAIRS: the two row-filtered planes go through identical arithmetic, so the
-// consumer keeps them as 2-vectors and every multiply-add becomes one v_pk_fma_f32 -- half the instructions a
-// wave has to issue for the same (bitwise identical) result.  The LDS ring holds the planes interleaved.
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ f32x2 fma_s(float s, f32x2 x, f32x2 a)
-{
-    const f32x2 sv = {s, s};
-    return __builtin_elementwise_fma(sv, x, a);
-}
-__device__ __forceinline__ float fma_s(float s, float x, float a) { return fmaf(s, x, a); }
-
-// The single-band kernel (swt_band.hip) runs the same cascade on one plane: V = float, last1() for its one column filter.
-template <int L, int NLEV, int N, typename V = f32x2>
-struct VStep {
-    using T = V;
-    static constexpr int HALO = (L - 1) * ((1 << NLEV) - 1);
-    // levels LEV .. NLEV-1: cur[] holds N new level-LEV inputs on entry, N new level-NLEV inputs on exit
-    template <int LEV>
-    static __device__ __forceinline__ void lower(T (&cur)[N], T (&tail)[HALO], const float (&lo)[L])
-    {
-        if constexpr (LEV < NLEV) {
-            constexpr int S = 1 << (LEV - 1), TT = (L - 1) * S, OFF = (L - 1) * (S - 1);
-            T seq[TT + N];
-#pragma unroll
-            for (int i = 0; i < TT; ++i) seq[i] = tail[OFF + i];
-#pragma unroll
-            for (int i = 0; i < N; ++i) seq[TT + i] = cur[i];
-#pragma unroll
-            for (int t = 0; t < N; ++t) {
-                T a = lo[0] * seq[t + S * (L - 1)];
-#pragma unroll
-                for (int m = 1; m < L; ++m) a = fma_s(lo[m], seq[t + S * (L - 1 - m)], a);
-                cur[t] = a;
-            }
-#pragma unroll
-            for (int i = 0; i < TT; ++i) tail[OFF + i] = seq[N + i];
-            lower<LEV + 1>(cur, tail, lo);
-        }
-    }
-    // last level: seq = tail ++ cur; out(t) for t < N; tail updated
-    template <typename Emit>
-    static __device__ __forceinline__ void last(const T (&cur)[N], T (&tail)[HALO], const float (&lo)[L],
-                                                const float (&hi)[L], Emit emit)
-    {
-        constexpr int S = 1 << (NLEV - 1), TT = (L - 1) * S, OFF = (L - 1) * (S - 1);
-        T seq[TT + N];
-#pragma unroll
-        for (int i = 0; i < TT; ++i) seq[i] = tail[OFF + i];
-#pragma unroll
-        for (int i = 0; i < N; ++i) seq[TT + i] = cur[i];
-#pragma unroll
-        for (int t = 0; t < N; ++t) {
-            T a = lo[0] * seq[t + S * (L - 1)], d = hi[0] * seq[t + S * (L - 1)];
-#pragma unroll
-            for (int m = 1; m < L; ++m) {
-                a = fma_s(lo[m], seq[t + S * (L - 1 - m)], a);
-                d = fma_s(hi[m], seq[t + S * (L - 1 - m)], d);
-            }
-            emit(t, a, d);
-        }
-#pragma unroll
-        for (int i = 0; i < TT; ++i) tail[OFF + i] = seq[N + i];
-    }
-    // last level of one band: the one column filter f, same taps in the same order
-    template <typename Emit>
-    static __device__ __forceinline__ void last1(const T (&cur)[N], T (&tail)[HALO], const float (&f)[L], Emit emit)
-    {
-        constexpr int S = 1 << (NLEV - 1), TT = (L - 1) * S, OFF = (L - 1) * (S - 1);
-        T seq[TT + N];
-#pragma unroll
-        for (int i = 0; i < TT; ++i) seq[i] = tail[OFF + i];
-#pragma unroll
-        for (int i = 0; i < N; ++i) seq[TT + i] = cur[i];
-#pragma unroll
-        for (int t = 0; t < N; ++t) {
-            T a = f[0] * seq[t + S * (L - 1)];
-#pragma unroll
-            for (int m = 1; m < L; ++m) a = fma_s(f[m], seq[t + S * (L - 1 - m)], a);
-            emit(t, a);
-        }
-#pragma unroll
-        for (int i = 0; i < TT; ++i) tail[OFF + i] = seq[N + i];
-    }
-    // warm-up: only refresh the last level's tail
-    static __device__ __forceinline__ void prime_last(const T (&cur)[N], T (&tail)[HALO])
-    {
-        constexpr int S = 1 << (NLEV - 1), TT = (L - 1) * S, OFF = (L - 1) * (S - 1);
-        T seq[TT + N];
-#pragma unroll
-        for (int i = 0; i < TT; ++i) seq[i] = tail[OFF + i];
-#pragma unroll
-        for (int i = 0; i < N; ++i) seq[TT + i] = cur[i];
-#pragma unroll
-        for (int i = 0; i < TT; ++i) tail[OFF + i] = seq[N + i];
-    }
-};
-
-// LAYOUT: 0 = NCHW, 1 = NHWC with C == 3.  One aligned 4-pixel group of channel c, raw.
-template <typename InT, int LAYOUT>
-struct SRaw {
-    uint32_t d[sizeof(InT) == 1 ? (LAYOUT == 1 ? 3 : 1) : 4];
-};
-
-// `img` = uniform base of the (b) image [NHWC] or of the (b, c) plane [NCHW]; off = lane offset in elements
-template <typename InT, int LAYOUT>
-__device__ __forceinline__ SRaw<InT, LAYOUT> s_fetch4(const InT *__restrict__ img, uint32_t pix, int c)
-{
-    SRaw<InT, LAYOUT> r;
-    if constexpr (sizeof(InT) == 1) {
-        if constexpr (LAYOUT == 0) {
-            r.d[0] = *reinterpret_cast<const uint32_t *>(img + pix);
-        } else {
-            const uint32_t *p = reinterpret_cast<const uint32_t *>(img + pix * 3u);
-            r.d[0] = p[0]; r.d[1] = p[1]; r.d[2] = p[2];
-        }
-    } else {
-        float4 v;
-        if constexpr (LAYOUT == 0) {
-            v = *reinterpret_cast<const float4 *>(img + pix);
-        } else {
-            const InT *p = img + pix * 3u + c;
-            v = make_float4(p[0], p[3], p[6], p[9]);
-        }
-        r.d[0] = __float_as_uint(v.x); r.d[1] = __float_as_uint(v.y);
-        r.d[2] = __float_as_uint(v.z); r.d[3] = __float_as_uint(v.w);
-    }
-    return r;
-}
-
-template <typename InT, int LAYOUT>
-__device__ __forceinline__ float4 s_convert4(const SRaw<InT, LAYOUT> &r, int c)
-{
-    if constexpr (sizeof(InT) == 1) {
-        if constexpr (LAYOUT == 1) return rgb4_to_unit(r.d[0], r.d[1], r.d[2], c);
-        else return u8x4_to_unit(r.d[0]);
-    } else {
-        return make_float4(__uint_as_float(r.d[0]), __uint_as_float(r.d[1]), __uint_as_float(r.d[2]),
-                           __uint_as_float(r.d[3]));
-    }
-}
-
-// Store through "SGPR base + 32-bit lane offset" addressing (global_store ... saddr): the row pointer is
-// wave-uniform, so no per-store 64-bit vector address arithmetic is needed.  hipcc builds the address in
-// VGPRs for this pattern, hence the explicit instruction.  Only V waves store and they issue no vector
-// loads in their loop, so the compiler's vmcnt bookkeeping is unaffected.
-__device__ __forceinline__ void store_row(float *row_uniform, uint32_t byte_off, float v)
-{
-#ifdef WV_SWT_NOSTORE   // diagnostic build: arithmetic only (the store survives only for a value that never occurs)
-    if (__float_as_uint(v) == byte_off * 0x9E3779B1u + 0x7fc12345u)
-        *reinterpret_cast<float *>(reinterpret_cast<char *>(row_uniform) + byte_off) = v;
-    return;
-#endif
-    asm volatile("global_store_dword %0, %1, %2" : : "v"(byte_off), "v"(v), "s"(row_uniform) : "memory");
-}
-__device__ __forceinline__ void store_row(__hip_bfloat16 *row_uniform, uint32_t byte_off, __hip_bfloat16 v)
-{
-    *reinterpret_cast<__hip_bfloat16 *>(reinterpret_cast<char *>(row_uniform) + byte_off) = v;
-}
-
-
 // ------------------------------------------------------------------------------- host side
 // One call of wv_swt2d_forward[_ex]: L taps, `level` levels, WV_DT_* dtypes, WV_LAYOUT_* input layout.
 struct SwtShape {
@@ -318,19 +105,15 @@ struct SwtShape {
     int in_dtype, out_dtype, in_layout;
 };
 
-// LDS ring of width W holding `planes` row-filtered planes (2: lo and hi, the four-band kernel; 1: the single-band
-// kernel): runs per row, pitch, bytes.  The planner (slide_fits) and the launches use this one computation.
-struct SlideRing {
-    int nrun, P;
-    size_t lds;
-};
-inline SlideRing slide_ring(int W, int planes = 2)
+// The (taps, levels) the sliding and the register-fused kernels are instantiated for, X(taps, levels) once per pair: the shipped
+// configs (db2 L3 = c1, haar L1 = c0), the other levels of 2 and 4 taps, level 1 of the 8 and 10 taps the studies sweep (db4, bior4.4).
+#define WV_SWT_CONFIGS(X) X(4, 3) X(2, 1) X(4, 1) X(4, 2) X(2, 2) X(2, 3) X(8, 1) X(10, 1)
+inline bool swt_config(int L, int n)
 {
-    SlideRing r;
-    r.nrun = (int)ceil_div(W, kSlideR);
-    r.P = r.nrun * kSlideR + kPitchPad;                         // multiple of 4; rows hold whole runs
-    r.lds = (size_t)2 * planes * kSlideTH * r.P * sizeof(float);   // 2 buffers x planes
-    return r;
+#define WV_IS(LL, NN) if (L == LL && n == NN) return true;
+    WV_SWT_CONFIGS(WV_IS)
+#undef WV_IS
+    return false;
 }
 
 // The sliding kernel computes the shape.  On false, `why` (if given) receives the rule the shape breaks.

@@ -156,23 +156,18 @@ static int pick_shape(const void *in, void *out, const FusedGeom &g, const float
     return launch_fused<L, NLEV, 16, 4, 32, InT>(in, out, g, lo, hi, st);
 }
 
-// the (taps, levels) instantiated below; any width W % 4 == 0, any height, dtype and layout
+// the (taps, levels) of WV_SWT_CONFIGS (swt.hpp); any width W % 4 == 0, any height, dtype and layout
 bool fused_fits(const SwtShape &s)
 {
-    const int L = s.L, n = s.level;
-    return (((L == 2 || L == 4) && n >= 1 && n <= 3) || ((L == 8 || L == 10) && n == 1)) && s.W % 4 == 0;
+    return swt_config(s.L, s.level) && s.W % 4 == 0;
 }
 
 template <typename InT>
 static int pick_filter(int L, int n, const void *in, void *out, const FusedGeom &g, const float *lo,
                        const float *hi, hipStream_t st)
 {
-#define WV_CASE(LL, NN) \
-    if (L == LL && n == NN) return pick_shape<LL, NN, InT>(in, out, g, lo, hi, st)
-    WV_CASE(2, 1); WV_CASE(2, 2); WV_CASE(2, 3);
-    WV_CASE(4, 1); WV_CASE(4, 2); WV_CASE(4, 3);
-    WV_CASE(8, 1);
-    WV_CASE(10, 1);
+#define WV_CASE(LL, NN) if (L == LL && n == NN) return pick_shape<LL, NN, InT>(in, out, g, lo, hi, st);
+    WV_SWT_CONFIGS(WV_CASE)
 #undef WV_CASE
     WV_FAIL(WV_ENOTSUP, "swt fused: %d taps at level %d", L, n);   // unreachable after fused_fits()
 }

@@ -1,9 +1,9 @@
 """Shared by tests/test_swt_schedule_cases.py (no GPU) and tests/test_gpu_swt_schedule.py: the sliding SWT kernel's window
-and plane schedule restated in plain Python (csrc/swt_slide.hip: slide_fits, launch_slide, the `q` loops of k_swt_slide),
+and plane schedule restated in plain Python (csrc/swt_slide.hip: slide_fits; csrc/swt_slide.hpp: slide_launch, PlaneSchedule),
 the case tables that make a launch persistent on a device of `cu` compute units, seeded inputs in the five forms the
 kernel reads, and the C oracle applied plane by plane.
 
-The schedule: launch_slide starts grid = min(planes, 2 * cu) workgroups.  With 8 | grid (a persistent launch rounds the
+The schedule: slide_launch starts grid = min(planes, 2 * cu) workgroups.  With 8 | grid (a persistent launch rounds the
 grid down to that) image b belongs to XCD b % 8, whose planes are dealt in (image, channel) order to its grid / 8
 workgroups, each looping q = wg_in_xcd, wg_in_xcd + grid / 8, ...; otherwise workgroup w takes planes w, w + grid, ....
 """
@@ -13,7 +13,7 @@ import numpy as np
 
 TAPS = {"haar": 2, "db2": 4, "db4": 8, "bior4.4": 10}
 TH = 16                 # rows per chunk (kSlideTH)
-WGS_PER_CU = 2          # per_cu of launch_slide for every width the kernel takes
+WGS_PER_CU = 2          # per_cu of slide_launch for every width the kernel takes
 XCDS = 8
 SHIPPED = [("haar", 1), ("db2", 3)]
 OTHERS = [("haar", 2), ("haar", 3), ("db2", 1), ("db2", 2), ("db4", 1), ("bior4.4", 1)]

@@ -12,9 +12,10 @@ from wvhash.transforms import swt2d, swt2d_band, swt2d_band_host
 pytestmark = pytest.mark.gpu
 
 # (wavelet, level, H, W): db2 L3 at W = 40 (W % 16 != 0: strided producer loads) and W = 48 (coalesced producer loads of
-# planar uint8); W = 256 is the widest row the kernel takes
+# planar uint8, 4 taps); haar and db4 at W = 48 take the 2- and 8-tap pixel windows of the coalesced producer through the
+# single-band stage; W = 256 is the widest row the kernel takes
 SHAPES = [("haar", 1, 40, 40), ("haar", 3, 40, 40), ("db2", 3, 64, 40), ("db2", 3, 64, 48), ("db4", 1, 40, 40),
-          ("bior4.4", 1, 40, 40), ("db2", 2, 40, 256)]
+          ("bior4.4", 1, 40, 40), ("db2", 2, 40, 256), ("haar", 1, 40, 48), ("db4", 1, 40, 48)]
 B, C = 3, 3
 
 
@@ -39,8 +40,8 @@ def test_band_equals_four_band_kernel(wl, lev, H, W, out_dtype):
 
 @pytest.mark.parametrize("wl,lev,H,W,rem", [("db2", 3, 64, 48, 5), ("haar", 1, 40, 40, 0)])
 def test_persistent_launch_every_plane(wl, lev, H, W, rem):
-    """More planes than workgroups.  launch_band (csrc/swt_band.hip) starts min(planes, 2 * CUs) workgroups -- two per CU
-    by the occupancy the kernel is compiled for, the LDS ring allowing more -- rounded down to a multiple of 8; B is the
+    """More planes than workgroups.  slide_launch (csrc/swt_slide.hpp, the launch rule k_swt_band shares with k_swt_slide)
+    starts min(planes, 2 * CUs) workgroups -- two per CU by the occupancy the kernel is compiled for, the LDS ring allowing more -- rounded down to a multiple of 8; B is the
     smallest batch with B % 8 == rem and 3 * B >= 2.3 * 2 * CUs, so every workgroup loops over two or three planes and
     (rem = 5) the XCDs own different numbers of images.  Every plane is compared."""
     cu = torch.cuda.get_device_properties(0).multi_processor_count

@@ -1,7 +1,8 @@
-"""The plane schedule of the sliding SWT kernel (csrc/swt_slide.hip): every plane of a launch, not a sample of them.
+"""The plane schedule of the sliding SWT kernel (csrc/swt_slide.hip; PlaneSchedule, csrc/swt_slide.hpp): every plane of a
+launch, not a sample of them.
 
-launch_slide starts min(planes, 2 * CUs) workgroups.  With more planes than that a workgroup loops over several planes of
-its XCD and reuses the LDS ring, the producer's prefetch and the barrier pairing from one plane to the next; with a plane
+slide_launch (csrc/swt_slide.hpp) starts min(planes, 2 * CUs) workgroups.  With more planes than that a workgroup loops
+over several planes of its XCD and reuses the LDS ring, the producer's prefetch and the barrier pairing from one plane to the next; with a plane
 count that is a multiple of 8 the images are dealt to the 8 XCDs even when those own unequal numbers of them or none.  The
 batches here (tests/swt_schedule_cases.py, checked without a GPU by tests/test_swt_schedule_cases.py) give every workgroup
 two or three planes with unequal XCD shares, at heights of both parities of the chunk count, for every (taps, level) the
