@@ -549,7 +549,11 @@ int wv_band_attn_pool(const wv_head_params *p, const float *feats, int B, float 
                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* logits = fused @ hash_w.T (+ hash_b); BN(eval); codes = sign(logits) as fp32 and bit-packed.
- * Any of logits_out / codes_out / packed_out may be NULL.  bn_* NULL = no BatchNorm. */
+ * Any of logits_out / codes_out / packed_out may be NULL.  bn_* NULL = no BatchNorm.
+ *   - codes is +1, -1, or 0.0 for a logit of exactly zero; a NaN logit is passed through as NaN.
+ *   - the packed bit is logit > 0, so a zero and a NaN logit both pack as 0 (wv_pack_bits in mode 0 flags those codes).
+ *   - packed_out is [B][ceil(nbits / 64)] words; the pad bits of the last word above nbits are 0.
+ *   - E % 4 == 0, E >= 4, 4 E bytes <= 48 KB, nbits >= 1 (WV_EINVAL otherwise, checked before any launch); B = 0 writes nothing. */
 int wv_hash_tail(const float *fused, int B, int E, const float *hash_w, const float *hash_b,
                  const float *bn_w, const float *bn_b, const float *bn_mean, const float *bn_var,
                  float bn_eps, int nbits, float *logits_out, float *codes_out,
@@ -559,7 +563,8 @@ int wv_hash_tail(const float *fused, int B, int E, const float *hash_w, const fl
  * prepared are ignored; no stream, no workspace; csrc/host_head.cpp) for a model whose tensors live on the host.  fp32 with
  * a machine-independent summation order (eight interleaved fmaf chains, one fixed tree); they agree with the kernels to
  * fp32 rounding (both are held to the reference-made golden vectors with the same tolerance), the codes wherever the
- * logit is not within that of zero. */
+ * logit is not within that of zero.  wv_hash_tail_cpu follows the rules of wv_hash_tail for zero and NaN logits, the packed bit
+ * and the pad bits; it needs E % 8 == 0 (the kernels: E % 4 == 0) and returns WV_EINVAL otherwise. */
 int wv_band_attn_pool_cpu(const wv_head_params *p, const float *feats, int B, float *out);
 int wv_hash_tail_cpu(const float *fused, int B, int E, const float *hash_w, const float *hash_b, const float *bn_w,
                      const float *bn_b, const float *bn_mean, const float *bn_var, float bn_eps, int nbits,
