@@ -170,6 +170,9 @@ SIGNATURES = {
     "wv_lift_images_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "wv_lift_images": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "wv_lift_images_cpu": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _i, _i, _i, _vp]),
+    "wv_group_layernorm_check": (_i, [_i, _i, _i64, _i64, _i, _i]),
+    "wv_group_layernorm": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i, _i, _vp, _vp, _f, _vp]),
+    "wv_group_layernorm_cpu": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i, _i, _vp, _vp, _f]),
 }
 
 _LIB = None

@@ -1,6 +1,6 @@
 """Wavelet-band hashing models: class names, kwargs and state_dict keys of
 /root/reference/main/models/multi_dino_attention.py (SharedDinoHashing :792-833,
-MultiDinoHashing :716-750).
+MultiDinoHashing :716-750, PromptedSharedDinoHashing :835-899).
 
 Only the tail of these models is on the accelerated path: band split -> [ViT] ->
 fusion head (HIP/MFMA) -> hash_fc -> BatchNorm1d -> sign -> bit-pack (HIP).  The DINOv2 backbone
@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..transforms import functional as TF
+from .dsln import inject_domain_specific_layernorms
 from .fusion import get_fusion_head
 
 
@@ -226,6 +227,53 @@ class MultiDinoHashing(_WaveletHashingBase):
         bands = self._band_major(x)                      # bands[i] = x[..., i, :, :] (:745)
         features = [_cls(backbone(bands[i])) for i, backbone in enumerate(self.backbones)]
         return self.fusion_head(features)
+
+    def forward(self, x):
+        return self._tail(self.fused_embedding(x))
+
+
+class PromptedSharedDinoHashing(_WaveletHashingBase):
+    """The prompt-tuned shared backbone (multi_dino_attention.py:835-899): ``num_prompts`` learned tokens per band between
+    the CLS token and the patch tokens.  ``backbone_config['use_dsln']`` swaps every LayerNorm of the backbone for a
+    MultiDomainLayerNorm (one LayerNorm per band); without gradients those run the grouped LayerNorm kernel, and the block
+    norms -- whose only readers are the qkv / fc1 Linears -- emit bf16 under bf16 autocast (``emit_dtype = "auto"``).  The
+    final norm keeps the stock dtype: the fusion head reads it."""
+
+    def __init__(self, backbone_config, fusion_config, binary_config, num_prompts=10, backbone=None, **kwargs):
+        super().__init__()
+        self.shared_backbone = backbone if backbone is not None else load_dinov2(backbone_config['name'])
+        self.use_dsln = backbone_config.get('use_dsln', False)
+        if self.use_dsln:
+            self.shared_backbone = inject_domain_specific_layernorms(self.shared_backbone, num_domains=4)
+            for blk in self.shared_backbone.blocks:
+                blk.norm1.emit_dtype = blk.norm2.emit_dtype = "auto"
+        if backbone_config.get('frozen', True):
+            for p in self.shared_backbone.parameters():
+                p.requires_grad = False
+            self.shared_backbone.eval()
+            self.shared_backbone.train = lambda mode=False: None
+        embed_dim = self.shared_backbone.embed_dim
+        self.num_prompts = num_prompts
+        self.prompts = nn.Parameter(torch.randn(4, num_prompts, embed_dim) * 0.02)
+        self.fusion_head = get_fusion_head(fusion_config, [embed_dim] * 4)
+        self.nbits = binary_config['nbits']
+        self.bn = nn.BatchNorm1d(self.nbits)
+        self.hash_fc = nn.Linear(fusion_config['output_dim'], self.nbits, bias=False)
+        nn.init.normal_(self.hash_fc.weight, std=0.01)
+
+    def _train_output(self, logits):
+        return torch.tanh(logits)
+
+    def fused_embedding(self, x):
+        bands = self._band_major(x)                      # [4, B, 3, H, W]
+        s, b, c, h, w = bands.shape
+        x_tokens = self.shared_backbone.prepare_tokens_with_masks(bands.reshape(s * b, c, h, w))
+        prompts = self.prompts.unsqueeze(1).expand(-1, b, -1, -1).reshape(s * b, self.num_prompts, -1)
+        tokens = torch.cat([x_tokens[:, 0:1, :], prompts, x_tokens[:, 1:, :]], dim=1)
+        for blk in self.shared_backbone.blocks:
+            tokens = blk(tokens)
+        tokens = self.shared_backbone.norm(tokens)
+        return self.fusion_head(list(tokens[:, 0].chunk(4, dim=0)))
 
     def forward(self, x):
         return self._tail(self.fused_embedding(x))

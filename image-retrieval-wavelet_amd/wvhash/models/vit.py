@@ -76,9 +76,16 @@ class ViT(nn.Module):
         self.blocks = nn.ModuleList([_Block(embed_dim, num_heads) for _ in range(depth)])
         self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
 
-    def forward(self, x):
+    def prepare_tokens_with_masks(self, x, masks=None):
+        """[B, 3, H, W] -> [B, 1 + patches, E]: patch embedding, CLS token, position embedding (DINOv2's method of that name;
+        this stand-in has no mask token, so ``masks`` must be None)."""
+        if masks is not None:
+            raise NotImplementedError("wvhash.models.vit.ViT has no mask token")
         x = self.patch_embed(x)
-        x = torch.cat([self.cls_token.expand(x.shape[0], -1, -1), x], dim=1) + self.pos_embed
+        return torch.cat([self.cls_token.expand(x.shape[0], -1, -1), x], dim=1) + self.pos_embed
+
+    def forward(self, x):
+        x = self.prepare_tokens_with_masks(x)
         for blk in self.blocks:
             x = blk(x)
         x = self.norm(x)

@@ -60,6 +60,7 @@ const char *wv_last_error(void);
  * So was the batched lifting tail (wv_lift_images[_workspace_bytes], wv_lift_images_cpu, wv_lift_images_check,
  * wv_lift_out_size, wv_lift_images_tile): 92 symbols.
  * So was the single-band SWT (wv_swt2d_band_forward, wv_swt2d_band_forward_cpu): 94 symbols.
+ * So was the grouped LayerNorm (wv_group_layernorm, wv_group_layernorm_cpu, wv_group_layernorm_check): 97 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -711,6 +712,26 @@ int wv_colour_jitter(uint8_t *img, const wv_colour_ops *ops, int n, int max_h, i
                      size_t workspace_bytes, void *stream);
 int wv_colour_jitter_cpu(uint8_t *img, const wv_colour_ops *ops, int n);
 int wv_colour_jitter_check(const wv_colour_ops *ops, int n);
+
+/* ------------------------------------------------------------------------------------------
+ * Grouped LayerNorm: MultiDomainLayerNorm.forward of main/models/multi_dino_attention.py:922-929 -- x.chunk(G, 0), one
+ * nn.LayerNorm per chunk, torch.cat -- as one pass.  Restated in csrc/group_layernorm.hpp.
+ * x, out: [N][T][E], tightly packed, WV_DT_F32 or WV_DT_BF16 each (any pairing); out must not be x.  gamma, beta: [G][E] fp32.
+ * Sequence n takes gamma / beta of group n / ceil(N / G): torch.chunk, including N % G != 0 and N < G (fewer groups in use).
+ * Per row, in fp32: mean, biased variance of the centred values, 1 / sqrt(var + eps), ((x - mean) * rstd) * gamma + beta;
+ * bf16 is widened on load and rounded to nearest even on store.  Any E >= 1; E % 4 == 0 moves 16 bytes (fp32) or 8 bytes
+ * (bf16) per lane.  N * T == 0: WV_OK, nothing touched (pointers may be NULL).
+ * wv_group_layernorm       DEVICE pointers; one launch on `stream`, no workspace, no hidden synchronisation.
+ * wv_group_layernorm_cpu   host twin (HOST pointers): the kernel's order of sums replayed, equal to it bit for bit.
+ * wv_group_layernorm_check the argument check both run first: WV_EINVAL for an unknown dtype, N < 0, T < 0, E < 1, G < 1;
+ *                          WV_ENOTSUP for more than 4 * (2^31 - 1) rows.  Both entry points then refuse (WV_EINVAL) a NULL
+ *                          x / out / gamma / beta and out == x; every message names the argument.
+ * ------------------------------------------------------------------------------------------ */
+int wv_group_layernorm_check(int x_dtype, int out_dtype, int64_t N, int64_t T, int E, int G);
+int wv_group_layernorm(const void *x, int x_dtype, void *out, int out_dtype, int64_t N, int64_t T, int E, int G,
+                       const float *gamma, const float *beta, float eps, void *stream);
+int wv_group_layernorm_cpu(const void *x, int x_dtype, void *out, int out_dtype, int64_t N, int64_t T, int E, int G,
+                           const float *gamma, const float *beta, float eps);
 
 #ifdef __cplusplus
 }
