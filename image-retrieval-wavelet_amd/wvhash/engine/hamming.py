@@ -8,6 +8,10 @@ import ctypes
 import torch
 
 from .. import _lib
+from ._args import INDEX, PITCH, ROWS, WRITTEN, anchor, gate, same_device
+
+_DEVICE_TYPE = "cuda"            # where every tensor argument of this module lives (_pack alone moves its input there)
+_I64, _I32, _I16, _U8 = torch.int64, torch.int32, torch.int16, torch.uint8
 
 
 def _words(nbits):
@@ -18,9 +22,8 @@ def _pack(src, mode, check, what):
     lib = _lib.require_gpu()
     if src.dim() != 2:
         raise ValueError(f"{what}: expected a 2-D tensor, got {tuple(src.shape)}")
-    src = src.to(device=_device_of(src), dtype=torch.float32)
-    if src.stride(1) != 1:
-        src = src.contiguous()
+    src = src.to(device=_device_of(src), dtype=torch.float32)       # the one wrapper that moves and converts what it is given
+    src = gate(src, what, "values", torch.float32, src.device, (None, None), PITCH)
     rows, nbits = src.shape
     out = torch.empty((rows, _words(nbits)), dtype=torch.int64, device=src.device)
     flag = torch.zeros(1, dtype=torch.int32, device=src.device) if check else None
@@ -58,6 +61,7 @@ def pack_labels(labels, check=True):
 
 def bit_counts(packed, nbits):
     lib = _lib.require_gpu()
+    packed = gate(packed, "bit_counts", "packed", _I64, anchor(packed, "bit_counts", "packed", _DEVICE_TYPE), (None, _words(nbits)))
     counts = torch.empty(nbits, dtype=torch.int32, device=packed.device)
     with torch.cuda.device(packed.device):
         rc = lib.wv_bit_counts(_lib.ptr(packed), packed.shape[0], nbits, _lib.ptr(counts), _lib.stream_ptr())
@@ -76,9 +80,8 @@ class PreparedDB:
 
     def __init__(self, db_packed, nbits=None, _virtual=True):
         lib = _lib.require_gpu()
-        if db_packed.dim() != 2 or db_packed.dtype != torch.int64:
-            raise ValueError("PreparedDB: expected packed int64 codes [N, words] (see pack_codes)")
-        self.packed = db_packed.contiguous()
+        self.packed = gate(db_packed, "PreparedDB", "db_packed (packed int64 codes [N, words], see pack_codes)", _I64,
+                           anchor(db_packed, "PreparedDB", "db_packed", _DEVICE_TYPE), (None, None))
         self.N, self.words = self.packed.shape
         self.nbits = nbits if nbits is not None else self.words * 64
         nbytes = lib.wv_db_prepared_bytes(self.N, self.words)
@@ -108,15 +111,26 @@ class PreparedDB:
         return self.packed.device
 
 
+def _db_arg(what, db, device):
+    """`db` of the ranking wrappers: a PreparedDB on the anchor device or packed int64 codes [N, words]
+    -> (prepared, the PreparedDB or the gated tensor, N, words)"""
+    if isinstance(db, PreparedDB):
+        same_device(db, what, "db", device)
+        return True, db, db.N, db.words
+    db = gate(db, what, "db", _I64, device, (None, None))
+    return False, db, db.shape[0], db.shape[1]
+
+
 def hamming_dist(q_packed, db, nbits=None):
     """-> uint8 [Q, N] view (row pitch padded to 64 bytes so every row store is 16-B aligned).
     `db`: packed int64 codes [N, words] or a PreparedDB.  Distances are bytes: codes of more than 255 bits could
     reach 256 (complementary codes), which would wrap to 0 -- refused; `nbits` tells a 193..255-bit code
     (4 words, fine) from a 256-bit one."""
     lib = _lib.require_gpu()
+    dev = anchor(q_packed, "hamming_dist", "q_packed", _DEVICE_TYPE)
+    q_packed = gate(q_packed, "hamming_dist", "q_packed", _I64, dev, (None, None))
     Q, words = q_packed.shape
-    prepared = isinstance(db, PreparedDB)
-    N, dwords = (db.N, db.words) if prepared else db.shape
+    prepared, db, N, dwords = _db_arg("hamming_dist", db, dev)
     if dwords != words:
         raise ValueError("hamming_dist: query and database code widths differ")
     if nbits is None:
@@ -156,9 +170,10 @@ def hamming_topk(q_packed, db, nbits, k, idx_offset=0, workspace=None, want_dist
     -> (idx int32 [Q,k], dist uint8 [Q,k] or None)   [+ cum int32 [Q, nbits+2] when want_cum:
     cum[q, b] = number of rows with distance < b]."""
     lib = _lib.require_gpu()
+    dev = anchor(q_packed, "hamming_topk", "q_packed", _DEVICE_TYPE)
+    q_packed = gate(q_packed, "hamming_topk", "q_packed", _I64, dev, (None, None))
     Q, words = q_packed.shape
-    prepared, N = _shard_db_args(db, words, nbits, "hamming_topk")
-    dev = q_packed.device
+    prepared, db, N = _shard_db_args(db, words, nbits, "hamming_topk", dev)
     if prepared and db.parts and not want_cum and nbits <= 128 and Q:
         got = _virtual_shards_topk(q_packed, db, nbits, k, idx_offset, want_dist)
         if got is not None:                                 # None: a prefix beyond the windowed kernel's lists -- rank the whole database
@@ -169,7 +184,7 @@ def hamming_topk(q_packed, db, nbits, k, idx_offset=0, workspace=None, want_dist
     blob = db.blob if prepared and words <= 2 else None     # the ranking images exist for codes of <= 2 words
     ws = None
     if blob is None:                                        # the kernel's image of the database is made per call
-        ws = (workspace or TopkWorkspace()).get(lib.wv_hamming_topk_workspace_bytes(Q, N, words, k), dev)
+        ws = _workspace("hamming_topk", workspace, lib.wv_hamming_topk_workspace_bytes(Q, N, words, k), dev)
     with torch.cuda.device(dev):
         rc = lib.wv_hamming_topk_ex(_lib.ptr(q_packed), _lib.ptr(db.packed if prepared else db), _lib.ptr(blob), _lib.ptr(idx),
                                     _lib.ptr(dist), _lib.ptr(cum), Q, N, nbits, k, idx_offset, _lib.ptr(ws),
@@ -210,25 +225,34 @@ def _virtual_shards_topk(q_packed, db, nbits, k, idx_offset, want_dist):
     return idx, (dist if want_dist else None)
 
 
-def _shard_db_args(db, words, nbits, what):
-    prepared = isinstance(db, PreparedDB)
-    N, dwords = (db.N, db.words) if prepared else db.shape
+def _shard_db_args(db, words, nbits, what, device):
+    prepared, db, N, dwords = _db_arg(what, db, device)
     if dwords != words or words != _words(nbits):
         raise ValueError(f"{what}: code widths do not match nbits")
-    return prepared, N
+    return prepared, db, N
+
+
+def _workspace(what, workspace, nbytes, device):
+    """The scratch of a call on an unprepared database: the caller's TopkWorkspace (grown as needed) or one for this call.
+    A buffer the caller's workspace already holds is written as it stands: bytes, contiguous, on the anchor device."""
+    workspace = workspace or TopkWorkspace()
+    if workspace.buf is not None:
+        gate(workspace.buf, what, "workspace", _U8, device, (None,), WRITTEN)
+    return gate(workspace.get(nbytes, device), what, "workspace", _U8, device, (None,), WRITTEN)
 
 
 def _shard_step(what, q_packed, db, nbits, k, workspace, want_rows, want_cum):
     """One call of the sharded search's kernel on one shard -> (rows int16 [Q, k] or None, cum int32 [Q, nbits + 2] or None)."""
     lib = _lib.require_gpu()
+    dev = anchor(q_packed, what, "q_packed", _DEVICE_TYPE)
+    q_packed = gate(q_packed, what, "q_packed", _I64, dev, (None, None))
     Q, words = q_packed.shape
-    prepared, N = _shard_db_args(db, words, nbits, what)
-    dev = q_packed.device
+    prepared, db, N = _shard_db_args(db, words, nbits, what, dev)
     rows = torch.empty((Q, k), dtype=torch.int16, device=dev) if want_rows else None
     cum = torch.empty((Q, nbits + 2), dtype=torch.int32, device=dev) if want_cum else None
     ws = None
     if not prepared:
-        ws = (workspace or TopkWorkspace()).get(lib.wv_hamming_topk_workspace_bytes(Q, N, words, max(k, 1)), dev)
+        ws = _workspace(what, workspace, lib.wv_hamming_topk_workspace_bytes(Q, N, words, max(k, 1)), dev)
     src = (None if prepared else _lib.ptr(db), _lib.ptr(db.blob) if prepared else None)
     tail = (_lib.ptr(ws), ctypes.c_size_t(ws.numel() if ws is not None else 0), _lib.stream_ptr())
     with torch.cuda.device(dev):
@@ -262,8 +286,10 @@ def hamming_shard_prefix(q_packed, db, nbits, k, workspace=None):
 def topk_merge(idx_in, dist_in, k, nbits):
     """[G,Q,kin] per-shard lists (contiguous row shards in rank order) -> global [Q,k]."""
     lib = _lib.require_gpu()
+    dev = anchor(idx_in, "topk_merge", "idx_in", _DEVICE_TYPE)
+    idx_in = gate(idx_in, "topk_merge", "idx_in", INDEX, dev, (None, None, None))
     G, Q, kin = idx_in.shape
-    idx_in, dist_in = idx_in.contiguous(), dist_in.contiguous()
+    dist_in = gate(dist_in, "topk_merge", "dist_in", _U8, dev, (G, Q, kin))
     idx = torch.empty((Q, k), dtype=torch.int32, device=idx_in.device)
     dist = torch.empty((Q, k), dtype=torch.uint8, device=idx_in.device)
     with torch.cuda.device(idx_in.device):
@@ -279,15 +305,17 @@ def topk_merge_cum(idx_local, cum, shard_rows, k, nbits, need_out=None):
     need_out: int32 [1] device tensor (zeroed by the caller) that receives the longest prefix any shard had to contribute
     for any of these queries -- the lists are exact iff it is <= kin."""
     lib = _lib.require_gpu()
+    dev = anchor(idx_local, "topk_merge_cum", "idx_local", _DEVICE_TYPE)
+    idx_local = gate(idx_local, "topk_merge_cum", "idx_local", _I16, dev, (None, None, None))
     G, Q, kin = idx_local.shape
-    if idx_local.dtype != torch.int16 or cum.dtype != torch.int32 or tuple(cum.shape) != (G, Q, nbits + 2):
-        raise ValueError("topk_merge_cum: expected int16 [G,Q,kin] local indices and int32 [G,Q,nbits+2] histograms")
-    idx_local, cum = idx_local.contiguous(), cum.contiguous()
+    cum = gate(cum, "topk_merge_cum", "cum", _I32, dev, (G, Q, nbits + 2))
+    if need_out is not None:
+        need_out = gate(need_out, "topk_merge_cum", "need_out", _I32, dev, (1,), WRITTEN)
     idx = torch.empty((Q, k), dtype=torch.int32, device=idx_local.device)
     dist = torch.empty((Q, k), dtype=torch.uint8, device=idx_local.device)
     with torch.cuda.device(idx_local.device):
         rc = lib.wv_topk_merge_cum_need(_lib.ptr(idx_local), _lib.ptr(cum), G, Q, kin, shard_rows, _lib.ptr(idx),
-                                        _lib.ptr(dist), k, nbits, _lib.ptr(need_out) if need_out is not None else None,
+                                        _lib.ptr(dist), k, nbits, _lib.ptr(need_out),
                                         _lib.stream_ptr())
         _lib.check(rc, "wv_topk_merge_cum_need")
     return idx, dist
@@ -295,9 +323,9 @@ def topk_merge_cum(idx_local, cum, shard_rows, k, nbits, need_out=None):
 
 def rank_from_dist(dist_matrix, nbits, k):
     lib = _lib.require_gpu()
+    dist_matrix = gate(dist_matrix, "rank_from_dist", "dist_matrix", _U8, anchor(dist_matrix, "rank_from_dist", "dist_matrix", _DEVICE_TYPE),
+                       (None, None), PITCH)
     Q, N = dist_matrix.shape
-    if dist_matrix.stride(1) != 1:
-        dist_matrix = dist_matrix.contiguous()
     idx = torch.empty((Q, k), dtype=torch.int32, device=dist_matrix.device)
     dist = torch.empty((Q, k), dtype=torch.uint8, device=dist_matrix.device)
     with torch.cuda.device(dist_matrix.device):
@@ -321,17 +349,32 @@ def _ap_buffers(Q, tail, device):
     return torch.empty((Q,) + tail, dtype=torch.float32, device=device), torch.empty((Q,) + tail, dtype=torch.int32, device=device)
 
 
+def _list_args(what, idx, qlab_packed, dblab_packed, kind, device_type=None):
+    """The arguments of the wrappers that walk ranked lists: idx [Q, k] (int32; int64 is converted), one row of packed label
+    words per list, the database rows' label words of the same width -> (idx, qlab_packed, dblab_packed, label words), gated."""
+    dev = anchor(idx, what, "idx", device_type or _DEVICE_TYPE)
+    idx = gate(idx, what, "idx", INDEX, dev, (None, None), kind)
+    qlab_packed, dblab_packed, lw = _label_args(what, qlab_packed, dblab_packed, idx.shape[0], dev)
+    return idx, qlab_packed, dblab_packed, lw
+
+
+def _label_args(what, qlab_packed, dblab_packed, Q, dev):
+    qlab_packed = gate(qlab_packed, what, "qlab_packed", _I64, dev, (Q, None))
+    dblab_packed = gate(dblab_packed, what, "dblab_packed", _I64, dev, (None, None))
+    if dblab_packed.shape[1] != qlab_packed.shape[1]:
+        raise ValueError(f"{what}: label widths differ")
+    return qlab_packed, dblab_packed, qlab_packed.shape[1]
+
+
 def _map_at(what, idx, qlab_packed, dblab_packed, k, ks=None):
     lib = _lib.require_gpu()
+    idx, qlab_packed, dblab_packed, lw = _list_args(what, idx, qlab_packed, dblab_packed, PITCH)
     Q, kfull = idx.shape
+    if ks is None:
+        k = kfull if k is None else int(k)                  # map_at_k's default: the whole list
     cargs, tail, cols, kmax = _cuts(what, k, ks)
     if not 1 <= kmax <= kfull:
         raise ValueError(f"{what}: cut-off {kmax} outside the lists' length {kfull}")
-    lw = qlab_packed.shape[1]
-    if dblab_packed.shape[1] != lw:
-        raise ValueError(f"{what}: label widths differ")
-    if idx.stride(1) != 1:
-        idx = idx.contiguous()
     ap, nrel = _ap_buffers(Q, tail, idx.device)
     if Q:
         entry = "wv_map_at_k_ld" if ks is None else "wv_map_at_ks"
@@ -343,8 +386,11 @@ def _map_at(what, idx, qlab_packed, dblab_packed, k, ks=None):
 
 
 def map_at_k(idx, qlab_packed, dblab_packed, k=None):
-    """Average precision per query over (the first k entries of) its ranked list -> (ap float32 [Q], nrel int32 [Q])."""
-    return _map_at("map_at_k", idx, qlab_packed, dblab_packed, idx.shape[1] if k is None else int(k))
+    """Average precision per query over (the first k entries of) its ranked list -> (ap float32 [Q], nrel int32 [Q]).
+    idx: int32 [Q, >= k] (int64 is converted; a prefix idx[:, :k'] of wider lists is read in place); qlab_packed: int64
+    [Q, words], one row per list.  The VALUES of idx are not checked against the rows of dblab_packed: the entry point carries
+    no N, and a check would cost a reduction and a host read per call."""
+    return _map_at("map_at_k", idx, qlab_packed, dblab_packed, k)
 
 
 def map_at_ks(idx, qlab_packed, dblab_packed, ks):
@@ -360,9 +406,8 @@ class PreparedLabels:
 
     def __init__(self, dblab_packed, _virtual=True):
         lib = _lib.require_gpu()
-        if dblab_packed.dim() != 2 or dblab_packed.dtype != torch.int64:
-            raise ValueError("PreparedLabels: expected packed int64 label words [N, words] (see pack_codes)")
-        self.packed = dblab_packed.contiguous()
+        self.packed = gate(dblab_packed, "PreparedLabels", "dblab_packed (packed int64 label words [N, words], see pack_labels)", _I64,
+                           anchor(dblab_packed, "PreparedLabels", "dblab_packed", _DEVICE_TYPE), (None, None))
         self.N, self.words = self.packed.shape
         self.parts = None
         if SHARD_ROWS_MAX < self.N <= 64 * SHARD_ROWS_MAX and self.words <= 2 and _virtual:      # as PreparedDB: virtual shards
@@ -383,19 +428,26 @@ class PreparedLabels:
 def _fused_gate(what, q_packed, db, labels, qlab_packed, nbits, code_width=False):
     """The argument check of the entry points that read codes and labels in one kernel.  TypeError for unprepared inputs,
     ValueError for shapes that disagree (code_width: the packed width must also be nbits'); -> False when the shape is outside
-    the fused kernels (labels wider than 2 words, nbits > 128): the caller answers None."""
+    the fused kernels (labels wider than 2 words, nbits > 128): the caller answers None.
+    -> (inside the fused kernels, q_packed, qlab_packed), the two tensors gated: int64 rows on one device with `db` and `labels`,
+    one row of label words per query."""
     if not isinstance(db, PreparedDB) or not isinstance(labels, PreparedLabels):
         raise TypeError(f"{what}: needs a PreparedDB and PreparedLabels")
+    dev = anchor(q_packed, what, "q_packed", _DEVICE_TYPE)
+    q_packed = gate(q_packed, what, "q_packed", _I64, dev, (None, None))
+    qlab_packed = gate(qlab_packed, what, "qlab_packed", _I64, dev, (q_packed.shape[0], None))
+    same_device(db, what, "db", dev)
+    same_device(labels, what, "labels", dev)
     words = q_packed.shape[1]
     if words != db.words or labels.N != db.N or (code_width and words != _words(nbits)):
         raise ValueError(f"{what}: query / database / label shapes disagree")
-    return labels.ok and qlab_packed.shape[1] == labels.words and nbits <= 128
+    return labels.ok and qlab_packed.shape[1] == labels.words and nbits <= 128, q_packed, qlab_packed
 
 
 def _fused_map(what, q_packed, db, labels, qlab_packed, nbits, k, ks=None):
     """hamming_map_at_k (ks None) and hamming_map_at_ks: gate, virtual-shard route, direct route; the leaves differ (_cuts)."""
     lib = _lib.require_gpu()
-    ok = _fused_gate(what, q_packed, db, labels, qlab_packed, nbits)
+    ok, q_packed, qlab_packed = _fused_gate(what, q_packed, db, labels, qlab_packed, nbits)
     cargs, tail, cols, kmax = _cuts(what, k, ks)
     if ks is not None and kmax > db.N:
         raise ValueError(f"{what}: largest cut-off {kmax} must be <= N={db.N}")
@@ -417,8 +469,8 @@ def _fused_map(what, q_packed, db, labels, qlab_packed, nbits, k, ks=None):
     ap, nrel = _ap_buffers(Q, tail, dev)
     if Q:
         with torch.cuda.device(dev):
-            rc = getattr(lib, "wv_" + what)(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
-                                            _lib.ptr(qlab_packed.contiguous()), labels.words, Q, db.N, nbits, *cargs, _lib.ptr(ap),
+            rc = getattr(lib, "wv_" + what)(_lib.ptr(q_packed), _lib.ptr(db.blob), _lib.ptr(labels.blob),
+                                            _lib.ptr(qlab_packed), labels.words, Q, db.N, nbits, *cargs, _lib.ptr(ap),
                                             _lib.ptr(nrel), _lib.stream_ptr())
             if rc == _lib.WV_ENOTSUP:
                 return None
@@ -449,7 +501,8 @@ def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
     per-part calls.  None where hamming_map_at_k answers None (labels wider than 2 words, nbits > 128).
     db: PreparedDB; labels: PreparedLabels of the same rows; qlab_packed: int64 [Q, 1 or 2]."""
     lib = _lib.require_gpu()
-    if not _fused_gate("hamming_radius_hist", q_packed, db, labels, qlab_packed, nbits, code_width=True):
+    ok, q_packed, qlab_packed = _fused_gate("hamming_radius_hist", q_packed, db, labels, qlab_packed, nbits, code_width=True)
+    if not ok:
         return None
     Q = q_packed.shape[0]
     dev = q_packed.device
@@ -469,8 +522,8 @@ def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
     cumrel = torch.empty_like(cum)
     if Q:
         with torch.cuda.device(dev):
-            rc = lib.wv_hamming_radius_hist(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
-                                            _lib.ptr(qlab_packed.contiguous()), labels.words, Q, db.N, nbits, _lib.ptr(cum),
+            rc = lib.wv_hamming_radius_hist(_lib.ptr(q_packed), _lib.ptr(db.blob), _lib.ptr(labels.blob),
+                                            _lib.ptr(qlab_packed), labels.words, Q, db.N, nbits, _lib.ptr(cum),
                                             _lib.ptr(cumrel), _lib.stream_ptr())
             if rc == _lib.WV_ENOTSUP:
                 return None
@@ -500,10 +553,7 @@ def _columns(ap, nrel, cols):
     return ap.index_select(1, sel), nrel.index_select(1, sel)
 
 
-def _label_pair(qlab_packed, dblab_packed, what):
-    lw = qlab_packed.shape[1]
-    if qlab_packed.dim() != 2 or dblab_packed.dim() != 2 or dblab_packed.shape[1] != lw:
-        raise ValueError(f"{what}: label widths differ")
+def _graded_words(lw, what):
     if lw not in (1, 2):
         raise ValueError(f"{what}: {lw} label words (graded overlap takes 1 or 2: up to 128 classes)")
     return lw
@@ -513,12 +563,14 @@ def label_overlap_hist(qlab_packed, dblab_packed):
     """hist int32 [Q, 64 * lwords + 1]: hist[q, r] = database rows that share exactly r classes with query q
     (wv_label_overlap_hist: one pass over the packed label words, any N; the tables of row shards add up)."""
     lib = _lib.require_gpu()
-    lw = _label_pair(qlab_packed, dblab_packed, "label_overlap_hist")
+    dev = anchor(qlab_packed, "label_overlap_hist", "qlab_packed", _DEVICE_TYPE)
+    qlab_packed, dblab_packed, lw = _label_args("label_overlap_hist", qlab_packed, dblab_packed, None, dev)
+    _graded_words(lw, "label_overlap_hist")
     Q, N = qlab_packed.shape[0], dblab_packed.shape[0]
     hist = torch.zeros((Q, 64 * lw + 1), dtype=torch.int32, device=qlab_packed.device)
     if Q and N:                                      # an empty shard contributes zeros
         with torch.cuda.device(qlab_packed.device):
-            _lib.check(lib.wv_label_overlap_hist(_lib.ptr(qlab_packed.contiguous()), _lib.ptr(dblab_packed.contiguous()), lw, Q, N,
+            _lib.check(lib.wv_label_overlap_hist(_lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw, Q, N,
                                                  _lib.ptr(hist), _lib.stream_ptr()), "wv_label_overlap_hist")
     return hist
 
@@ -539,30 +591,26 @@ def ndcg_weights(k, device=None):
 
 def ndcg_at_ks(idx, qlab_packed, dblab_packed, ks, hist=None):
     """DCG and ideal DCG of ranked lists at several cut-offs from one walk (wv_ndcg_at_ks)
-    -> (dcg, idcg) float64 [Q, len(ks)].  idx: int32 [Q, >= max(ks)]; hist: label_overlap_hist of the WHOLE database (made
+    -> (dcg, idcg) float64 [Q, len(ks)].  idx: int32 [Q, >= max(ks)] (int64 is converted); hist: label_overlap_hist of the WHOLE database (made
     here when None).  Gains are 2^overlap - 1 in fp64 (beyond an overlap of 62 the reference's int64 overflows: no parity)."""
     lib = _lib.require_gpu()
+    idx, qlab_packed, dblab_packed, lw = _list_args("ndcg_at_ks", idx, qlab_packed, dblab_packed, PITCH)
+    _graded_words(lw, "ndcg_at_ks")
     Q, kfull = idx.shape
-    lw = _label_pair(qlab_packed, dblab_packed, "ndcg_at_ks")
     uniq, c_ks, cols = _cutoffs(ks, "ndcg_at_ks")
     if uniq[-1] > kfull:
         raise ValueError(f"ndcg_at_ks: cut-off {uniq[-1]} outside the lists' length {kfull}")
-    if idx.dtype != torch.int32:
-        raise ValueError("ndcg_at_ks: expected int32 lists")
-    if idx.stride(1) != 1:
-        idx = idx.contiguous()
+    dev = idx.device
     if hist is None:
         hist = label_overlap_hist(qlab_packed, dblab_packed)
-    if tuple(hist.shape) != (Q, 64 * lw + 1) or hist.dtype != torch.int32:
-        raise ValueError("ndcg_at_ks: hist must be the int32 [Q, 64 * lwords + 1] table of label_overlap_hist")
-    dev = idx.device
+    hist = gate(hist, "ndcg_at_ks", "hist (the int32 [Q, 64 * lwords + 1] table of label_overlap_hist)", _I32, dev, (Q, 64 * lw + 1))
     w = ndcg_weights(uniq[-1], dev)
     dcg = torch.zeros((Q, len(uniq)), dtype=torch.float64, device=dev)
     idcg = torch.zeros_like(dcg)
     if Q:
         with torch.cuda.device(dev):
-            _lib.check(lib.wv_ndcg_at_ks(_lib.ptr(idx), idx.stride(0), Q, c_ks, len(uniq), _lib.ptr(qlab_packed.contiguous()),
-                                         _lib.ptr(dblab_packed.contiguous()), lw, _lib.ptr(hist.contiguous()), _lib.ptr(w),
+            _lib.check(lib.wv_ndcg_at_ks(_lib.ptr(idx), idx.stride(0), Q, c_ks, len(uniq), _lib.ptr(qlab_packed),
+                                         _lib.ptr(dblab_packed), lw, _lib.ptr(hist), _lib.ptr(w),
                                          _lib.ptr(dcg), _lib.ptr(idcg), _lib.stream_ptr()), "wv_ndcg_at_ks")
     return _columns(dcg, idcg, cols)
 
@@ -580,7 +628,7 @@ def relbits_wire_words(kin, nbits):
 
 def _wire_args(wire, nbits):
     """The four C arguments that describe a contiguous wire buffer [.., relbits_wire_words]: relevance strings (pointer, row
-    pitch in 64-bit words), histograms (pointer, row pitch in int32)."""
+    pitch in 64-bit words), histograms (pointer, row pitch in int32).  `wire` is a gate() result: its data_ptr() is taken here."""
     ld = wire.shape[-1]
     return wire.data_ptr() + 8 * _hist_words(nbits), ld, wire.data_ptr(), 2 * ld
 
@@ -592,19 +640,20 @@ def hamming_shard_relbits(q_packed, db, labels, qlab_packed, nbits, k, wire=None
     tail of the string zero) -- a single all_to_all moves both.  `wire`: preallocated (zeroed) buffer.
     -> wire, or None when the shape is outside the fused kernel."""
     lib = _lib.require_gpu()
-    if not _fused_gate("hamming_shard_relbits", q_packed, db, labels, qlab_packed, nbits) or not 1 <= k <= db.N:
-        return None
+    ok, q_packed, qlab_packed = _fused_gate("hamming_shard_relbits", q_packed, db, labels, qlab_packed, nbits)
     Q = q_packed.shape[0]
     kin = k if kin is None else kin
     ld = relbits_wire_words(kin, nbits)
+    if wire is not None:
+        wire = gate(wire, "hamming_shard_relbits", "wire", _I64, q_packed.device, (Q, ld), WRITTEN)
+    if not ok or not 1 <= k <= db.N:
+        return None
     if wire is None:
         wire = torch.zeros((Q, ld), dtype=torch.int64, device=q_packed.device)
-    elif tuple(wire.shape) != (Q, ld) or wire.dtype != torch.int64 or not wire.is_contiguous():
-        raise ValueError("hamming_shard_relbits: wire buffer of the wrong shape")
     if Q:
         with torch.cuda.device(q_packed.device):
-            rc = lib.wv_hamming_shard_relbits(_lib.ptr(q_packed.contiguous()), _lib.ptr(db.blob), _lib.ptr(labels.blob),
-                                              _lib.ptr(qlab_packed.contiguous()), labels.words, *_wire_args(wire, nbits),
+            rc = lib.wv_hamming_shard_relbits(_lib.ptr(q_packed), _lib.ptr(db.blob), _lib.ptr(labels.blob),
+                                              _lib.ptr(qlab_packed), labels.words, *_wire_args(wire, nbits),
                                               Q, db.N, nbits, k, _lib.stream_ptr())
             if rc == _lib.WV_ENOTSUP:
                 return None
@@ -614,11 +663,12 @@ def hamming_shard_relbits(q_packed, db, labels, qlab_packed, nbits, k, wire=None
 
 def _merge_relbits(what, wire, kin, k, ks, nbits, need_out):
     lib = _lib.require_gpu()
+    dev = anchor(wire, what, "wire", _DEVICE_TYPE)
+    wire = gate(wire, what, "wire (int64 [G, Q, relbits_wire_words(kin, nbits)])", _I64, dev, (None, None, relbits_wire_words(kin, nbits)))
     G, Q, ld = wire.shape
-    if wire.dtype != torch.int64 or ld != relbits_wire_words(kin, nbits):
-        raise ValueError(f"{what}: expected the int64 [G, Q, relbits_wire_words(kin, nbits)] wire buffer")
+    if need_out is not None:
+        need_out = gate(need_out, what, "need_out", _I32, dev, (1,), WRITTEN)
     cargs, tail, cols, _ = _cuts(what, k, ks)
-    wire = wire.contiguous()
     ap, nrel = _ap_buffers(Q, tail, wire.device)
     if Q:
         with torch.cuda.device(wire.device):
@@ -659,16 +709,16 @@ def wire_histograms(wire, nbits):
 
 
 def hit_prefix(idx, qlab_packed, dblab_packed):
-    """hits[q, p] = number of relevant entries among idx[q, :p+1] (uint32 counts as int32 tensor [Q, k])."""
+    """hits[q, p] = number of relevant entries among idx[q, :p+1] (uint32 counts as int32 tensor [Q, k]).
+    idx: int32 [Q, k] (int64 is converted); qlab_packed: int64 [Q, words].  As in map_at_k, the values of idx are not checked
+    against the rows of dblab_packed (no N in the entry point; a check would cost a reduction and a host read)."""
     lib = _lib.require_gpu()
+    idx, qlab_packed, dblab_packed, lw = _list_args("hit_prefix", idx, qlab_packed, dblab_packed, ROWS)
     Q, k = idx.shape
-    lw = qlab_packed.shape[1]
-    if dblab_packed.shape[1] != lw:
-        raise ValueError("hit_prefix: label widths differ")
     hits = torch.empty((Q, k), dtype=torch.int32, device=idx.device)
     if Q:
         with torch.cuda.device(idx.device):
-            rc = lib.wv_hit_prefix(_lib.ptr(idx.contiguous()), Q, k, _lib.ptr(qlab_packed), _lib.ptr(dblab_packed),
+            rc = lib.wv_hit_prefix(_lib.ptr(idx), Q, k, _lib.ptr(qlab_packed), _lib.ptr(dblab_packed),
                                    lw, _lib.ptr(hits), _lib.stream_ptr())
             _lib.check(rc, "wv_hit_prefix")
     return hits

@@ -3,13 +3,18 @@ engine/hamming.py, on CPU tensors.  This is the module of the host backend (engi
 selects in CustomCalculator, RankCache, get_knn, NDCG / ndcg_at / p_topK and the radius metrics -- the configuration the reference itself
 runs its calculator in (/root/reference/main/engine/evaluate.py:76-81, accuracy_calculator.py:290-293) and BASELINE config
 c0 ("CPU ... plumbing, no GPU").  Same integers as the kernels; average precision bit-identical (same summation order).
-No GPU is touched and none is needed."""
+No GPU is touched and none is needed.  Every tensor handed to the library passes the gate of engine/_args.py, as in
+engine/hamming.py: host tensors only (pack_codes / pack_labels alone move their input here), any stride, int64 index lists
+converted, every other dtype or shape mismatch a ValueError."""
 import ctypes
 
 import torch
 
 from .. import _lib
+from ._args import PITCH, ROWS, anchor, gate
 
+_DEVICE_TYPE = "cpu"             # every tensor argument of this module is a host tensor (_pack alone moves its input here)
+_I64, _I32 = torch.int64, torch.int32
 SHARD_ROWS_MAX = 1 << 62        # no windowed-kernel limit on the host
 MAX_CUTOFFS = 16                # WV_MAX_CUTOFFS
 
@@ -18,7 +23,18 @@ def _words(nbits):
     return (nbits + 63) // 64
 
 
+def _codes(what, name, t, device=None, words=None, rows=None):
+    """Packed int64 rows [rows, words] on the host, gated -> (tensor, device)"""
+    device = anchor(t, what, name, _DEVICE_TYPE) if device is None else device
+    return gate(t, what, name, _I64, device, (rows, words)), device
+
+
+def _packed_of(obj, kinds):
+    return obj.packed if isinstance(obj, kinds) else obj
+
+
 def _host(t, dtype=None):
+    """_pack's move of whatever it is given to a contiguous host tensor"""
     if not torch.is_tensor(t):
         t = torch.as_tensor(t)
     t = t.detach().cpu()
@@ -32,6 +48,7 @@ def _pack(src, mode, check, what):
     src = _host(src, torch.float32)
     if src.dim() != 2:
         raise ValueError(f"{what}: expected a 2-D tensor, got {tuple(src.shape)}")
+    src = gate(src, what, "values", torch.float32, src.device, (None, None), PITCH)
     rows, nbits = src.shape
     out = torch.empty((rows, _words(nbits)), dtype=torch.int64)
     flag = ctypes.c_int32(0)
@@ -57,7 +74,7 @@ def pack_labels(labels, check=True):
 
 def bit_counts(packed, nbits):
     lib = _lib.load()
-    packed = _host(packed)
+    packed, _ = _codes("bit_counts", "packed", packed, words=_words(nbits))
     counts = torch.empty(nbits, dtype=torch.int32)
     _lib.check(lib.wv_bit_counts_cpu(_lib.ptr(packed), packed.shape[0], nbits, _lib.ptr(counts)), "wv_bit_counts_cpu")
     return counts
@@ -65,7 +82,8 @@ def bit_counts(packed, nbits):
 
 def hamming_dist(q_packed, db, nbits=None):
     lib = _lib.load()
-    q_packed, db = _host(q_packed), _host(db)
+    q_packed, dev = _codes("hamming_dist", "q_packed", q_packed)
+    db, _ = _codes("hamming_dist", "db", _packed_of(db, PreparedDB), dev)
     Q, words = q_packed.shape
     N = db.shape[0]
     if db.shape[1] != words:
@@ -84,7 +102,8 @@ def hamming_topk(q_packed, db, nbits, k, idx_offset=0, workspace=None, want_dist
     if want_cum:
         raise NotImplementedError("hamming_topk on the host: histograms are a by-product of the sharded GPU search only")
     lib = _lib.load()
-    q_packed, db = _host(q_packed), _host(db.packed if isinstance(db, PreparedDB) else db)
+    q_packed, dev = _codes("hamming_topk", "q_packed", q_packed)
+    db, _ = _codes("hamming_topk", "db", _packed_of(db, PreparedDB), dev)
     Q, words = q_packed.shape
     N = db.shape[0]
     if db.shape[1] != words or words != _words(nbits):
@@ -98,17 +117,15 @@ def hamming_topk(q_packed, db, nbits, k, idx_offset=0, workspace=None, want_dist
 
 
 def _map_at(what, idx, qlab_packed, dblab_packed, k, ks=None):
-    from .hamming import _cuts, _columns
+    from .hamming import _cuts, _columns, _list_args
     lib = _lib.load()
-    idx = _host(idx, torch.int32) if idx.stride(-1) != 1 or idx.dtype != torch.int32 or idx.is_cuda else idx
-    qlab_packed, dblab_packed = _host(qlab_packed), _host(dblab_packed)
+    idx, qlab_packed, dblab_packed, lw = _list_args(what, idx, qlab_packed, dblab_packed, PITCH, _DEVICE_TYPE)
     Q, kfull = idx.shape
+    if ks is None:
+        k = kfull if k is None else int(k)                  # map_at_k's default: the whole list
     cargs, tail, cols, kmax = _cuts(what, k, ks)
     if not 1 <= kmax <= kfull:
         raise ValueError(f"{what}: cut-off {kmax} outside the lists' length {kfull}")
-    lw = qlab_packed.shape[1]
-    if dblab_packed.shape[1] != lw:
-        raise ValueError(f"{what}: label widths differ")
     ap = torch.empty((Q,) + tail, dtype=torch.float32)
     nrel = torch.empty((Q,) + tail, dtype=torch.int32)
     if Q:
@@ -119,7 +136,7 @@ def _map_at(what, idx, qlab_packed, dblab_packed, k, ks=None):
 
 
 def map_at_k(idx, qlab_packed, dblab_packed, k=None):
-    return _map_at("map_at_k", idx, qlab_packed, dblab_packed, idx.shape[1] if k is None else int(k))
+    return _map_at("map_at_k", idx, qlab_packed, dblab_packed, k)
 
 
 def map_at_ks(idx, qlab_packed, dblab_packed, ks):
@@ -128,13 +145,10 @@ def map_at_ks(idx, qlab_packed, dblab_packed, ks):
 
 
 def hit_prefix(idx, qlab_packed, dblab_packed):
+    from .hamming import _list_args
     lib = _lib.load()
-    idx = _host(idx, torch.int32)
-    qlab_packed, dblab_packed = _host(qlab_packed), _host(dblab_packed)
+    idx, qlab_packed, dblab_packed, lw = _list_args("hit_prefix", idx, qlab_packed, dblab_packed, ROWS, _DEVICE_TYPE)
     Q, k = idx.shape
-    lw = qlab_packed.shape[1]
-    if dblab_packed.shape[1] != lw:
-        raise ValueError("hit_prefix: label widths differ")
     hits = torch.empty((Q, k), dtype=torch.int32)
     if Q:
         _lib.check(lib.wv_hit_prefix_cpu(_lib.ptr(idx), Q, k, _lib.ptr(qlab_packed), _lib.ptr(dblab_packed), lw, _lib.ptr(hits)),
@@ -146,7 +160,7 @@ class PreparedDB:
     """Nothing to prepare on the host: keeps the packed codes (the calculator's code path is shared with the GPU)."""
 
     def __init__(self, db_packed, nbits=None, _virtual=True):
-        self.packed = _host(db_packed)
+        self.packed, _ = _codes("PreparedDB", "db_packed", db_packed)
         self.N, self.words = self.packed.shape
         self.nbits = nbits if nbits is not None else self.words * 64
         self.parts = None
@@ -156,7 +170,7 @@ class PreparedLabels:
     """Nothing to prepare on the host either: keeps the packed label words."""
 
     def __init__(self, dblab_packed):
-        self.packed = _host(dblab_packed)
+        self.packed, _ = _codes("PreparedLabels", "dblab_packed", dblab_packed)
         self.N, self.words = self.packed.shape
         self.parts, self.ok, self.blob = None, self.words <= 2, None
 
@@ -165,10 +179,12 @@ def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
     """hamming.hamming_radius_hist through the host twin (wv_hamming_radius_hist_cpu), any N -> (cum, cumrel) int32
     [Q, nbits + 2], the kernel's integers.  db / labels: PreparedDB / PreparedLabels of this module or packed int64 tensors."""
     lib = _lib.load()
-    q_packed, qlab_packed = _host(q_packed), _host(qlab_packed)
-    dbp = _host(db.packed if isinstance(db, PreparedDB) else db)
-    lab = _host(labels.packed if isinstance(labels, PreparedLabels) else labels)
+    what = "hamming_radius_hist"
+    q_packed, dev = _codes(what, "q_packed", q_packed)
     Q, words = q_packed.shape
+    qlab_packed, _ = _codes(what, "qlab_packed", qlab_packed, dev, rows=Q)
+    dbp, _ = _codes(what, "db", _packed_of(db, PreparedDB), dev)
+    lab, _ = _codes(what, "labels", _packed_of(labels, PreparedLabels), dev)
     if dbp.shape[1] != words or lab.shape[0] != dbp.shape[0] or words != _words(nbits):
         raise ValueError("hamming_radius_hist: query / database / label shapes disagree")
     if lab.shape[1] > 2 or qlab_packed.shape[1] != lab.shape[1] or nbits > 128:
@@ -183,13 +199,11 @@ def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
 
 def label_overlap_hist(qlab_packed, dblab_packed):
     """hamming.label_overlap_hist through the host twin (wv_label_overlap_hist_cpu): the same integers."""
+    from .hamming import _graded_words, _label_args
     lib = _lib.load()
-    qlab_packed, dblab_packed = _host(qlab_packed), _host(dblab_packed)
-    lw = qlab_packed.shape[1]
-    if dblab_packed.shape[1] != lw:
-        raise ValueError("label_overlap_hist: label widths differ")
-    if lw not in (1, 2):
-        raise ValueError(f"label_overlap_hist: {lw} label words (graded overlap takes 1 or 2: up to 128 classes)")
+    dev = anchor(qlab_packed, "label_overlap_hist", "qlab_packed", _DEVICE_TYPE)
+    qlab_packed, dblab_packed, lw = _label_args("label_overlap_hist", qlab_packed, dblab_packed, None, dev)
+    _graded_words(lw, "label_overlap_hist")
     Q, N = qlab_packed.shape[0], dblab_packed.shape[0]
     hist = torch.zeros((Q, 64 * lw + 1), dtype=torch.int32)
     if Q and N:
@@ -201,18 +215,17 @@ def label_overlap_hist(qlab_packed, dblab_packed):
 def ndcg_at_ks(idx, qlab_packed, dblab_packed, ks, hist=None):
     """hamming.ndcg_at_ks through the host twin (wv_ndcg_at_ks_cpu): the same table w, the same summation order, the
     kernel's bits -> (dcg, idcg) float64 [Q, len(ks)]."""
-    from .hamming import _cutoffs, _columns, ndcg_weights
+    from .hamming import _cutoffs, _columns, _graded_words, _list_args, ndcg_weights
     lib = _lib.load()
-    idx = _host(idx, torch.int32) if idx.stride(-1) != 1 or idx.dtype != torch.int32 or idx.is_cuda else idx
-    qlab_packed, dblab_packed = _host(qlab_packed), _host(dblab_packed)
+    idx, qlab_packed, dblab_packed, lw = _list_args("ndcg_at_ks", idx, qlab_packed, dblab_packed, PITCH, _DEVICE_TYPE)
+    _graded_words(lw, "ndcg_at_ks")
     Q, kfull = idx.shape
-    lw = qlab_packed.shape[1]
     uniq, c_ks, cols = _cutoffs(ks, "ndcg_at_ks")
     if uniq[-1] > kfull:
         raise ValueError(f"ndcg_at_ks: cut-off {uniq[-1]} outside the lists' length {kfull}")
-    hist = label_overlap_hist(qlab_packed, dblab_packed) if hist is None else _host(hist, torch.int32)
-    if tuple(hist.shape) != (Q, 64 * lw + 1):
-        raise ValueError("ndcg_at_ks: hist must be the int32 [Q, 64 * lwords + 1] table of label_overlap_hist")
+    if hist is None:
+        hist = label_overlap_hist(qlab_packed, dblab_packed)
+    hist = gate(hist, "ndcg_at_ks", "hist (the int32 [Q, 64 * lwords + 1] table of label_overlap_hist)", _I32, idx.device, (Q, 64 * lw + 1))
     w = ndcg_weights(uniq[-1])
     dcg = torch.zeros((Q, len(uniq)), dtype=torch.float64)
     idcg = torch.zeros_like(dcg)

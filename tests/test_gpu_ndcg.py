@@ -38,7 +38,7 @@ def test_overlap_hist_edges_and_shards(classes):
     rl[N - 1] = ql[1]                                          # the last row of the tail slice shares every class with query 1
     qlp, rlp = HH.pack_labels(ql).cuda(), HH.pack_labels(rl).cuda()
     whole = H.label_overlap_hist(qlp, rlp)
-    assert torch.equal(whole.cpu(), HH.label_overlap_hist(qlp, rlp))
+    assert torch.equal(whole.cpu(), HH.label_overlap_hist(qlp.cpu(), rlp.cpu()))        # the host twin takes host tensors
     assert int(whole[0, 0]) == N and int(whole[1, classes]) == 2 and bool((whole.sum(1) == N).all())
     assert torch.equal(H.label_overlap_hist(qlp, rlp[:4097]) + H.label_overlap_hist(qlp, rlp[4097:]), whole)
     same = HH.pack_labels(ql[2:3].repeat(N, 1)).cuda()         # one bin holds all N rows
@@ -151,6 +151,6 @@ def test_c1_sized_run():
     dcg, idcg = H.ndcg_at_ks(idx, qlp, rlp, [100, k], hist=hist)
     assert float((ND.ndcg_from_sums(dcg, idcg) - got).abs().max()) <= C.mean_tol(Q)
     s = slice(100, 116)                                        # the twin on a 16-query slice
-    assert torch.equal(hist[s].cpu(), HH.label_overlap_hist(qlp[s], rlp))
+    assert torch.equal(hist[s].cpu(), HH.label_overlap_hist(qlp[s].cpu(), rlp.cpu()))
     want_d, want_i = HH.ndcg_at_ks(idx[s].cpu(), qlp[s].cpu(), rlp.cpu(), [100, k])
     assert torch.equal(bits(dcg[s]), bits(want_d)) and torch.equal(bits(idcg[s]), bits(want_i))
