@@ -58,7 +58,16 @@ def test_side_stream_is_honoured():
                                           ("db2", 3, 48, 224)])   # the last: below the sliding kernel's window
 def test_every_swt_implementation_agrees_with_the_oracle(path, wl, lev, H_, W_, diag):
     from wvhash.transforms import swt2d
+    import swt_fallback_cases as fc
     diag.setenv("WV_SWT_PATH", path)
+    # which kernel produces the numbers below: a pinned path that does not take the shape turns into generic silently, and
+    # only the generic kernels need a workspace
+    L = fc.TAPS[wl]
+    runs = {fc.path(L, lev, H_, W_, 3, nhwc, pin=path) for nhwc in (False, True)}
+    falls_back = path == "slide" and (H_, W_) == (48, 224)       # the one case meant to: H below the sliding window
+    assert runs == ({"generic"} if falls_back or path == "generic" else {path})
+    ws_bytes = _lib.require_gpu().wv_swt2d_workspace_bytes(2, 3, H_, W_, lev, L)
+    assert ws_bytes == (3 * 2 * 3 * H_ * W_ * 4 if "generic" in runs else 0) == fc.workspace_bytes(L, lev, H_, W_, 3, path)
     img = synth.natural_images(2, H_, W_, seed=lev + W_)
     ref = swt_np.c_transform_batch(img, wl, lev)
     x = torch.from_numpy(img).cuda()
