@@ -25,6 +25,7 @@ WV_BANDS_INNER, WV_BANDS_OUTER = 0, 1
 WV_TOKENS_SBE, WV_TOKENS_BSE = 0, 1      # band tokens as [S][B][E] (wv_band_attn_pool's) or [B][S][E] (torch.stack(kv_list, 1))
 WV_RESAMPLE_BILINEAR, WV_RESAMPLE_BICUBIC = 2, 3      # PIL's enum values
 WV_COLOUR_BRIGHTNESS, WV_COLOUR_CONTRAST, WV_COLOUR_SATURATION = 0, 1, 2
+WV_IP_MAP_ROWS_MAX = 2048   # include/wvhash.h: rows wv_ip_map_at_k ranks in one workgroup
 WV_ENOTSUP = -95            # return code: the shape is outside the kernel asked for (callers fall back)
 
 
@@ -173,6 +174,8 @@ SIGNATURES = {
     "wv_group_layernorm_check": (_i, [_i, _i, _i64, _i64, _i, _i]),
     "wv_group_layernorm": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i, _i, _vp, _vp, _f, _vp]),
     "wv_group_layernorm_cpu": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i, _i, _vp, _vp, _f]),
+    "wv_ip_map_at_k": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "wv_ip_map_at_k_cpu": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i, _i, _vp, _vp]),
 }
 
 _LIB = None

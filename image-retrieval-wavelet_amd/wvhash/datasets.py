@@ -45,9 +45,18 @@ class _SplitFileHashing(Dataset):
         root = os.path.join(data_dir, self.image_subdir) if self.image_subdir else data_dir
         self.paths = [os.path.join(root, n) for n in names]
         self.labels = list(self.label_matrix)
+        self.get_instance_dict()
+
+    def get_instance_dict(self):
+        """{tag index: [item indices]} of the CURRENT `labels` (make_subset replaces them and calls this): tags in the order
+        their first item appears, items ascending."""
         self.instance_dict = defaultdict(list)
-        for row, col in (self.label_matrix == 1.0).nonzero().tolist():
-            self.instance_dict[col].append(row)
+        if len(self.labels):
+            for row, col in (torch.stack(list(self.labels)) == 1.0).nonzero().tolist():
+                self.instance_dict[col].append(row)
+
+    def get_super_dict(self):
+        """The split files carry no super labels: nothing to group (make_subset calls it on every dataset)."""
 
     def __len__(self):
         return len(self.paths)

@@ -8,6 +8,8 @@ reference's own configuration, main/engine/evaluate.py:76-81; BASELINE config c0
 of the same entry points (csrc/host_rank.cpp; same integers, same AP bits) -- and routes the arithmetic through libwvhash:
   calc_hamming_dist       -> wv_hamming_dist        (:183-186)
   calculate_maphashing    -> wv_hamming_map_at_k, or wv_hamming_topk + wv_map_at_k   (:203-231, the reported metric)
+                             with soft_codes = True and embeddings that are not +-1 (the batch mAP proxy, engine/batch_map.py)
+                             -> wv_ip_map_at_k, or wv_knn_float + wv_map_at_k
   calculate_maphashing_at -> wv_hamming_map_at_ks / wv_map_at_ks: the same at several cut-offs from one ranking pass
   calculate_bit_balance / calculate_worst_bit_balance -> wv_bit_counts   (:188-200)
   calculate_map           -> get_knn + wv_map_at_k  (:156-167, torchmetrics RetrievalMAP)
@@ -140,6 +142,19 @@ class RankCache(object):
                 done.update({k: got[0] if len(ks) == 1 else got[0][:, i] for i, k in enumerate(ks)})
         return done[topk]
 
+    def ip_maphashing(self, query, query_labels, reference, reference_labels, topk):
+        """Average precision per query at `topk` (float32 [Q]) of REAL-VALUED embeddings ranked by descending inner product --
+        the order of the reference's key 0.5 * (nbits - q @ r.T), ties by ascending row: one launch (wv_ip_map_at_k) where
+        the shape allows; where that answers None the float k-NN ranks to `topk` and map_at_k reads the list: by the entry
+        point's contract the same bits."""
+        H = self.backend.H
+        qlp, rlp = self.packed_labels(query_labels, reference_labels)
+        got = H.ip_map_at_k(query, reference, qlp, rlp, topk)
+        if got is None:
+            _, idx = self.backend.knn_float(reference, query, topk, _lib.WV_METRIC_IP)
+            got = H.map_at_k(idx, qlp, rlp, k=topk)
+        return got[0]
+
     def map_at_k(self, idx, query_labels, reference_labels, k=None):
         """(ap, nrel) of lists the caller ranked (k-NN lists), over the session's packed labels."""
         return self.backend.H.map_at_k(idx, *self.packed_labels(query_labels, reference_labels), k=k)
@@ -197,6 +212,10 @@ class CustomCalculator(object):
         self.pr_curve_hamming_path, self.last_pr_curve_hamming = kwargs.pop("pr_curve_hamming_path", None), None
         self.distance_metric = distance_metric
         self.rank_cache = kwargs.pop("rank_cache", None)          # shared by the calculators of evaluate_multi_k
+        # False: calculate_maphashing takes +-1 codes only (anything else raises in the packer).  True: embeddings that are
+        # not exactly +-1 are ranked by inner product like the reference's calc_hamming_dist ranks them (wv_ip_map_at_k);
+        # +-1 codes take the packed path either way.  build_batch_map_calculator sets it.
+        self.soft_codes = False
         # device=None / 'cuda': the ranking stage lives on the GPU.  device='cpu' (what the reference pins its calculator
         # to, main/engine/evaluate.py:76-81): the host twins of the same entry points -- explicit, never a fallback: without
         # a GPU and without device='cpu' every metric raises WvhashUnavailable.
@@ -325,8 +344,15 @@ class CustomCalculator(object):
         num_query = query.shape[0]
         if num_query == 0:
             raise ZeroDivisionError("calculate_maphashing: no queries")
-        # ranking and AP in one kernel where the shape allows and no list exists yet; otherwise lists, then AP (same numbers)
-        ap = self._session().maphashing(query, query_labels, reference, reference_labels, topk)
+        if self.soft_codes and topk <= 0:
+            # a same-source batch in which no two rows share a tag: the reference's gnd[0:0] is empty, every AP is 0 -- no launch
+            return (0.0, torch.zeros(num_query, dtype=torch.float32, device=query.device)) if return_per_query else 0.0
+        if self.soft_codes and not (_is_pm1(reference) and (query is reference or _is_pm1(query))):
+            # real-valued embeddings (tanh values, BN logits): the reference's own key on them, no packing
+            ap = self._session().ip_maphashing(query, query_labels, reference, reference_labels, topk)
+        else:
+            # ranking and AP in one kernel where the shape allows and no list exists yet; otherwise lists, then AP (same numbers)
+            ap = self._session().maphashing(query, query_labels, reference, reference_labels, topk)
         result = ap.double().sum().item() / num_query
         if return_per_query:
             return result, ap
@@ -347,7 +373,11 @@ class CustomCalculator(object):
             raise ZeroDivisionError("calculate_maphashing_at: no queries")
         eff = [min(k, num_ref) for k in ks]
         session = self._session()
-        cols = {k: session.maphashing(query, query_labels, reference, reference_labels, k, also=eff) for k in eff}
+        if self.soft_codes and not (_is_pm1(reference) and (query is reference or _is_pm1(query))):
+            # real-valued embeddings: one wv_ip_map_at_k call per cut-off
+            cols = {k: session.ip_maphashing(query, query_labels, reference, reference_labels, k) for k in set(eff)}
+        else:
+            cols = {k: session.maphashing(query, query_labels, reference, reference_labels, k, also=eff) for k in eff}
         out = {}
         for k, ke in zip(ks, eff):
             value = cols[ke].double().sum().item() / num_query

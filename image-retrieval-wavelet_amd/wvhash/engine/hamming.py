@@ -493,6 +493,46 @@ def hamming_map_at_ks(q_packed, db, labels, qlab_packed, nbits, ks):
     return _fused_map("hamming_map_at_ks", q_packed, db, labels, qlab_packed, nbits, None, ks)
 
 
+IP_MAP_ROWS_MAX = _lib.WV_IP_MAP_ROWS_MAX     # WV_IP_MAP_ROWS_MAX: rows wv_ip_map_at_k ranks inside one workgroup
+
+
+def _ip_map_args(what, q, db, qlab_packed, dblab_packed, k, device_type):
+    """The arguments of ip_map_at_k on either side: fp32 rows on one device (bf16 / fp16 embeddings are widened, which is
+    exact), one row of packed label words per embedding row -> (q, db, qlab_packed, dblab_packed, label words, k), gated."""
+    dev = anchor(q, what, "q", device_type)
+    q, db = (t.float() if torch.is_tensor(t) and t.dtype in (torch.bfloat16, torch.float16) else t for t in (q, db))
+    q = gate(q, what, "q", torch.float32, dev, (None, None))
+    db = gate(db, what, "db", torch.float32, dev, (None, q.shape[1]))
+    qlab_packed = gate(qlab_packed, what, "qlab_packed", _I64, dev, (q.shape[0], None))
+    dblab_packed = gate(dblab_packed, what, "dblab_packed", _I64, dev, (db.shape[0], None))
+    if dblab_packed.shape[1] != qlab_packed.shape[1]:
+        raise ValueError(f"{what}: label widths differ")
+    return q, db, qlab_packed, dblab_packed, qlab_packed.shape[1], int(k)
+
+
+def ip_map_at_k(q, db, qlab_packed, dblab_packed, k):
+    """mAP@k ingredients of REAL-VALUED embeddings in one launch (wv_ip_map_at_k): rows of `db` ranked by descending inner
+    product with each row of `q` (ties: ascending row), AP over the first k -> (ap float32 [Q], nrel int32 [Q]): the numbers,
+    bit for bit, map_at_k returns for the lists knn_float(IP, k) makes.  None when the shape is outside the kernel (more
+    than IP_MAP_ROWS_MAX rows, D > 512, labels wider than 2 words): the caller then runs those two.
+    q [Q, D], db [N, D]: fp32 (bf16 / fp16 are widened); qlab_packed int64 [Q, words], dblab_packed int64 [N, words]."""
+    lib = _lib.require_gpu()
+    q, db, qlab_packed, dblab_packed, lw, k = _ip_map_args("ip_map_at_k", q, db, qlab_packed, dblab_packed, k, _DEVICE_TYPE)
+    if lw > 2:
+        return None
+    Q = q.shape[0]
+    ap, nrel = _ap_buffers(Q, (), q.device)
+    if not Q:
+        return ap, nrel
+    with torch.cuda.device(q.device):
+        rc = lib.wv_ip_map_at_k(_lib.ptr(q), _lib.ptr(db), Q, db.shape[0], q.shape[1], _lib.ptr(qlab_packed), _lib.ptr(dblab_packed),
+                                lw, k, _lib.ptr(ap), _lib.ptr(nrel), _lib.stream_ptr())
+        if rc == _lib.WV_ENOTSUP:
+            return None
+        _lib.check(rc, "wv_ip_map_at_k")
+    return ap, nrel
+
+
 def hamming_radius_hist(q_packed, db, labels, qlab_packed, nbits):
     """Cumulative distance histograms of every query over ALL rows of `db` and over the rows that share a label with it
     -> (cum, cumrel) int32 [Q, nbits + 2]: cum[q, b] = rows with distance < b (hamming_hist's numbers), cumrel[q, b] = those

@@ -235,6 +235,29 @@ def ndcg_at_ks(idx, qlab_packed, dblab_packed, ks, hist=None):
     return _columns(dcg, idcg, cols)
 
 
+IP_MAP_ROWS_MAX = _lib.WV_IP_MAP_ROWS_MAX
+
+
+def ip_map_at_k(q, db, qlab_packed, dblab_packed, k):
+    """hamming.ip_map_at_k through the host twin (wv_ip_map_at_k_cpu): the kernel's bits, the same limits -> (ap float32 [Q],
+    nrel int32 [Q]) or None outside them."""
+    from .hamming import _ip_map_args
+    lib = _lib.load()
+    q, db, qlab_packed, dblab_packed, lw, k = _ip_map_args("ip_map_at_k", q, db, qlab_packed, dblab_packed, k, _DEVICE_TYPE)
+    if lw > 2:
+        return None
+    Q = q.shape[0]
+    ap, nrel = torch.empty(Q, dtype=torch.float32), torch.empty(Q, dtype=torch.int32)
+    if not Q:
+        return ap, nrel
+    rc = lib.wv_ip_map_at_k_cpu(_lib.ptr(q), _lib.ptr(db), Q, db.shape[0], q.shape[1], _lib.ptr(qlab_packed), _lib.ptr(dblab_packed),
+                                lw, k, _lib.ptr(ap), _lib.ptr(nrel))
+    if rc == _lib.WV_ENOTSUP:
+        return None
+    _lib.check(rc, "wv_ip_map_at_k_cpu")
+    return ap, nrel
+
+
 def hamming_map_at_k(*args, **kwargs):
     return None                   # ranking and AP are two calls on the host (same numbers)
 

@@ -29,6 +29,7 @@ import torch
 import torch.distributed as dist
 
 from ..transforms.functional import size_images
+from .batch_map import compute_batch_map
 from ..transforms.sizing import RawBatch
 
 LOGGER = logging.getLogger("RETRIEVAL")
@@ -159,11 +160,14 @@ def _ortho_loss(net):
     return None
 
 
-def backward_step(net, images, labels, criteria, autocast_dtype=torch.bfloat16, scaler=None, sub_batch=None):
+def backward_step(net, images, labels, criteria, autocast_dtype=torch.bfloat16, scaler=None, sub_batch=None,
+                  batch_map_calculator=None, batch_map_metric=None):
     """Forward + backward of one LOCAL batch (gradients accumulate into .grad; no optimizer step, no exchange).
     images: what the DataLoader collated -- expanded sub-bands [B,3,4,H,W], raw uint8 [B,3,H,W] (deferred transform
     bound to the model) or a transforms.sizing.RawBatch (sizing="device": sized here on the GPU, then as raw images).
-    criteria: [(loss module, weight)].  Returns a dict of logged scalars."""
+    criteria: [(loss module, weight)].  batch_map_calculator / batch_map_metric (build_batch_map_calculator's pair):
+    logs["proxy_<metric>"] = compute_batch_map of the batch's detached embeddings and labels -- under sub_batch the gathered
+    embeddings of all micro-batches (base_update.py:70-73, 287-290); None: no extra work.  Returns a dict of logged scalars."""
     device = next(p for p in net.parameters()).device
     images = images.to(device, non_blocking=True)
     if isinstance(images, RawBatch):
@@ -179,6 +183,8 @@ def backward_step(net, images, labels, criteria, autocast_dtype=torch.bfloat16, 
     if not sub_batch or sub_batch >= total:
         with _autocast(device.type, autocast_dtype):
             emb = net(images)
+            if batch_map_calculator is not None:
+                logs[f"proxy_{batch_map_metric}"] = compute_batch_map(batch_map_calculator, batch_map_metric, emb, labels)
             losses = _criterion_loss(criteria, emb, labels, logs)
         ortho = _ortho_loss(net)
         if ortho is not None:
@@ -218,14 +224,18 @@ def backward_step(net, images, labels, criteria, autocast_dtype=torch.bfloat16, 
             if s == 0:
                 logs["Ortho_Loss"] = float(ortho.detach())
         torch.autograd.backward(tensors, grad_tensors=grads)
+    if batch_map_calculator is not None:
+        logs[f"proxy_{batch_map_metric}"] = compute_batch_map(batch_map_calculator, batch_map_metric, emb_full.detach(), labels)
     return logs
 
 
 def train_step(net, images, labels, criteria, optimizers, averager=None, autocast_dtype=torch.bfloat16, scaler=None,
-               sub_batch=None, clip_grad=None):
-    """One optimisation step of one rank: backward_step on the local batch, gradient average over the ranks, optional
-    clipping, optimizer steps (the model's optimizers and the losses' own, base_update.py:363-396), zero_grad."""
-    logs = backward_step(net, images, labels, criteria, autocast_dtype=autocast_dtype, scaler=scaler, sub_batch=sub_batch)
+               sub_batch=None, clip_grad=None, batch_map_calculator=None, batch_map_metric=None):
+    """One optimisation step of one rank: backward_step on the local batch (with its batch mAP proxy when a
+    batch_map_calculator is given), gradient average over the ranks, optional clipping, optimizer steps (the model's
+    optimizers and the losses' own, base_update.py:363-396), zero_grad."""
+    logs = backward_step(net, images, labels, criteria, autocast_dtype=autocast_dtype, scaler=scaler, sub_batch=sub_batch,
+                         batch_map_calculator=batch_map_calculator, batch_map_metric=batch_map_metric)
     if averager is not None:
         averager.average()
     optimizers = list(optimizers.values()) if isinstance(optimizers, dict) else list(optimizers)

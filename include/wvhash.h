@@ -61,6 +61,7 @@ const char *wv_last_error(void);
  * wv_lift_out_size, wv_lift_images_tile): 92 symbols.
  * So was the single-band SWT (wv_swt2d_band_forward, wv_swt2d_band_forward_cpu): 94 symbols.
  * So was the grouped LayerNorm (wv_group_layernorm, wv_group_layernorm_cpu, wv_group_layernorm_check): 97 symbols.
+ * So was the batch mAP proxy of real-valued embeddings (wv_ip_map_at_k, wv_ip_map_at_k_cpu): 99 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -496,6 +497,38 @@ size_t wv_rank_scores_workspace_bytes(int Q, int64_t N, int k);
 int wv_rank_scores(const float *S, int Q, int64_t N, int k, int flags, int32_t *idx, float *val, void *workspace,
                    size_t workspace_bytes, void *stream);
 int wv_rank_scores_cpu(const float *S, int Q, int64_t N, int k, int flags, int32_t *idx, float *val);
+
+/* ------------------------------------------------------------------------------------------
+ * Batch mAP proxy: average precision over the inner-product ranking of REAL-VALUED embeddings, scores, ranking and AP in one
+ * launch.  Replaces calculate_maphashing (accuracy_calculator.py:203-231) where its key 0.5 * (nbits - q @ r.T)
+ * (calc_hamming_dist :183-186) is taken of tanh values or BN logits: compute_batch_map's self-retrieval mAP of a minibatch
+ * (main/engine/batch_map.py, base_update.py:70-73,287-290).  The small problem -- no list wanted, one launch before a
+ * .item(); large shapes are wv_knn_float + wv_map_at_k.
+ *   q [Q][D], db [N][D] float32, dense; qlab [Q][lwords], dblab [N][lwords]: labels packed by wv_pack_bits(mode 1)
+ *   ap float32 [Q], nrel int32 [Q] or NULL
+ * The contract, the same for the kernel and the host twin, bit for bit:
+ *   score      s(q, n) = the fp32 value wv_knn_float(metric = WV_METRIC_IP) writes for the pair: one fmaf chain from 0.0f over
+ *              k in the order the matrix cores accumulate it (8c + e, 8c + 4 + e for e = 0..3 of every chunk c of eight).
+ *   order      descending score, ties by ascending row, on wv_knn_float's order-preserving 32-bit key: -0 equals +0; a NaN
+ *              with the sign bit clear ranks before +inf (first), a NaN with the sign bit set after -inf (last), NaNs of one
+ *              sign among themselves by payload.  The reference's key 0.5f * (D - s) is a non-increasing function of s and
+ *              its argsort is not stable: this order is one of the orders the reference can itself produce.
+ *   relevance  (qlab[q] & dblab[row]) != 0 over the lwords words.
+ *   AP         over the first k positions with the arithmetic and the summation order of wv_map_at_k: ap and nrel equal, bit
+ *              for bit, wv_map_at_k applied to the idx wv_knn_float(IP, k) returns for the same inputs.  A query without a
+ *              hit: ap = 0, nrel = 0.
+ * Arguments are checked on the host before any launch, the message names the argument: WV_EINVAL for a null pointer (nrel
+ * excepted), Q < 0, N < 1, D < 1, k outside [1, N], lwords outside {1, 2}; WV_ENOTSUP for N > WV_IP_MAP_ROWS_MAX (the ranked
+ * list of a query lives in one workgroup's LDS) or D > 512 (the staged query row), the message names the limit.  Q = 0 writes
+ * nothing and returns 0.  No workspace, asynchronous on `stream`, no hidden synchronisation.
+ * _cpu: host twin (HOST pointers, no stream; csrc/host_ip_map.cpp): the composition of wv_knn_float_cpu and wv_map_at_k_cpu the
+ * contract is defined by, under the same argument rules.
+ * ------------------------------------------------------------------------------------------ */
+#define WV_IP_MAP_ROWS_MAX 2048
+int wv_ip_map_at_k(const float *q, const float *db, int Q, int64_t N, int D, const uint64_t *qlab, const uint64_t *dblab,
+                   int lwords, int k, float *ap, int32_t *nrel, void *stream);
+int wv_ip_map_at_k_cpu(const float *q, const float *db, int Q, int64_t N, int D, const uint64_t *qlab, const uint64_t *dblab,
+                       int lwords, int k, float *ap, int32_t *nrel);
 
 /* ------------------------------------------------------------------------------------------
  * Band-attention pooling head + hashing tail (eval mode).

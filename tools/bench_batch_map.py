@@ -1,0 +1,131 @@
+"""The batch mAP proxy in ONE run: wv_ip_map_at_k against the composed path it replaces and against the reference's op sequence,
+on same-source minibatches B = 96, 256, 1024 of D = 64 real-valued embeddings (tanh values), 38 classes at p = 0.10,
+k = "max_bin_count" (resolved once per batch).
+
+    python tools/bench_batch_map.py [--out profiles/batch_map.json] [--rounds 6] [--calls 5]
+
+Per batch size, after a warm-up of every variant, variants alternating inside every round, median [min, max] over
+rounds x calls (>= 20) single calls:
+  fused_ms         hamming.ip_map_at_k: one launch.  HIP events around the call (allocation of the two outputs included)
+  composed_ms      knn_float(IP, k) + hamming.map_at_k on the same inputs: the path that gives the same bits.  HIP events
+  proxy_ms         compute_batch_map end to end, as train_step calls it (label packing, max_bin_count, the +-1 test, the launch,
+                   the .item()): host clock around the call, which ends in a device synchronise
+  reference_ms     the reference's calculate_maphashing op sequence restated in torch ON THE DEVICE (per query: label matmul,
+                   0.5 * (D - q @ r.T), argsort, gather, slice, two .item()): host clock, the same way
+The numbers of the variants are compared first: fused and composed bit for bit, the proxy against the restated sequence to
+1e-6.  HIP-event times of sub-10 us kernels are launch-gap times as much as kernel times: they are what a caller waits for
+on the stream, not a kernel's share of any peak.  Prints one JSON row.
+"""
+import argparse
+import json
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path[:0] = [".", "image-retrieval-wavelet_amd"]
+from wvhash import _lib  # noqa: E402
+from wvhash.engine import batch_map, hamming as H  # noqa: E402
+from wvhash.engine.get_knn import knn_float  # noqa: E402
+
+BATCHES, D, CLASSES, P_TAG = (96, 256, 1024), 64, 38, 0.10
+
+
+def event_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def host_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def reference_sequence(emb, lab):
+    """calculate_maphashing(query = reference = the batch, topk = "max_bin_count", ref_includes_query=True) op for op"""
+    rel = (lab @ lab.t()) > 0
+    topk = int(rel.sum(dim=1).max().item()) - 1
+    nbits, total = emb.shape[1], 0.0
+    for i in range(emb.shape[0]):
+        gnd = ((lab[i:i + 1] @ lab.t()) > 0).float().squeeze()
+        hamm = (0.5 * (nbits - emb[i:i + 1] @ emb.t())).squeeze()
+        tgnd = gnd[torch.argsort(hamm)][0:topk]
+        tsum = torch.sum(tgnd).int().item()
+        if tsum == 0:
+            continue
+        tindex = torch.where(tgnd == 1)[0].float() + 1.0
+        count = torch.arange(1, tsum + 1, device=emb.device).float()
+        total += torch.mean(count / tindex).item()
+    return total / emb.shape[0]
+
+
+def spread(v):
+    return {"ms": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--calls", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_batch_map: needs the GPU (a time measured elsewhere says nothing about it)")
+    calc, name = batch_map.build_batch_map_calculator("hamming", None)
+    rows = []
+    for B in BATCHES:
+        g = torch.Generator().manual_seed(B)
+        emb = torch.tanh(torch.randn(B, D, generator=g)).cuda()
+        lab = (torch.rand(B, CLASSES, generator=g) < P_TAG).float().cuda()
+        lp = H.pack_labels(lab)
+        k = int(((lab @ lab.t()) > 0).sum(1).max().item()) - 1
+
+        def composed():
+            _, idx = knn_float(emb, emb, k, _lib.WV_METRIC_IP)
+            return H.map_at_k(idx, lp, lp, k=k)
+
+        variants = {"fused": (event_ms, lambda: H.ip_map_at_k(emb, emb, lp, lp, k)), "composed": (event_ms, composed),
+                    "proxy": (host_ms, lambda: batch_map.compute_batch_map(calc, name, emb, lab)),
+                    "reference": (host_ms, lambda: reference_sequence(emb, lab))}
+        a, b = variants["fused"][1](), composed()
+        same_bits = bool(torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)) and torch.equal(a[1], b[1]))
+        proxy, ref = variants["proxy"][1](), variants["reference"][1]()
+        for _ in range(3):                                                   # warm-up: code objects, allocator, clocks
+            for _, fn in variants.values():
+                fn()
+        torch.cuda.synchronize()
+        ms = {v: [] for v in variants}
+        for _ in range(args.rounds):                                         # alternating
+            for v, (clock, fn) in variants.items():
+                ms[v] += [clock(fn) for _ in range(args.calls)]
+        med = {v: statistics.median(t) for v, t in ms.items()}
+        rows.append({"B": B, "D": D, "k": k, "fused_equals_composed_bits": same_bits, "proxy": round(proxy, 9),
+                     "reference_sequence": round(ref, 9), "proxy_minus_reference": abs(proxy - ref),
+                     "calls_per_variant": args.rounds * args.calls,
+                     "fused": spread(ms["fused"]), "composed": spread(ms["composed"]),
+                     "composed_over_fused": round(med["composed"] / med["fused"], 3),
+                     "fused_faster_than_composed": bool(med["fused"] < med["composed"]),
+                     "proxy_end_to_end": spread(ms["proxy"]), "reference_torch_on_device": spread(ms["reference"]),
+                     "reference_over_proxy": round(med["reference"] / med["proxy"], 2)})
+    row = {"what": "wv_ip_map_at_k (one launch) against knn_float(IP, k) + map_at_k, and compute_batch_map against the "
+                   "reference's op sequence in torch on the device; same-source batches, tanh embeddings",
+           "device": torch.cuda.get_device_name(0), "classes": CLASSES, "p_tag": P_TAG,
+           "clocks": {"fused, composed": "HIP events around one call", "proxy, reference": "host clock around one call ending in a synchronise"},
+           "shapes": rows}
+    line = json.dumps(row)
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
