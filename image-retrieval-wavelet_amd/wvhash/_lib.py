@@ -26,6 +26,8 @@ WV_TOKENS_SBE, WV_TOKENS_BSE = 0, 1      # band tokens as [S][B][E] (wv_band_att
 WV_RESAMPLE_BILINEAR, WV_RESAMPLE_BICUBIC = 2, 3      # PIL's enum values
 WV_COLOUR_BRIGHTNESS, WV_COLOUR_CONTRAST, WV_COLOUR_SATURATION = 0, 1, 2
 WV_IP_MAP_ROWS_MAX = 2048   # include/wvhash.h: rows wv_ip_map_at_k ranks in one workgroup
+WV_PAIR_LOSS_SCH, WV_PAIR_LOSS_HASHNET = 0, 1
+WV_PAIR_LOSS_ROWS_MAX = 2048   # include/wvhash.h: rows of a batch wv_pair_loss takes (D <= 512)
 WV_ENOTSUP = -95            # return code: the shape is outside the kernel asked for (callers fall back)
 
 
@@ -70,6 +72,12 @@ class ColourOps(ctypes.Structure):
     """wv_colour_ops: the colour operations of one image, in the order they run; 48 bytes = 12 32-bit words."""
     _fields_ = [("offset", ctypes.c_int64), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("row_bytes", ctypes.c_int32),
                 ("n_ops", ctypes.c_int32), ("kind", ctypes.c_int32 * 3), ("factor", ctypes.c_float * 3)]
+
+
+class PairLossParams(ctypes.Structure):
+    """wv_pair_loss_params: which pairwise loss (WV_PAIR_LOSS_*) and its constants; 24 bytes."""
+    _fields_ = [("kind", ctypes.c_int), ("apply_tanh", ctypes.c_int), ("pre_scale", ctypes.c_float),
+                ("nbits", ctypes.c_float), ("alpha", ctypes.c_float), ("beta", ctypes.c_float)]
 
 
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
@@ -176,6 +184,9 @@ SIGNATURES = {
     "wv_group_layernorm_cpu": (_i, [_vp, _i, _vp, _i, _i64, _i64, _i, _i, _vp, _vp, _f]),
     "wv_ip_map_at_k": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "wv_ip_map_at_k_cpu": (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "wv_pair_loss_workspace_bytes": (_sz, [_i, _i]),
+    "wv_pair_loss": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(PairLossParams), _vp, _vp, _vp, _sz, _vp]),
+    "wv_pair_loss_cpu": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(PairLossParams), _vp, _vp]),
 }
 
 _LIB = None

@@ -251,6 +251,8 @@ def train_step(net, images, labels, criteria, optimizers, averager=None, autocas
         if own is not None:
             scaler.step(own) if scaler is not None else own.step()
             own.zero_grad()
+        elif hasattr(crit, "step"):     # a schedule of the loss's own (HashNetAdapter's continuation scale), base_update.py:380-390
+            crit.step()
     net.zero_grad()
     for crit, _ in criteria:
         crit.zero_grad()

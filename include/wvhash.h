@@ -62,6 +62,7 @@ const char *wv_last_error(void);
  * So was the single-band SWT (wv_swt2d_band_forward, wv_swt2d_band_forward_cpu): 94 symbols.
  * So was the grouped LayerNorm (wv_group_layernorm, wv_group_layernorm_cpu, wv_group_layernorm_check): 97 symbols.
  * So was the batch mAP proxy of real-valued embeddings (wv_ip_map_at_k, wv_ip_map_at_k_cpu): 99 symbols.
+ * So were the pairwise hashing losses (wv_pair_loss[_workspace_bytes], wv_pair_loss_cpu, struct wv_pair_loss_params): 102 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -765,6 +766,50 @@ int wv_group_layernorm(const void *x, int x_dtype, void *out, int out_dtype, int
                        const float *gamma, const float *beta, float eps, void *stream);
 int wv_group_layernorm_cpu(const void *x, int x_dtype, void *out, int out_dtype, int64_t N, int64_t T, int E, int G,
                            const float *gamma, const float *beta, float eps);
+
+/* ------------------------------------------------------------------------------------------
+ * Pairwise hashing losses: value AND gradient w.r.t. the embeddings of SCHLoss.forward (main/losses/dsch.py:31-59) and
+ * HashNetLoss.forward (main/losses/hashnet_loss.py:49-66) -- in the reference about 25 elementwise, boolean-index and reduction
+ * ops on [B, B] tensors, forward and again backward.  Here two launches; no [B, B] matrix reaches memory.
+ *   e      [B][D] float32, dense: the embeddings
+ *   labels [B][lwords]: multi-hot labels packed by wv_pack_bits(mode 1)
+ *   out    float32 [3]: the loss and its two parts (SCH: loss1, loss2; HashNet: the means over the pairs that share a label and
+ *          over those that do not)
+ *   grad   float32 [B][D]: d loss / d e, or NULL -- then that part of the work is skipped and `out` has the same bits.
+ * With n_i = |L_i|, c_ij = |L_i & L_j|, u = tanh(pre_scale * e) (apply_tanh != 0) or pre_scale * e, G = u u^T:
+ *   WV_PAIR_LOSS_SCH      k = nbits; S = c / sqrt(n_i n_j) (0 where n_i n_j = 0); same: c = n_i = n_j > 0; disjoint: c = 0;
+ *                         lambda = (1 - S) k / 2; lambda_l = max(lambda - 3, 0), k / 2 where disjoint; W_l = 0 | beta | 1 and
+ *                         W_u = alpha | 0 | 1 for same | disjoint | other; H = (k - G) / 2;
+ *                         loss = |relu(lambda_l - H) W_l|_F / B^2 + |relu(H - lambda) W_u|_F / B^2, diagonal included.  A part
+ *                         whose norm is 0 has gradient 0 (torch.norm's backward), never NaN.  `same` is the exact set relation,
+ *                         not the reference's fp32 test S == 1.
+ *   WV_PAIR_LOSS_HASHNET  P = c > 0; dp = alpha G; t = softplus(dp) - P dp; S1 = #P, S0 = B^2 - S1;
+ *                         loss = sum_P t / S1 + sum_notP t / S0, an empty class contributing nothing.  nbits, beta unused.
+ * fp32 arithmetic (G by fmaf), the two global sums in double.  No floating-point atomics: the same call gives the same bits.
+ * Everything is enqueued on `stream`; no hidden synchronisation.
+ * workspace: device memory of wv_pair_loss_workspace_bytes(B, D) bytes (two [B][D] fp32 sums + one record per 8 rows).
+ * Arguments are checked on the host before any pointer is read: WV_EINVAL for a null pointer (grad excepted), B < 1, D < 1,
+ * lwords outside {1, 2}, an unknown kind, pre_scale <= 0, a workspace shorter than the query says; WV_ENOTSUP for
+ * B > WV_PAIR_LOSS_ROWS_MAX or D > 512; the message names the argument.
+ * _cpu: host twin (HOST pointers, no workspace, no stream; csrc/host_pair_loss.cpp) under the same rules, the same per-pair
+ * code (csrc/pair_loss.hpp); it agrees with the kernel to fp32 rounding, not bit for bit (device tanh / exp / log1p).
+ * ------------------------------------------------------------------------------------------ */
+#define WV_PAIR_LOSS_SCH 0
+#define WV_PAIR_LOSS_HASHNET 1
+#define WV_PAIR_LOSS_ROWS_MAX 2048
+typedef struct wv_pair_loss_params {
+    int kind;        /* WV_PAIR_LOSS_* */
+    int apply_tanh;  /* u = tanh(pre_scale * e) instead of pre_scale * e */
+    float pre_scale; /* > 0; HashNet's continuation scale, 1 for SCH */
+    float nbits;     /* SCH: k */
+    float alpha;     /* SCH: W_u of `same` pairs; HashNet: the factor of G inside the sigmoid */
+    float beta;      /* SCH: W_l of `disjoint` pairs */
+} wv_pair_loss_params;
+size_t wv_pair_loss_workspace_bytes(int B, int D);
+int wv_pair_loss(const float *e, const uint64_t *labels, int lwords, int B, int D, const struct wv_pair_loss_params *p,
+                 float *out, float *grad, void *workspace, size_t workspace_bytes, void *stream);
+int wv_pair_loss_cpu(const float *e, const uint64_t *labels, int lwords, int B, int D, const struct wv_pair_loss_params *p,
+                     float *out, float *grad);
 
 #ifdef __cplusplus
 }
