@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from ._prepared import PreparedCache, param_key
 
 _DTYPES = {torch.float32: _lib.WV_DT_F32, torch.bfloat16: _lib.WV_DT_BF16}
 
@@ -64,17 +65,16 @@ class MultiDomainLayerNorm(nn.Module):
                     norm.bias.copy_(original_norm.bias)
         self.kernel_calls = 0
         self.stock_calls = 0
-        self._stacked = None            # (key, gamma [G, E], beta [G, E]): rebuilt when a parameter changes or moves
+        self._prepared = PreparedCache()    # slot "affine": (gamma [G, E], beta [G, E]), rebuilt when a parameter changes or moves
 
     def _affine(self, device):
-        params = [p for norm in self.norms for p in (norm.weight, norm.bias)]
-        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
-        if self._stacked is None or self._stacked[0] != key:
+        def build():
             with torch.no_grad():
                 gamma = torch.stack([norm.weight.detach().float() for norm in self.norms]).contiguous()
                 beta = torch.stack([norm.bias.detach().float() for norm in self.norms]).contiguous()
-            self._stacked = (key, gamma, beta)
-        return self._stacked[1], self._stacked[2]
+            return gamma, beta
+        params = [p for norm in self.norms for p in (norm.weight, norm.bias)]
+        return self._prepared.get("affine", device, param_key(*params), build)
 
     def _library_path(self, x):
         first = self.norms[0]

@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
+from ._prepared import PreparedCache, param_key
 
 LOGGER = logging.getLogger("RETRIEVAL")
 
@@ -69,83 +70,87 @@ def _head_params(S, E, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mea
     return p, keep
 
 
+Prepared = collections.namedtuple("Prepared", "blob qp")
+
+
+def _prepared_key(query_key, q_src, watched, *config):
+    """Key of what is prepared from the parameters: the identity of what q_eff was made from (query_key; by default q_eff
+    itself), of the watched weights, and the configuration the layout depends on."""
+    return (query_key if query_key is not None else param_key(q_src), param_key(*watched)) + config
+
+
 def band_attn_pool(features_list, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mean=False,
-                   workspace=None, qproj_cache=None, qproj_key=None, matrix_dtype=None, bf16_cache=None):
+                   cache=None, query_key=None, matrix_dtype=None, workspace=None):
     """HIP forward of the attention-pooling core.  features_list: S x [B, E] CUDA fp32.
     matrix_dtype: None = the fp32 matrix-core path; torch.bfloat16 / "bf16" / "auto" (see resolve_matrix_dtype) = the bf16
     path (wv_band_attn_pool_bf16: bf16 operands, fp32 accumulation, fp32 output), which also takes bf16 features as they
-    are; bf16_cache: a dict owned by the module for that path's prepared blob -- separate from qproj_cache, so that
-    alternating precisions rebuilds neither.
-    qproj_cache: a dict owned by the module; holds what is made from parameters alone -- the projected query tokens and,
-    for the configurations with a one-launch front (wv_band_attn_prepared_bytes), the fragment-ordered copy of the
-    weights -- so that it is rebuilt when a parameter changes, not in every call; qproj_key identifies the parameters
-    q_eff was made from (storage pointers + version counters)."""
+    are.
+    cache: the module's PreparedCache; holds, per device, what is made from parameters alone, so that it is rebuilt when a
+    parameter changes, not in every call.  Slot "fp32": the projected query tokens (`qp`) or, for the configurations with a
+    one-launch front (wv_band_attn_prepared_bytes), the fragment-ordered copy of the weights (`blob`); slot "bf16": that
+    path's prepared blob -- separate slots, so that alternating precisions rebuilds neither.  Without a cache nothing is
+    kept: the fp32 path projects the queries in the call, the bf16 path builds a blob for this call alone.
+    query_key identifies the parameters q_eff was made from (param_key).
+    workspace: a caller-owned uint8 buffer for this one call; by default a fresh allocation of the advertised size."""
     lib = _lib.require_gpu()
     use_bf16 = resolve_matrix_dtype(matrix_dtype) == "bf16"
     feats = _stacked(features_list, keep_bf16=use_bf16)                               # [S, B, E]
     S, B, E = feats.shape
+    dev = feats.device
     q_src = q_eff
     q_eff = q_eff.detach().float().reshape(-1, E).contiguous()
     p, keep = _head_params(S, E, q_eff, attn, norm1, norm2, mlp0, mlp2, out_proj, pool_mean)
     for t in keep:
         if not t.is_cuda:
             raise ValueError("band_attn_pool: module parameters must live on the GPU")
-    out = torch.empty((B, E), dtype=torch.float32, device=feats.device)
+    out = torch.empty((B, E), dtype=torch.float32, device=dev)
     if B == 0:
         return out
+    # the query tokens and the weights are parameters: key on their storage and version counters
+    watched = (attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, mlp0.weight, mlp2.weight)
     if use_bf16:
-        return _band_attn_pool_bf16(lib, p, feats, out, workspace, bf16_cache, qproj_key, q_src, attn, mlp0, mlp2, out_proj)
-    if qproj_cache is not None:
-        # the query tokens and the weights are parameters: key on their storage and version counters
-        watched = (attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, mlp0.weight, mlp2.weight)
-        key = (qproj_key if qproj_key is not None else (q_src.data_ptr(), q_src._version),
-               tuple((t.data_ptr(), t._version) for t in watched), attn.num_heads, S, feats.device)
-        if qproj_cache.get("key") != key:
-            with torch.cuda.device(feats.device):
+        key = _prepared_key(query_key, q_src, watched + (out_proj.weight,), attn.num_heads, S, p.pool_mean)
+        return _band_attn_pool_bf16(lib, p, feats, out, workspace, cache, key)
+    if cache is not None:
+        def build():
+            with torch.cuda.device(dev):
                 nbytes = lib.wv_band_attn_prepared_bytes(ctypes.byref(p))
                 if nbytes:      # this configuration has the one-launch front: projected queries + fragment-ordered weights
-                    blob = torch.empty(nbytes, dtype=torch.uint8, device=feats.device)
+                    blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
                     _lib.check(lib.wv_band_attn_prepare(ctypes.byref(p), _lib.ptr(blob), _lib.stream_ptr()), "wv_band_attn_prepare")
-                    entry = dict(key=key, blob=blob, qp=None)
-                else:
-                    qp = torch.empty_like(q_eff)
-                    _lib.check(lib.wv_band_attn_qproj(ctypes.byref(p), _lib.ptr(qp), _lib.stream_ptr()), "wv_band_attn_qproj")
-                    entry = dict(key=key, blob=None, qp=qp)
-            qproj_cache.clear()
-            qproj_cache.update(entry)
-        if qproj_cache["blob"] is not None:
-            p.prepared = qproj_cache["blob"].data_ptr()
+                    return Prepared(blob, None)
+                qp = torch.empty_like(q_eff)
+                _lib.check(lib.wv_band_attn_qproj(ctypes.byref(p), _lib.ptr(qp), _lib.stream_ptr()), "wv_band_attn_qproj")
+                return Prepared(None, qp)
+        prepared = cache.get("fp32", dev, _prepared_key(query_key, q_src, watched, attn.num_heads, S), build)
+        if prepared.blob is not None:
+            p.prepared = prepared.blob.data_ptr()
         else:
-            p.q_proj = qproj_cache["qp"].data_ptr()
+            p.q_proj = prepared.qp.data_ptr()
     ws_bytes = lib.wv_band_attn_pool_workspace_bytes(ctypes.byref(p), B)
-    if workspace is None or workspace.numel() < ws_bytes or workspace.device != feats.device:
-        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=feats.device)
-    with torch.cuda.device(feats.device):
+    if workspace is None or workspace.numel() < ws_bytes or workspace.device != dev:
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
         rc = lib.wv_band_attn_pool(ctypes.byref(p), _lib.ptr(feats), B, _lib.ptr(out), _lib.ptr(workspace),
                                    ctypes.c_size_t(workspace.numel()), _lib.stream_ptr())
         _lib.check(rc, "wv_band_attn_pool")
     return out
 
 
-def _band_attn_pool_bf16(lib, p, feats, out, workspace, cache, qproj_key, q_src, attn, mlp0, mlp2, out_proj):
+def _band_attn_pool_bf16(lib, p, feats, out, workspace, cache, key):
     """The bf16 matrix-core path: prepared blob (projected queries + bf16 weights) from `cache`, then one call."""
     S, B, E = feats.shape
     dev = feats.device
-    watched = (attn.in_proj_weight, attn.in_proj_bias, attn.out_proj.weight, mlp0.weight, mlp2.weight, out_proj.weight)
-    key = (qproj_key if qproj_key is not None else (q_src.data_ptr(), q_src._version),
-           tuple((t.data_ptr(), t._version) for t in watched), attn.num_heads, S, p.pool_mean, dev)
-    entry = cache.get("entry") if cache is not None else None
-    if entry is None or entry[0] != key:
+
+    def build():
         with torch.cuda.device(dev):
             nbytes = lib.wv_band_attn_bf16_prepared_bytes(ctypes.byref(p))
             if not nbytes:      # never a silent fp32 run
                 raise _lib.WvhashError("wv_band_attn_bf16_prepared_bytes: " + lib.wv_last_error().decode(errors="replace"))
             blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             _lib.check(lib.wv_band_attn_bf16_prepare(ctypes.byref(p), _lib.ptr(blob), _lib.stream_ptr()), "wv_band_attn_bf16_prepare")
-        entry = (key, blob)
-        if cache is not None:
-            cache["entry"] = entry          # one assignment: a replica that reads the dict sees the old or the new pair
-    blob = entry[1]
+        return Prepared(blob, None)
+    blob = (cache.get("bf16", dev, key, build) if cache is not None else build()).blob
     ws_bytes = lib.wv_band_attn_pool_bf16_workspace_bytes(ctypes.byref(p), B)
     if workspace is None or workspace.numel() < ws_bytes or workspace.device != dev:
         workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -285,12 +290,10 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
         in_dim = embed_dim if self._pool == "mean" else num_queries * embed_dim
         self.out_proj = nn.Linear(in_dim, embed_dim)
         self.last_ortho_loss = 0.0
-        self._ws = None
         self._zero_loss = None
-        self._qproj_cache = {}
+        self._prepared = PreparedCache()        # slots "fp32" and "bf16" (band_attn_pool); shared with replicas, on purpose
         # None: fp32 matrix cores (default); torch.bfloat16 / "bf16": the bf16 path; "auto": bf16 under bf16 autocast
         self.matrix_dtype = None
-        self._bf16_cache = {}
 
     # -- pieces shared by the four variants ------------------------------------------------
     def compute_ortho_loss(self):
@@ -307,7 +310,7 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
 
     def _query_key(self):
         """Identity of the parameters effective_queries() is made from (for the cached query projection)."""
-        return tuple((t.data_ptr(), t._version) for t in (self.query_tokens,))
+        return param_key(self.query_tokens)
 
     def _ortho_after_attention(self, attn_weights, mask_ll, device):
         if self.training and self.ortho_weight > 0:
@@ -392,9 +395,8 @@ class CrossAttentionBottleneckHeadAdvanced(nn.Module):
                 self._observe_attention(kv_list, batch_size)
             with torch.no_grad():
                 out = band_attn_pool(kv_list, self.effective_queries(), self.attn, self.norm1, self.norm2,
-                                     self.mlp[0], self.mlp[2], self.out_proj, self._pool == "mean", self._ws,
-                                     self._qproj_cache, self._query_key(), matrix_dtype=self.matrix_dtype,
-                                     bf16_cache=self._bf16_cache)
+                                     self.mlp[0], self.mlp[2], self.out_proj, self._pool == "mean", self._prepared,
+                                     self._query_key(), matrix_dtype=self.matrix_dtype)
             return out
 
         # training / unsupported shapes: stock PyTorch on the GPU (outside the accelerated path)
@@ -461,7 +463,7 @@ class CrossAttentionBottleneckHeadDecoupled(CrossAttentionBottleneckHeadAdvanced
         return q * self.query_scale
 
     def _query_key(self):
-        return tuple((t.data_ptr(), t._version) for t in (self.query_tokens, self.query_scale)) + (self.normalize_queries,)
+        return param_key(self.query_tokens, self.query_scale) + (self.normalize_queries,)
 
 
 _HIP_TYPES = {

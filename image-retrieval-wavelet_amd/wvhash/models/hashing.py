@@ -68,6 +68,22 @@ def hash_tail(fused, hash_fc, bn, want=("codes",), host_twin=False):
     return out
 
 
+def library_tail(module, features):
+    """-> (take, host): whether hash_tail serves this call -- eval mode, no grad, GPU tensors or host tensors of a model with
+    ``host_twin = True`` (explicit; never a silent fallback) -- and whether it is the host twin that does."""
+    host = not features.is_cuda and getattr(module, "host_twin", False)
+    take = not module.training and not torch.is_grad_enabled() and (features.is_cuda or host)
+    return take, host
+
+
+def freeze_backbone(module):
+    """A frozen backbone: no gradients, eval mode, and it stays in eval mode when the model around it is put in train mode."""
+    for p in module.parameters():
+        p.requires_grad = False
+    module.eval()
+    module.train = lambda mode=False: None
+
+
 def _cls(out):
     return out['x_norm_clstoken'] if isinstance(out, dict) else out
 
@@ -155,8 +171,8 @@ class _WaveletHashingBase(nn.Module):
         return tf.apply_band(x, index, channels_last=channels_last, out_dtype=self._band_dtype())
 
     def _tail(self, fused_embedding):
-        host = not fused_embedding.is_cuda and getattr(self, "host_twin", False)      # explicit: model.host_twin = True
-        if not self.training and (fused_embedding.is_cuda or host) and not torch.is_grad_enabled():
+        take, host = library_tail(self, fused_embedding)
+        if take:
             return hash_tail(fused_embedding, self.hash_fc, self.bn, want=("codes",), host_twin=host)["codes"]
         logits = self.bn(self.hash_fc(fused_embedding))
         return self._train_output(logits) if self.training else torch.sign(logits)
@@ -172,10 +188,7 @@ class SharedDinoHashing(_WaveletHashingBase):
         super().__init__()
         self.shared_backbone = backbone if backbone is not None else load_dinov2(backbone_config['name'])
         if backbone_config.get('frozen', True):
-            for p in self.shared_backbone.parameters():
-                p.requires_grad = False
-            self.shared_backbone.eval()
-            self.shared_backbone.train = lambda mode=False: None
+            freeze_backbone(self.shared_backbone)
         embed_dim = self.shared_backbone.embed_dim
         self.fusion_head = get_fusion_head(fusion_config, [embed_dim] * 4)
         self.nbits = binary_config['nbits']
@@ -205,10 +218,7 @@ class MultiDinoHashing(_WaveletHashingBase):
         for i, bb_cfg in enumerate(backbones_config):
             model = backbones[i] if backbones is not None else load_dinov2(bb_cfg['name'])
             if bb_cfg.get('frozen', True):
-                for p in model.parameters():
-                    p.requires_grad = False
-                model.eval()
-                model.train = lambda mode=False: None
+                freeze_backbone(model)
             self.backbones.append(model)
             output_dims.append(model.embed_dim)
         self.fusion_head = get_fusion_head(fusion_config, output_dims)
@@ -248,10 +258,7 @@ class PromptedSharedDinoHashing(_WaveletHashingBase):
             for blk in self.shared_backbone.blocks:
                 blk.norm1.emit_dtype = blk.norm2.emit_dtype = "auto"
         if backbone_config.get('frozen', True):
-            for p in self.shared_backbone.parameters():
-                p.requires_grad = False
-            self.shared_backbone.eval()
-            self.shared_backbone.train = lambda mode=False: None
+            freeze_backbone(self.shared_backbone)
         embed_dim = self.shared_backbone.embed_dim
         self.num_prompts = num_prompts
         self.prompts = nn.Parameter(torch.randn(4, num_prompts, embed_dim) * 0.02)

@@ -16,13 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .hashing import _WaveletHashingBase, _cls, hash_tail, load_dinov2
-
-
-def _hip_tail(module, features):
-    """The eval-mode, no-grad case hash_tail serves: GPU tensors, or host tensors of a model with host_twin = True."""
-    host = not features.is_cuda and getattr(module, "host_twin", False)
-    return not module.training and not torch.is_grad_enabled() and (features.is_cuda or host), host
+from .hashing import _WaveletHashingBase, _cls, freeze_backbone, hash_tail, library_tail, load_dinov2
 
 
 class SingleBandNet(_WaveletHashingBase):
@@ -52,8 +46,8 @@ class SingleBandNet(_WaveletHashingBase):
         features = self.features(x)
         if not self.is_hashing:
             return F.normalize(self.head(features), p=2, dim=1)
-        hip, host = _hip_tail(self, features)
-        if hip:
+        take, host = library_tail(self, features)
+        if take:
             return hash_tail(features, self.head, self.bn, want=("codes",), host_twin=host)["codes"]
         out = self.bn(self.head(features))
         return out if self.training else torch.sign(out)      # raw logits in training: HashLoss applies the tanh
@@ -74,10 +68,7 @@ class DINOHashBaseline(nn.Module):
         self.backbone = backbone if backbone is not None else load_dinov2(dino_backbone)
         self.frozen = frozen
         if frozen:
-            for p in self.backbone.parameters():
-                p.requires_grad = False
-            self.backbone.eval()
-            self.backbone.train = lambda mode=False: None
+            freeze_backbone(self.backbone)
         self.hash_head = nn.Sequential(
             nn.Linear(embed_dim, binary_config['nbits'], bias=False),
             nn.BatchNorm1d(binary_config['nbits'])
@@ -90,8 +81,8 @@ class DINOHashBaseline(nn.Module):
 
     def forward(self, x):
         features = self.features(x)
-        hip, host = _hip_tail(self, features)
-        if hip:
+        take, host = library_tail(self, features)
+        if take:
             return hash_tail(features, self.hash_head[0], self.hash_head[1], want=("codes",), host_twin=host)["codes"]
         logits = self.hash_head(features)
         return logits if self.training else torch.sign(logits)

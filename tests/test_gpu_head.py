@@ -4,6 +4,9 @@ REFERENCE's own modules (tests/golden/head_golden.npz) and against oracle/head_t
 Tolerance: every contraction is fp32 (v_mfma_f32_32x32x2_f32 = fmaf chain); only the summation
 order differs from ATen's blocked fp32 GEMM.  Outputs are LayerNorm'ed (|y| ~ 3): atol 5e-5.
 """
+import copy
+import threading
+
 import numpy as np
 import pytest
 import torch
@@ -82,7 +85,7 @@ def run_fronts(head, dev, diag):
     with torch.no_grad():
         diag.delenv("WV_HEAD_FRONT", raising=False)
         outs["auto"] = head(dev).cpu()
-        if head._qproj_cache["blob"] is not None:
+        if head._prepared.peek("fp32", dev[0].device)[1].blob is not None:
             for front in ("0", "1"):
                 diag.setenv("WV_HEAD_FRONT", front)
                 outs[front] = head(dev).cpu()
@@ -175,7 +178,7 @@ def test_one_launch_front_against_separate_launches_and_oracle(nq, heads, B, dia
         for front in ("1", "0"):
             diag.setenv("WV_HEAD_FRONT", front)
             out[front] = head(dev).cpu()
-    assert head._qproj_cache["blob"] is not None                 # this configuration has a prepared stream
+    assert head._prepared.peek("fp32", dev[0].device)[1].blob is not None                 # this configuration has a prepared stream
     assert not torch.equal(out["0"], out["1"])                   # two different kernels did run
     assert (out["0"] - out["1"]).abs().max().item() < 2e-5
     ref = head_torch.band_attn_pool(feats, sd, heads, dtype=torch.float64)
@@ -201,7 +204,8 @@ def test_front_is_chosen_by_batch_size_and_unsupported_shapes_fall_back(diag):
     other = other.cuda().eval()                                   # E = 64 has no fused kernel: no blob, separate launches
     with torch.no_grad():
         y = other([f.cuda() for f in synth.band_features(5, 64, seed=3)])
-    assert other._qproj_cache["blob"] is None and other._qproj_cache["qp"] is not None and torch.isfinite(y).all()
+    prepared = other._prepared.peek("fp32", y.device)[1]
+    assert prepared.blob is None and prepared.qp is not None and torch.isfinite(y).all()
 
 
 def test_hip_path_equals_stock_torch_forward_of_same_module():
@@ -325,12 +329,12 @@ def test_cached_query_projection_follows_parameter_updates(ftype, front, diag):
     with torch.no_grad():
         y0 = head(feats)
         assert (y0.cpu() - ref()).abs().max() < ATOL
-        key0 = head._qproj_cache["key"]
+        key0 = head._prepared.peek("fp32", y0.device)[0]
         head(feats)
-        assert head._qproj_cache["key"] == key0                       # second call: projection reused
+        assert head._prepared.peek("fp32", y0.device)[0] == key0                       # second call: projection reused
         head.query_tokens.mul_(1.5)
         y1 = head(feats)
-        assert head._qproj_cache["key"] != key0 and (y1.cpu() - ref()).abs().max() < ATOL
+        assert head._prepared.peek("fp32", y0.device)[0] != key0 and (y1.cpu() - ref()).abs().max() < ATOL
         head.attn.in_proj_weight.add_(0.01)
         y2 = head(feats)
         assert (y2.cpu() - ref()).abs().max() < ATOL and not torch.equal(y1, y2)
@@ -343,3 +347,61 @@ def test_cached_query_projection_follows_parameter_updates(ftype, front, diag):
             head.query_scale.mul_(0.5)
             y3 = head(feats)
             assert (y3.cpu() - ref()).abs().max() < ATOL and not torch.equal(y2, y3)
+
+
+@pytest.mark.parametrize("E,heads,B,alternate", [(384, 8, 9, True), (64, 4, 5, False)], ids=["e384_blob_and_bf16", "e64_qp"])
+def test_replicas_on_two_threads_share_one_prepared_cache(E, heads, B, alternate):
+    """Two replicas of one head (copy.copy: shared parameters, shared PreparedCache, as nn.DataParallel's replicas of one
+    device would) run from two threads on the same device and stream, before and after a parameter update.  E = 384 has the
+    prepared stream and alternates with the bf16 blob; E = 64 has neither and keeps the projected queries.  Every output is
+    bit-equal to that of a freshly built head with the same state and matrix_dtype."""
+    cfg = {"type": "cross_attention_advanced", "output_dim": E, "num_queries": 4, "num_heads": heads}
+    head = get_fusion_head(cfg, [E] * 4)
+    head.load_state_dict(synth.head_state(E, 4, "concat", seed=11))
+    head = head.cuda().eval()
+    a, b = copy.copy(head), copy.copy(head)
+    assert a._prepared is head._prepared and b._prepared is head._prepared and a.query_tokens is head.query_tokens
+    dev = [f.cuda() for f in synth.band_features(B, E, seed=12)]
+    plans = ([None, "bf16", None], ["bf16", None, "bf16"]) if alternate else ([None] * 3, [None] * 3)
+
+    def fresh(matrix_dtype):
+        single = get_fusion_head(cfg, [E] * 4)
+        single.load_state_dict({k: v.detach().cpu() for k, v in head.state_dict().items()})
+        single = single.cuda().eval()
+        single.matrix_dtype = matrix_dtype
+        with torch.no_grad():
+            return single(dev).cpu()
+
+    def two_threads():
+        outs, errors = {}, []
+
+        def worker(name, replica, plan):
+            try:
+                with torch.no_grad():
+                    for i, matrix_dtype in enumerate(plan):
+                        replica.matrix_dtype = matrix_dtype
+                        outs[name, i] = (matrix_dtype, replica(dev).cpu())
+            except Exception as e:                      # noqa: BLE001  reported below, in the main thread
+                errors.append((name, repr(e)))
+        threads = [threading.Thread(target=worker, args=args, daemon=True) for args in (("a", a, plans[0]), ("b", b, plans[1]))]
+        for th in threads:
+            th.start()
+        for th in threads:
+            th.join(timeout=60)
+            assert not th.is_alive(), "a replica's thread did not finish"
+        assert not errors, errors
+        assert len(outs) == 6
+        want = {matrix_dtype: fresh(matrix_dtype) for matrix_dtype in set(plans[0] + plans[1])}
+        for (name, i), (matrix_dtype, y) in sorted(outs.items()):
+            assert torch.equal(y, want[matrix_dtype]), (name, i, matrix_dtype)
+        return want
+
+    before = two_threads()
+    prepared = head._prepared.peek("fp32", dev[0].device)[1]
+    assert (prepared.blob is not None and prepared.qp is None) if alternate else (prepared.blob is None and prepared.qp is not None)
+    assert (head._prepared.peek("bf16", dev[0].device) is not None) == alternate
+    with torch.no_grad():
+        head.query_tokens.mul_(1.5)
+    after = two_threads()
+    for matrix_dtype, y in after.items():
+        assert not torch.equal(y, before[matrix_dtype]), matrix_dtype       # the update reached every replica

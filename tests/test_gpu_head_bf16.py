@@ -178,17 +178,18 @@ def test_auto_follows_autocast_and_the_c4_model_runs_end_to_end(gold):
 def test_parameter_update_invalidates_the_bf16_blob_only(gold):
     head, feats, _, _ = build("adv_e384_nq4", gold)
     y0_f32, y0 = run(head, feats, None), run(head, feats, "bf16")
-    blob32 = head._qproj_cache.get("blob")
-    key32 = head._qproj_cache.get("key")
-    blob16 = head._bf16_cache["entry"][1]
-    assert torch.equal(run(head, feats, "bf16"), y0) and head._bf16_cache["entry"][1] is blob16      # cached
+    peek = lambda slot: head._prepared.peek(slot, head.query_tokens.device)        # noqa: E731   (key, Prepared(blob, qp))
+    key32, blob32 = peek("fp32")[0], peek("fp32")[1].blob
+    blob16 = peek("bf16")[1].blob
+    assert blob32 is not None and blob16 is not None
+    assert torch.equal(run(head, feats, "bf16"), y0) and peek("bf16")[1].blob is blob16              # cached
     run(head, feats, None)
-    assert head._bf16_cache["entry"][1] is blob16 and head._qproj_cache.get("key") == key32          # alternating rebuilds neither
+    assert peek("bf16")[1].blob is blob16 and peek("fp32")[0] == key32                                # alternating rebuilds neither
     with torch.no_grad():
         head.out_proj.weight.mul_(1.5)               # read-out weights: in the bf16 blob, not in the fp32 one
     y1 = run(head, feats, "bf16")
-    assert not torch.equal(y1, y0) and head._bf16_cache["entry"][1] is not blob16
-    assert head._qproj_cache.get("blob") is blob32 and head._qproj_cache.get("key") == key32          # fp32 blob untouched
+    assert not torch.equal(y1, y0) and peek("bf16")[1].blob is not blob16
+    assert peek("fp32")[1].blob is blob32 and peek("fp32")[0] == key32                                # fp32 blob untouched
     y1_f32 = run(head, feats, None)
     assert not torch.equal(y1_f32, y0_f32)           # (the fp32 path reads out_proj from the parameters)
     with torch.no_grad():
@@ -204,7 +205,7 @@ def test_default_is_the_existing_fp32_entry_point(gold):
         y = head(dev)
         direct = fusion.band_attn_pool(dev, head.effective_queries(), head.attn, head.norm1, head.norm2, head.mlp[0], head.mlp[2],
                                        head.out_proj, False)
-    assert torch.equal(y, direct) and not head._bf16_cache
+    assert torch.equal(y, direct) and head._prepared.peek("bf16", y.device) is None
 
 
 
@@ -310,7 +311,7 @@ def test_the_callers_buffers_are_written_only_where_they_are_owned(config, B):
         ws = torch.full((need + TAIL,), FILL, dtype=torch.uint8, device="cuda")
         ws[:need] = byte
         with torch.no_grad():
-            outs[name] = fusion.band_attn_pool(dev, *hc.module_args(head), workspace=ws, matrix_dtype="bf16", bf16_cache={}).cpu()
+            outs[name] = fusion.band_attn_pool(dev, *hc.module_args(head), workspace=ws, matrix_dtype="bf16").cpu()
         assert bool((ws[need:] == FILL).all()), f"{name}: bytes past the advertised workspace size were written"
     ys.check(outs["zeros"], f"caller workspace {config} B={B}")
     assert torch.equal(outs["zeros"], outs["nan"]), "the result depends on what the workspace held before the call"

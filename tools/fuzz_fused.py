@@ -37,7 +37,7 @@ for case in range(25):
             out[front] = head(dev).cpu()
     ref = head_torch.band_attn_pool(feats, sd, heads, dtype=torch.float64)
     e1, e0 = float((out["1"].double() - ref).abs().max()), float((out["0"].double() - ref).abs().max())
-    ok = e1 < 5e-5 and e0 < 5e-5 and head._qproj_cache["blob"] is not None
+    ok = e1 < 5e-5 and e0 < 5e-5 and head._prepared.peek("fp32", dev[0].device)[1].blob is not None
     bad += not ok
     print(f"head nq={nq} heads={heads} B={B}: front {e1:.1e} separate {e0:.1e} {'ok' if ok else 'BAD'}", flush=True)
 os.environ.pop("WV_HEAD_FRONT", None)

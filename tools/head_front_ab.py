@@ -10,9 +10,9 @@ from wvhash.models.fusion import band_attn_pool
 
 
 def run(head, feats, prepared):
-    cache = head._qproj_cache if prepared else None
     return band_attn_pool(feats, head.effective_queries(), head.attn, head.norm1, head.norm2, head.mlp[0], head.mlp[2],
-                          head.out_proj, pool_mean=False, qproj_cache=cache, qproj_key=head._query_key() if prepared else None)
+                          head.out_proj, pool_mean=False, cache=head._prepared if prepared else None,
+                          query_key=head._query_key() if prepared else None)
 
 
 def timeit(fn, n=30):
