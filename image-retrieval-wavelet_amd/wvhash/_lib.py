@@ -28,7 +28,10 @@ WV_COLOUR_BRIGHTNESS, WV_COLOUR_CONTRAST, WV_COLOUR_SATURATION = 0, 1, 2
 WV_IP_MAP_ROWS_MAX = 2048   # include/wvhash.h: rows wv_ip_map_at_k ranks in one workgroup
 WV_PAIR_LOSS_SCH, WV_PAIR_LOSS_HASHNET = 0, 1
 WV_PAIR_LOSS_ROWS_MAX = 2048   # include/wvhash.h: rows of a batch wv_pair_loss takes (D <= 512)
-WV_ENOTSUP = -95            # return code: the shape is outside the kernel asked for (callers fall back)
+WV_RANK_AP_SMOOTH, WV_RANK_AP_SUP = 0, 1
+WV_RANK_AP_QUICK, WV_RANK_AP_GENERAL = 0, 1
+WV_RANK_AP_COLS_MAX = 4096     # include/wvhash.h: rows and columns of a score matrix wv_rank_ap takes
+WV_ENOTSUP = -95           # return code: the shape is outside the kernel asked for (callers fall back)
 
 
 class WvhashUnavailable(RuntimeError):
@@ -80,7 +83,14 @@ class PairLossParams(ctypes.Structure):
                 ("nbits", ctypes.c_float), ("alpha", ctypes.c_float), ("beta", ctypes.c_float)]
 
 
-_vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
+class RankApParams(ctypes.Structure):
+    """wv_rank_ap_params: which rank approximation (WV_RANK_AP_SMOOTH | _SUP), which form (_QUICK | _GENERAL) and the
+    constants; 28 bytes."""
+    _fields_ = [("kind", ctypes.c_int), ("form", ctypes.c_int), ("tau", ctypes.c_float), ("rho", ctypes.c_float),
+                ("offset", ctypes.c_float), ("delta", ctypes.c_float), ("start", ctypes.c_float)]
+
+
+_vp, _i, _i64, _sz, _f =ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _fp = ctypes.POINTER(ctypes.c_float)
 
 # name -> (restype, argtypes); must list every symbol include/wvhash.h declares
@@ -187,6 +197,9 @@ SIGNATURES = {
     "wv_pair_loss_workspace_bytes": (_sz, [_i, _i]),
     "wv_pair_loss": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(PairLossParams), _vp, _vp, _vp, _sz, _vp]),
     "wv_pair_loss_cpu": (_i, [_vp, _vp, _i, _i, _i, ctypes.POINTER(PairLossParams), _vp, _vp]),
+    "wv_rank_ap_workspace_bytes": (_sz, [_i, _i, _i]),
+    "wv_rank_ap": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(RankApParams), _vp, _vp, _vp, _sz, _vp]),
+    "wv_rank_ap_cpu": (_i, [_vp, _vp, _i, _i, ctypes.POINTER(RankApParams), _vp, _vp]),
 }
 
 _LIB = None

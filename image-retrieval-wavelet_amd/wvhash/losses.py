@@ -8,8 +8,14 @@ And the two pairwise hashing baselines, SCHLoss (main/losses/dsch.py:6-59, `loss
 (main/losses/hashnet_loss.py:9-66): the same names, kwargs, attributes and numbers, each with two paths that agree to fp32
 rounding -- stock PyTorch ops under autograd (CPU tensors, fp64, large or non-0/1 label shapes), and one library call for
 the loss and its gradient w.r.t. the embeddings (wv_pair_loss, csrc/pair_loss.hip) behind a torch.autograd.Function for CUDA
-tensors.  `module.fused = False` forces the plain path; neither path ever moves a tensor to another device."""
+tensors.  `module.fused = False` forces the plain path; neither path ever moves a tensor to another device.
+
+And the rank-approximation AP losses on score matrices, SmoothRankAP / SmoothAP / SupAP / HeavisideAP
+(main/losses/smooth_rank_ap.py; SupAP is the ranking part of `loss: roadmap`), with the same two paths: the fused one is
+wv_rank_ap (csrc/rank_ap.hip), AP per query row and its gradient with no [B, B, B] tensor."""
 import ctypes
+import math
+from functools import partial
 
 import torch
 import torch.nn as nn
@@ -275,3 +281,263 @@ class HashNetAdapter(nn.Module):
         self.global_batch_step += 1
         current_real_epoch = self.global_batch_step // self.batches_per_epoch
         self.criterion.scale = (current_real_epoch // self.step_continuation) + 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Rank-approximation AP losses
+# ---------------------------------------------------------------------------------------------------------------------
+RANK_AP_COLS_MAX = _lib.WV_RANK_AP_COLS_MAX          # rows and columns of a score matrix wv_rank_ap takes
+
+
+def rank_ap_params(kind, form, tau=0.01, rho=100.0, offset=0.0, delta=0.0, start=0.5):
+    """wv_rank_ap_params of include/wvhash.h.  kind: 'smooth' or 'sup', form: 'quick' or 'general' (or the WV_RANK_AP_*
+    values); offset is a number: resolve the reference's offset=None with sup_offset()."""
+    kind = {"smooth": _lib.WV_RANK_AP_SMOOTH, "sup": _lib.WV_RANK_AP_SUP}.get(kind, kind)
+    form = {"quick": _lib.WV_RANK_AP_QUICK, "general": _lib.WV_RANK_AP_GENERAL}.get(form, form)
+    return _lib.RankApParams(int(kind), int(form), float(tau), float(rho), float(offset), float(delta), float(start))
+
+
+def sup_offset(tau, delta, start):
+    """What step_rank makes of offset=None: start + sigmoid_tau(delta)"""
+    return start + 1.0 / (1.0 + math.exp(min(max(-delta / tau, -50.0), 50.0)))
+
+
+def _rank_ap(what, scores, target, params, want_grad, device_type):
+    """The arguments of rank_ap on either side, gated (engine/_args.py), and the call -> (ap float32 [B], grad or None)"""
+    dev = anchor(scores, what, "scores", device_type)
+    if scores.dtype in _HALF:
+        scores = scores.float()                      # exact
+    scores = gate(scores, what, "scores", torch.float32, dev, (None, None))
+    target = gate(target, what, "target", torch.float32, dev, tuple(scores.shape))
+    if not isinstance(params, _lib.RankApParams):
+        raise ValueError(f"{what}: params: expected a RankApParams (rank_ap_params()), got {type(params).__name__}")
+    B, M = scores.shape
+    ap = torch.empty(B, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(scores) if want_grad else None
+    if device_type == "cpu":
+        rc = _lib.load().wv_rank_ap_cpu(_lib.ptr(scores), _lib.ptr(target), B, M, ctypes.byref(params), _lib.ptr(ap),
+                                        _lib.ptr(grad))
+        name = "wv_rank_ap_cpu"
+    else:
+        lib = _lib.require_gpu()
+        with torch.cuda.device(dev):
+            nbytes = lib.wv_rank_ap_workspace_bytes(B, M, params.form)
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            rc = lib.wv_rank_ap(_lib.ptr(scores), _lib.ptr(target), B, M, ctypes.byref(params), _lib.ptr(ap), _lib.ptr(grad),
+                                _lib.ptr(ws), ctypes.c_size_t(nbytes), _lib.stream_ptr())
+        name = "wv_rank_ap"
+    if rc == _lib.WV_ENOTSUP:
+        raise _lib.WvhashUnsupported(f"{name}: " + _lib.load().wv_last_error().decode(errors="replace"))
+    _lib.check(rc, name)
+    return ap, grad
+
+
+def rank_ap(scores, target, params, want_grad=True):
+    """SmoothAP / SupAP of every query row with its gradient in one library call (wv_rank_ap, two or three launches on the
+    current stream).  scores [B, M] on a CUDA device, fp32 (bf16 / fp16 are widened); target float32 [B, M] of 0 / 1; params:
+    rank_ap_params() -> (ap float32 [B];  grad float32 [B, M] = d ap[q] / d scores[q, :], or None when not wanted: the kernel
+    then skips that part).  A row without a positive: ap 0, grad 0.  WvhashUnsupported above RANK_AP_COLS_MAX rows or columns."""
+    return _rank_ap("rank_ap", scores, target, params, want_grad, "cuda")
+
+
+def rank_ap_host(scores, target, params, want_grad=True):
+    """rank_ap on host tensors, over the host twin wv_rank_ap_cpu: the same rules and per-pair code."""
+    return _rank_ap("rank_ap_host", scores, target, params, want_grad, "cpu")
+
+
+class _FusedRankAP(torch.autograd.Function):
+    """ap = wv_rank_ap(scores); the gradient the same call returned is kept for backward (row q of it belongs to ap[q])."""
+
+    @staticmethod
+    def forward(ctx, scores, target, params, want):
+        # want: grad mode was on at the call and scores require grad; otherwise the gradient pointer is null
+        ap, grad = rank_ap(scores.detach(), target, params, want_grad=want)
+        if want:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = scores.dtype
+        return ap
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        return (grad_output.unsqueeze(1) * grad).to(ctx.in_dtype), None, None, None
+
+
+class _Heaviside(torch.autograd.Function):
+    """torch.heaviside with no gradient (smooth_rank_ap.py:13-19)"""
+
+    @staticmethod
+    def forward(ctx, inputs, val):
+        return torch.heaviside(inputs, torch.as_tensor(val, device=inputs.device, dtype=inputs.dtype))
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return None, None
+
+
+def heaviside(tens, val=1., target=None, general=None):
+    return _Heaviside.apply(tens, val)
+
+
+def tau_sigmoid(tensor, tau, target=None, general=None):
+    """temperature controlled sigmoid, the exponent clamped to [-50, 50] (smooth_rank_ap.py:25-33)"""
+    return 1.0 / (1. + (-tensor / tau).clamp(-50, 50).exp())
+
+
+def step_rank(tens, tau, rho, offset=None, delta=None, start=0.5, target=None, general=False):
+    """SupAP's rank approximation (smooth_rank_ap.py:36-64) as one expression instead of masked assignments in place: the
+    same regions, the same values, differentiable by autograd.  tens [..., i, j] = S[q, j] - S[q, i].
+    general: target is the query's positive mask [M]; otherwise the whole target [B, B], and a pair (q, i, j) is a target
+    pair where rows i and j of it share a column and T[q, j] is set.
+    tau as 'n_p' (two temperatures, negative and positive side): the pieces are read as numbers."""
+    if general:
+        tgt = target.bool().view(1, -1).expand(tens.size(0), -1)
+    else:
+        t = target.float()
+        tgt = ((t @ t.t()) > 0) & target.bool().unsqueeze(1)
+    tau_n, tau_p = (float(x) for x in tau.split("_")) if isinstance(tau, str) else (tau, tau)
+    if delta is None:
+        up = rho * tens + offset
+    else:
+        if offset is None:
+            offset = sup_offset(tau_p, delta, start)
+        up = torch.where(tens > delta, rho * (tens - delta) + offset, start + tau_sigmoid(tens, tau_p))
+    return torch.where(tgt, heaviside(tens), torch.where(tens > 0, up, tau_sigmoid(tens, tau_n)))
+
+
+class SmoothRankAP(nn.Module):
+    """AP of every query row under a smooth rank (main/losses/smooth_rank_ap.py:67-161): same names, kwargs, asserts, choice
+    between the two forms and return types.  scores, target [B, M]; no `takes_embeddings`: train_step hands over the score
+    matrix emb @ emb.t() and the label matrix.
+
+    quick form (square input):  [B, B, B] tensors, a pair (q, i, j) weighted by T[i, j]
+    general form (B != M or force_general): a loop over the queries, weighted by T[q, j]
+    The two are different functions on multi-hot label matrices, as in the reference.
+
+    Two paths.  plain: stock PyTorch ops under autograd, on any device, in the dtype of `scores` (bf16 / fp16 widened to
+    fp32) -- fp64, CPU tensors, targets that are not 0 / 1, a row without a positive (the reference's NaN), a quick-form
+    target with a zero on its diagonal, a `tau` string, anything above RANK_AP_COLS_MAX, HeavisideAP and any other
+    rank_approximation.  fused (SmoothAP, SupAP; CUDA fp32 / bf16 / fp16): one library call returns AP and its gradient
+    (wv_rank_ap, csrc/rank_ap.hip) behind a torch.autograd.Function.  `fused = False` forces the plain path;
+    `check_labels = False` promises 0 / 1 targets with a positive in every row (and a unit diagonal when square) and saves
+    the check with its synchronise."""
+    fused = True
+    check_labels = True
+    _kind = None            # the kernel's name for rank_approximation; None: plain path only
+
+    def __init__(self, rank_approximation, return_type='1-mAP'):
+        super().__init__()
+        self.rank_approximation = rank_approximation
+        self.return_type = return_type
+        assert return_type in ["1-mAP", "1-AP", "AP", 'mAP']
+
+    def general_forward(self, scores, target, verbose=False):
+        mask = 1 - torch.eye(target.size(1), device=scores.device, dtype=scores.dtype)
+        ap_score = []
+        for idx in range(target.size(0)):
+            pos_mask = target[idx].bool()
+            query = scores[idx].view(1, -1) - scores[idx][pos_mask].view(-1, 1)                    # [positives, M]
+            query = self.rank_approximation(query, target=pos_mask, general=True) * mask[pos_mask]
+            rk = 1 + query.sum(-1)
+            pos_rk = 1 + (query * pos_mask.view(1, -1)).sum(-1)
+            ap_score.append((pos_rk / rk).sum(-1) / pos_mask.sum())
+        return torch.stack(ap_score)
+
+    def quick_forward(self, scores, target):
+        eye = torch.eye(target.size(0), device=scores.device, dtype=scores.dtype)
+        sim_diff = scores.unsqueeze(1) - scores.unsqueeze(2)                                       # [q, i, j] = S[q, j] - S[q, i]
+        sim_diff_sigmoid = self.rank_approximation(sim_diff, target=target)
+        sim_all_rk = torch.sum(sim_diff_sigmoid * (1.0 - eye.unsqueeze(0)), dim=-1) + 1
+        sim_pos_rk = (torch.sum(sim_diff_sigmoid * (target - eye), dim=-1) + target) * target
+        return (sim_pos_rk / sim_all_rk).sum(1) * (1 / target.sum(1))
+
+    def _fused_params(self, general):
+        kw = self.rank_approximation.keywords
+        form = "general" if general else "quick"
+        if self._kind == "smooth":
+            return rank_ap_params("smooth", form, kw["tau"])
+        delta, offset, start = kw["delta"], kw["offset"], kw["start"]
+        if delta is None:                            # rho d + offset on every d > 0: a linear part that begins at 0
+            delta = 0.0
+        elif offset is None:
+            offset = sup_offset(kw["tau"], delta, start)
+        return rank_ap_params("sup", form, kw["tau"], kw["rho"], offset, delta, start)
+
+    def _takes_fused(self, scores, target, general):
+        if not (self.fused and self._kind is not None and scores.is_cuda and scores.dtype in (torch.float32,) + _HALF):
+            return False
+        if not (1 <= scores.shape[0] <= RANK_AP_COLS_MAX and 1 <= scores.shape[1] <= RANK_AP_COLS_MAX):
+            return False
+        kw = self.rank_approximation.keywords
+        if isinstance(kw["tau"], str) or (self._kind == "sup" and kw["delta"] is None and kw["offset"] is None):
+            return False
+        if not self.check_labels:
+            return True
+        ok = ((target == 0) | (target == 1)).all() & (target != 0).any(1).all()
+        if not general:
+            ok = ok & (target.diagonal() == 1).all()
+        return bool(ok)
+
+    def forward(self, scores, target, force_general=False, verbose=False):
+        assert scores.shape == target.shape
+        assert len(scores.shape) == 2
+
+        general = force_general or scores.size(0) != scores.size(1)
+        if self._takes_fused(scores, target, general):
+            want = torch.is_grad_enabled() and scores.requires_grad    # the Function itself runs with grad mode off
+            ap = _FusedRankAP.apply(scores, target.to(device=scores.device, dtype=torch.float32), self._fused_params(general), want)
+        else:
+            with torch.autocast(scores.device.type, enabled=False):
+                wide = scores.float() if scores.dtype in _HALF else scores
+                t = target.to(device=wide.device, dtype=wide.dtype)
+                ap = self.general_forward(wide, t, verbose=verbose) if general else self.quick_forward(wide, t)
+
+        if self.return_type == 'AP':
+            return ap
+        elif self.return_type == 'mAP':
+            return ap.mean()
+        elif self.return_type == '1-AP':
+            return 1 - ap
+        elif self.return_type == '1-mAP':
+            return 1 - ap.mean()
+
+    @property
+    def my_repr(self):
+        return f"return_type={self.return_type}"
+
+
+class HeavisideAP(SmoothRankAP):
+    """here for testing purposes: the exact rank, no gradient.  Always the plain path."""
+
+    def __init__(self, **kwargs):
+        super().__init__(partial(heaviside), **kwargs)
+
+    def extra_repr(self):
+        return self.my_repr
+
+
+class SmoothAP(SmoothRankAP):
+    _kind = "smooth"
+
+    def __init__(self, tau=0.01, **kwargs):
+        super().__init__(partial(tau_sigmoid, tau=tau), **kwargs)
+        self.tau = tau
+
+    def extra_repr(self):
+        return f"tau={self.tau}, {self.my_repr}"
+
+
+class SupAP(SmoothRankAP):
+    """`loss: roadmap`'s ranking part (config/loss/roadmap.yaml: tau 0.01, rho 100, offset 1.44, delta 0.05)."""
+    _kind = "sup"
+
+    def __init__(self, tau=0.01, rho=100, offset=None, delta=0.05, start=0.5, **kwargs):
+        super().__init__(partial(step_rank, tau=tau, rho=rho, offset=offset, delta=delta, start=start), **kwargs)
+        self.tau = tau
+        self.rho = rho
+        self.offset = offset
+        self.delta = delta
+
+    def extra_repr(self):
+        return f"tau={self.tau}, rho={self.rho}, offset={self.offset}, delta={self.delta}, {self.my_repr}"

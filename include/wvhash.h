@@ -63,6 +63,7 @@ const char *wv_last_error(void);
  * So was the grouped LayerNorm (wv_group_layernorm, wv_group_layernorm_cpu, wv_group_layernorm_check): 97 symbols.
  * So was the batch mAP proxy of real-valued embeddings (wv_ip_map_at_k, wv_ip_map_at_k_cpu): 99 symbols.
  * So were the pairwise hashing losses (wv_pair_loss[_workspace_bytes], wv_pair_loss_cpu, struct wv_pair_loss_params): 102 symbols.
+ * So were the rank-approximation AP losses (wv_rank_ap[_workspace_bytes], wv_rank_ap_cpu, struct wv_rank_ap_params): 105 symbols.
  * A struct gaining a field bumps it. */
 int wv_abi_version(void);
 
@@ -810,6 +811,60 @@ int wv_pair_loss(const float *e, const uint64_t *labels, int lwords, int B, int 
                  float *out, float *grad, void *workspace, size_t workspace_bytes, void *stream);
 int wv_pair_loss_cpu(const float *e, const uint64_t *labels, int lwords, int B, int D, const struct wv_pair_loss_params *p,
                      float *out, float *grad);
+
+/* ------------------------------------------------------------------------------------------
+ * Rank-approximation AP losses: SmoothAP and SupAP (main/losses/smooth_rank_ap.py), the AP of every query row AND its
+ * gradient w.r.t. that row's scores.  The reference materialises S[q,j] - S[q,i] as a [B, B, B] tensor, rewrites it with
+ * boolean-mask assignments and keeps all of it for autograd (quick_forward), or loops over the B queries in Python
+ * (general_forward).  Here nothing of size B x M x M exists: one workgroup per query row, the row in LDS.
+ *   scores [B][M] float32, dense
+ *   target [B][M] float32 holding 0 / 1 (any non-zero value counts as 1)
+ *   ap     float32 [B]: AP_q
+ *   grad   float32 [B][M]: d AP_q / d scores[q][.], or NULL -- then that part of the work is skipped and `ap` has the same
+ *          bits.  Row q of the gradient depends on row q of the scores only.
+ * For query row q:  P = { i : T[q,i] = 1 },  n = |P|,  d_ij = S[q,j] - S[q,i]  (i in P, all j),
+ *   sigma(x) = 1 / (1 + exp(clamp(-x / tau, -50, 50))),  derivative sigma (1 - sigma) / tau inside the clamp, 0 outside.
+ *   WV_RANK_AP_SMOOTH  R_ij = sigma(d_ij); the pair's target bit is ignored.
+ *   WV_RANK_AP_SUP     where tgt_ij: R = [d >= 0], derivative 0;  elsewhere  d > delta: R = rho (d - delta) + offset, derivative
+ *                      rho;  0 < d <= delta: R = start + sigma(d);  d <= 0: R = sigma(d).  `offset` is a number: the caller
+ *                      resolves the reference's offset=None to start + sigma(delta).
+ *   WV_RANK_AP_GENERAL any [B][M]:      tgt_ij = T[q,j],  w_ij = T[q,j]
+ *   WV_RANK_AP_QUICK   B = M required:  tgt_ij = LM[i,j] and T[q,j] with LM = (T T^t > 0),  w_ij = T[i,j] (row i, not row q)
+ *   rk_i = 1 + sum_{j != i} R_ij,  prk_i = 1 + sum_{j != i} R_ij w_ij,  AP_q = (1 / n) sum_{i in P} prk_i / rk_i.
+ *   With f_i = prk_i / rk_i and g_ij = (w_ij - f_i) / (rk_i n) R'_ij (j != i):  grad[q][j] += g_ij,  grad[q][i] -= g_ij.
+ * The quick form equals the reference's quick_forward for targets with T[i,i] = 1 (a label matrix of non-empty rows has
+ * them); for T[i,i] = 0 the reference subtracts R_ii from prk_i, which this entry point does not.
+ * A row without a positive gives ap 0 and grad 0 (the reference: 0 / 0 = NaN).
+ * fp32 arithmetic; every sum has one fixed order, no floating-point atomics: the same call gives the same bits.
+ * Two launches for the general form (bit-packing of T; the rows), three for the quick form (the bit rows of LM between
+ * them), all on `stream`; no hidden synchronisation.
+ * workspace: device memory of wv_rank_ap_workspace_bytes(B, M, form) bytes: the bit rows of T, [B][ceil(M / 64)] 64-bit
+ * words, and for the quick form as many for LM.
+ * Arguments are checked on the host before any pointer is read: WV_EINVAL for a null pointer (grad excepted), B < 1, M < 1, an
+ * unknown kind or form, the quick form with B != M, tau not > 0, a workspace shorter than the query says; WV_ENOTSUP for
+ * B or M above WV_RANK_AP_COLS_MAX (a row, its bit mask, its positives' list and their records live in one workgroup's LDS).
+ * _cpu: host twin (HOST pointers, no workspace, no stream; csrc/host_rank_ap.cpp) under the same rules and the same
+ * per-pair code (csrc/rank_ap.hpp); it agrees with the kernel to fp32 rounding, not bit for bit (device exp, sum order).
+ * ------------------------------------------------------------------------------------------ */
+#define WV_RANK_AP_SMOOTH 0
+#define WV_RANK_AP_SUP 1
+#define WV_RANK_AP_QUICK 0
+#define WV_RANK_AP_GENERAL 1
+#define WV_RANK_AP_COLS_MAX 4096
+typedef struct wv_rank_ap_params {
+    int kind;     /* WV_RANK_AP_SMOOTH | WV_RANK_AP_SUP */
+    int form;     /* WV_RANK_AP_QUICK | WV_RANK_AP_GENERAL */
+    float tau;    /* > 0: the sigmoid's temperature */
+    float rho;    /* SUP: slope beyond delta */
+    float offset; /* SUP: value at d = delta+ */
+    float delta;  /* SUP: where the linear part begins (the reference's delta=None: 0) */
+    float start;  /* SUP: added to the sigmoid on 0 < d <= delta */
+} wv_rank_ap_params;
+size_t wv_rank_ap_workspace_bytes(int B, int M, int form);
+int wv_rank_ap(const float *scores, const float *target, int B, int M, const struct wv_rank_ap_params *p, float *ap,
+               float *grad, void *workspace, size_t workspace_bytes, void *stream);
+int wv_rank_ap_cpu(const float *scores, const float *target, int B, int M, const struct wv_rank_ap_params *p, float *ap,
+                   float *grad);
 
 #ifdef __cplusplus
 }
