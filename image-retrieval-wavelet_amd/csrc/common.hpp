@@ -28,6 +28,16 @@ const char *tune(const char *name);
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t align_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 
+// Raises a kernel's dynamic-LDS limit where it asks for more than the 64 KB every kernel may have.
+inline int set_lds_attr(const void *fn, size_t bytes, const char *what)
+{
+    if (bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) WV_FAIL(WV_EHIP, "%s: hipFuncSetAttribute(%zu): %s", what, bytes, hipGetErrorString(e));
+    }
+    return WV_OK;
+}
+
 // prepared-database blob = [distance-kernel tile image][ranking-kernel images: rank.hpp]
 size_t dist_prepared_bytes(int64_t N, int words);
 int dist_prepare(const uint64_t *db, void *dbP, int64_t N, int words, hipStream_t st);
@@ -76,6 +86,13 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 }
 
 __device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+__device__ __forceinline__ float wave_sum_f32(float v)
 {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);

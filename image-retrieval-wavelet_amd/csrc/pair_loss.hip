@@ -187,11 +187,7 @@ extern "C" int wv_pair_loss(const float *e, const uint64_t *labels, int lwords, 
     float *g = static_cast<float *>(ws);
     auto *part = reinterpret_cast<wv::PairLossPartial *>(static_cast<char *>(ws) + wv::pair_loss_g_bytes(B, D));
     const size_t lds = wv::pair_main_lds(D);
-    if (lds > 64 * 1024) {
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(wv::k_pair_main),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) WV_FAIL(WV_EHIP, "pair_loss: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(err));
-    }
+    if (int rc = wv::set_lds_attr(reinterpret_cast<const void *>(wv::k_pair_main), lds, "pair_loss")) return rc;
     hipLaunchKernelGGL(wv::k_pair_main, dim3((unsigned)nb), dim3(wv::kPlThreads), lds, (hipStream_t)stream, e, labels, lwords, B,
                        D, *p, g, part, grad ? 1 : 0);
     WV_CHECK_LAUNCH("pair_loss");

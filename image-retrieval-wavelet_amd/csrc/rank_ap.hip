@@ -34,13 +34,6 @@ inline size_t rank_ap_lds(int M)
 static_assert(sizeof(RankApRecord) == 12 && kRankApMax <= 65536, "record of three floats; a column index fits 16 bits");
 static_assert(kRankApMaxWords <= kWave, "one wave scans the popcounts of a bit row");
 
-__device__ __forceinline__ float wave_sum_f32(float v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(kRaPackWaves *kWave) void k_rank_ap_pack(const float *__restrict__ T, int M, int W,
                                                                        uint64_t *__restrict__ bits)
 {
@@ -177,11 +170,7 @@ extern "C" int wv_rank_ap(const float *scores, const float *target, int B, int M
         WV_CHECK_LAUNCH("rank_ap (label matrix)");
     }
     const size_t lds = wv::rank_ap_lds(M);
-    if (lds > 64 * 1024) {
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(wv::k_rank_ap_rows),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) WV_FAIL(WV_EHIP, "rank_ap: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(err));
-    }
+    if (int rc = wv::set_lds_attr(reinterpret_cast<const void *>(wv::k_rank_ap_rows), lds, "rank_ap")) return rc;
     hipLaunchKernelGGL(wv::k_rank_ap_rows, dim3((unsigned)B), dim3(wv::kRaThreads), lds, st, scores, bits, lm, M, W, *p, ap,
                        grad);
     WV_CHECK_LAUNCH("rank_ap");

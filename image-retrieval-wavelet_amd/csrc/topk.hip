@@ -641,15 +641,6 @@ __global__ __launch_bounds__(256) void k_merge_cum(const uint16_t *__restrict__ 
     }
 }
 
-static int set_lds_attr(const void *fn, size_t bytes, const char *what)
-{
-    if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) WV_FAIL(WV_EHIP, "%s: hipFuncSetAttribute(%zu): %s", what, bytes, hipGetErrorString(e));
-    }
-    return WV_OK;
-}
-
 template <int WORDS>
 static int launch_transpose(const uint64_t *db, uint64_t *dbT, int64_t N, hipStream_t st)
 {

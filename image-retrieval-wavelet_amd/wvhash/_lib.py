@@ -263,9 +263,12 @@ def require_gpu():
     return load()
 
 
-def check(rc, what=""):
+def check(rc, what="", unsupported=False):
+    """unsupported: the caller has another way to the same result, so WV_ENOTSUP is a WvhashUnsupported of its own"""
     if rc != 0:
         msg = load().wv_last_error().decode(errors="replace")
+        if unsupported and rc == WV_ENOTSUP:
+            raise WvhashUnsupported(f"{what}: {msg}")
         if rc == -22:
             raise ValueError(f"{what}: {msg}")
         raise WvhashError(f"{what}: rc={rc}: {msg}")
@@ -291,9 +294,7 @@ def wv_band_attn_maps(p, feats, layout, B, probs=None, probs_mean=None, scores=N
         nbytes = lib.wv_band_attn_maps_workspace_bytes(ctypes.byref(p), B)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=feats.device)
         rc = lib.wv_band_attn_maps(ctypes.byref(p), ptr(feats), layout, B, *outs, ptr(ws), ctypes.c_size_t(nbytes), stream_ptr())
-    if rc == WV_ENOTSUP:
-        raise WvhashUnsupported("wv_band_attn_maps: " + lib.wv_last_error().decode(errors="replace"))
-    check(rc, "wv_band_attn_maps")
+    check(rc, "wv_band_attn_maps", unsupported=True)
 
 
 def host_floats(values):

@@ -13,6 +13,7 @@ tensors.  `module.fused = False` forces the plain path; neither path ever moves 
 And the rank-approximation AP losses on score matrices, SmoothRankAP / SmoothAP / SupAP / HeavisideAP
 (main/losses/smooth_rank_ap.py; SupAP is the ranking part of `loss: roadmap`), with the same two paths: the fused one is
 wv_rank_ap (csrc/rank_ap.hip), AP per query row and its gradient with no [B, B, B] tensor."""
+import collections
 import ctypes
 import math
 from functools import partial
@@ -69,12 +70,111 @@ class HashLoss(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Fused losses: the library call, the autograd Function and the path switch that every one of them uses
+# ---------------------------------------------------------------------------------------------------------------------
+_HALF = (torch.bfloat16, torch.float16)
+
+# What differs between the library calls of two fused losses.  Entry points have the shape
+#   stem(x, second, *dims, params, out, grad, workspace, workspace_bytes, stream), stem_cpu without the last three
+#   stem          the entry point; stem_cpu is its host twin, stem_workspace_bytes sizes its workspace
+#   params_type   the params struct, params_fn the name of the function that builds one (for the error message)
+#   first         argument name of the input x, fp32 [B, *]
+#   second        name, dtype and shape (a function of x) of the second tensor
+#   out_len       x -> length of the fp32 output
+#   dims          (x, second) -> the int arguments between the tensors and the params
+#   ws_args       (x, params) -> the arguments of stem_workspace_bytes
+_FusedOp = collections.namedtuple("_FusedOp", "stem params_type params_fn first second out_len dims ws_args")
+
+_PAIR_LOSS = _FusedOp("wv_pair_loss", _lib.PairLossParams, "pair_loss_params", "e",
+                      ("labels_packed", torch.int64, lambda e: (e.shape[0], None)), lambda e: 3,
+                      lambda e, lp: (lp.shape[1],) + tuple(e.shape), lambda e, params: tuple(e.shape))
+_RANK_AP = _FusedOp("wv_rank_ap", _lib.RankApParams, "rank_ap_params", "scores",
+                    ("target", torch.float32, lambda s: tuple(s.shape)), lambda s: s.shape[0],
+                    lambda s, t: tuple(s.shape), lambda s, params: tuple(s.shape) + (params.form,))
+
+
+def _fused_call(op, what, x, second, params, want_grad, device_type):
+    """The arguments of a fused loss on either side, gated (engine/_args.py), and the call -> (out float32, grad or None)"""
+    dev = anchor(x, what, op.first, device_type)
+    if x.dtype in _HALF:
+        x = x.float()                                # exact
+    x = gate(x, what, op.first, torch.float32, dev, (None, None))
+    second_name, second_dtype, second_shape = op.second
+    second = gate(second, what, second_name, second_dtype, dev, second_shape(x))
+    if not isinstance(params, op.params_type):
+        raise ValueError(f"{what}: params: expected a {op.params_type.__name__} ({op.params_fn}()), "
+                         f"got {type(params).__name__}")
+    out = torch.empty(op.out_len(x), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(x) if want_grad else None
+    args = (_lib.ptr(x), _lib.ptr(second), *op.dims(x, second), ctypes.byref(params), _lib.ptr(out), _lib.ptr(grad))
+    if device_type == "cpu":
+        name = op.stem + "_cpu"
+        rc = getattr(_lib.load(), name)(*args)
+    else:
+        name = op.stem
+        lib = _lib.require_gpu()
+        with torch.cuda.device(dev):
+            nbytes = getattr(lib, name + "_workspace_bytes")(*op.ws_args(x, params))
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            rc = getattr(lib, name)(*args, _lib.ptr(ws), ctypes.c_size_t(nbytes), _lib.stream_ptr())
+    _lib.check(rc, name, unsupported=True)
+    return out, grad
+
+
+class _FusedLoss(torch.autograd.Function):
+    """value = call(x): pair_loss, rank_ap or a host twin; the gradient the same call returned is kept for backward.
+    pick: the element of the call's output that is the value (0: the loss of pair_loss), None: all of it (the ap of
+    rank_ap, whose gradient row q belongs to ap[q])."""
+
+    @staticmethod
+    def forward(ctx, call, pick, x, second, params, want):
+        # want: grad mode was on at the call and x requires grad; otherwise the gradient pointer is null
+        out, grad = call(x.detach(), second, params, want_grad=want)
+        if want:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = x.dtype
+        return out if pick is None else out[pick]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        (grad,) = ctx.saved_tensors
+        # grad_output over the gradient's trailing dimensions: a [B] one scales [B, M] row by row; a 0-dim one scales [B, D]
+        # as it is (reshaped to [1, 1] it gives the same bits for 5 us more host time per backward)
+        if grad_output.dim():
+            grad_output = grad_output.reshape(grad_output.shape + (1,) * (grad.dim() - grad_output.dim()))
+        return None, None, (grad_output * grad).to(ctx.in_dtype), None, None, None
+
+
+class _FusedPaths:
+    """What SCHLoss, HashNetLoss and SmoothRankAP share: the two switches, what any fused path asks of its input, the way
+    into the Function, the operands of the plain path.  A family adds its shape limits, its label rule and its params."""
+    fused = True            # False: always the plain path
+    check_labels = True     # False: labels are promised to be what the fused path takes -- skips one reduction and a sync per call
+
+    def _fusable(self, x):
+        return self.fused and x.is_cuda and x.dtype in (torch.float32,) + _HALF
+
+    @staticmethod
+    def _fused(call, pick, x, second, params):
+        """call: the public wrapper, looked up in this module when the family calls (tests count its calls)"""
+        want = torch.is_grad_enabled() and x.requires_grad      # the Function itself runs with grad mode off
+        return _FusedLoss.apply(call, pick, x, second, params, want)
+
+    @staticmethod
+    def _run_plain(fn, x, labels, *args):
+        """fn(x, labels, *args) out of autocast's reach: bf16 / fp16 x widened, labels in x's dtype, on x's device"""
+        with torch.autocast(x.device.type, enabled=False):
+            wide = x.float() if x.dtype in _HALF else x
+            return fn(wide, labels.to(device=wide.device, dtype=wide.dtype), *args)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Pairwise hashing losses
 # ---------------------------------------------------------------------------------------------------------------------
 PAIR_LOSS_ROWS_MAX = _lib.WV_PAIR_LOSS_ROWS_MAX      # rows of a batch wv_pair_loss takes
 PAIR_LOSS_D_MAX = 512                                # ... and its widest embedding
 PAIR_LOSS_CLASSES_MAX = 128                          # two packed label words
-_HALF = (torch.bfloat16, torch.float16)
 
 
 def pair_loss_params(kind, apply_tanh=False, pre_scale=1.0, nbits=64.0, alpha=0.1, beta=0.1):
@@ -83,73 +183,21 @@ def pair_loss_params(kind, apply_tanh=False, pre_scale=1.0, nbits=64.0, alpha=0.
     return _lib.PairLossParams(int(kind), int(bool(apply_tanh)), float(pre_scale), float(nbits), float(alpha), float(beta))
 
 
-def _pair_loss(what, e, labels_packed, params, want_grad, device_type):
-    """The arguments of pair_loss on either side, gated (engine/_args.py), and the call -> (out float32 [3], grad or None)"""
-    dev = anchor(e, what, "e", device_type)
-    if e.dtype in _HALF:
-        e = e.float()                                # exact
-    e = gate(e, what, "e", torch.float32, dev, (None, None))
-    labels_packed = gate(labels_packed, what, "labels_packed", torch.int64, dev, (e.shape[0], None))
-    if not isinstance(params, _lib.PairLossParams):
-        raise ValueError(f"{what}: params: expected a PairLossParams (pair_loss_params()), got {type(params).__name__}")
-    B, D = e.shape
-    lw = labels_packed.shape[1]
-    out = torch.empty(3, dtype=torch.float32, device=dev)
-    grad = torch.empty_like(e) if want_grad else None
-    if device_type == "cpu":
-        rc = _lib.load().wv_pair_loss_cpu(_lib.ptr(e), _lib.ptr(labels_packed), lw, B, D, ctypes.byref(params), _lib.ptr(out),
-                                          _lib.ptr(grad))
-        name = "wv_pair_loss_cpu"
-    else:
-        lib = _lib.require_gpu()
-        with torch.cuda.device(dev):
-            nbytes = lib.wv_pair_loss_workspace_bytes(B, D)
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            rc = lib.wv_pair_loss(_lib.ptr(e), _lib.ptr(labels_packed), lw, B, D, ctypes.byref(params), _lib.ptr(out),
-                                  _lib.ptr(grad), _lib.ptr(ws), ctypes.c_size_t(nbytes), _lib.stream_ptr())
-        name = "wv_pair_loss"
-    if rc == _lib.WV_ENOTSUP:
-        raise _lib.WvhashUnsupported(f"{name}: " + _lib.load().wv_last_error().decode(errors="replace"))
-    _lib.check(rc, name)
-    return out, grad
-
-
 def pair_loss(e, labels_packed, params, want_grad=True):
     """SCHLoss / HashNetLoss with its gradient in one library call (wv_pair_loss, two launches on the current stream).
     e [B, D] on a CUDA device, fp32 (bf16 / fp16 are widened); labels_packed int64 [B, 1 or 2] (pack_labels); params:
     pair_loss_params() -> (out float32 [3]: loss, part 1, part 2;  grad float32 [B, D] = d loss / d e, or None when not
     wanted: the kernel then skips that part).  WvhashUnsupported above PAIR_LOSS_ROWS_MAX rows or D > 512."""
-    return _pair_loss("pair_loss", e, labels_packed, params, want_grad, "cuda")
+    return _fused_call(_PAIR_LOSS, "pair_loss", e, labels_packed, params, want_grad, "cuda")
 
 
 def pair_loss_host(e, labels_packed, params, want_grad=True):
     """pair_loss on host tensors, over the host twin wv_pair_loss_cpu: the same rules and per-pair code, fp32."""
-    return _pair_loss("pair_loss_host", e, labels_packed, params, want_grad, "cpu")
+    return _fused_call(_PAIR_LOSS, "pair_loss_host", e, labels_packed, params, want_grad, "cpu")
 
 
-class _FusedPairLoss(torch.autograd.Function):
-    """loss = wv_pair_loss(e); the gradient the same call returned is kept for backward."""
-
-    @staticmethod
-    def forward(ctx, emb, labels_packed, params, want):
-        # want: grad mode was on at the call and emb requires grad; otherwise the gradient pointer is null
-        out, grad = pair_loss(emb.detach(), labels_packed, params, want_grad=want)
-        if want:
-            ctx.save_for_backward(grad)
-        ctx.in_dtype = emb.dtype
-        return out[0]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        (grad,) = ctx.saved_tensors
-        return (grad_output * grad).to(ctx.in_dtype), None, None, None
-
-
-class _PairLossPaths:
-    """What SCHLoss and HashNetLoss share: the label rule, the choice between the two paths, the widening."""
-    fused = True            # False: always the plain path
-    check_labels = True     # False: labels are promised to be 0/1 -- skips one reduction and a sync per call
+class _PairLossPaths(_FusedPaths):
+    """The pairwise family's own: 2-D multi-hot 0/1 labels, packed; the limits of wv_pair_loss."""
 
     @staticmethod
     def _labels_2d(what, labels):
@@ -158,7 +206,7 @@ class _PairLossPaths:
                              "(class-id labels have no pairwise relation here)")
 
     def _takes_fused(self, emb, labels):
-        if not (self.fused and emb.is_cuda and emb.dim() == 2 and emb.dtype in (torch.float32,) + _HALF):
+        if not (self._fusable(emb) and emb.dim() == 2):
             return False
         if emb.shape[0] > PAIR_LOSS_ROWS_MAX or emb.shape[1] > PAIR_LOSS_D_MAX or emb.shape[0] < 1 or emb.shape[1] < 1:
             return False
@@ -166,16 +214,9 @@ class _PairLossPaths:
             return False
         return not self.check_labels or bool(((labels == 0) | (labels == 1)).all())
 
-    def _fused(self, emb, labels, params):
+    def _fused_pair(self, emb, labels, params):
         from .engine.hamming import pack_labels
-        want = torch.is_grad_enabled() and emb.requires_grad      # the Function itself runs with grad mode off
-        return _FusedPairLoss.apply(emb, pack_labels(labels.to(emb.device), check=False), params, want)
-
-    @staticmethod
-    def _widened(emb, labels):
-        """Operands of the plain path: bf16 / fp16 widened, labels in the embeddings' dtype, on the embeddings' device"""
-        emb = emb.float() if emb.dtype in _HALF else emb
-        return emb, labels.to(device=emb.device, dtype=emb.dtype)
+        return self._fused(pair_loss, 0, emb, pack_labels(labels.to(emb.device), check=False), params)
 
 
 class SCHLoss(nn.Module, _PairLossPaths):
@@ -200,9 +241,8 @@ class SCHLoss(nn.Module, _PairLossPaths):
     def forward(self, batch, labels):
         self._labels_2d("SCHLoss", labels)
         if self._takes_fused(batch, labels):
-            return self._fused(batch, labels, pair_loss_params("sch", self.apply_tanh, 1.0, self.n_bits, self.alpha, self.beta))
-        with torch.autocast(batch.device.type, enabled=False):
-            return self.plain(*self._widened(batch, labels))
+            return self._fused_pair(batch, labels, pair_loss_params("sch", self.apply_tanh, 1.0, self.n_bits, self.alpha, self.beta))
+        return self._run_plain(self.plain, batch, labels)
 
     def plain(self, batch, labels):
         """Stock PyTorch ops, differentiable by autograd, in the dtype of `batch`."""
@@ -240,9 +280,8 @@ class HashNetLoss(nn.Module, _PairLossPaths):
         self._labels_2d("HashNetLoss", y)
         alpha = config["alpha"]
         if self._takes_fused(u, y):
-            return self._fused(u, y, pair_loss_params("hashnet", True, self.scale, 0.0, alpha, 0.0))
-        with torch.autocast(u.device.type, enabled=False):
-            return self.plain(*self._widened(u, y), alpha)
+            return self._fused_pair(u, y, pair_loss_params("hashnet", True, self.scale, 0.0, alpha, 0.0))
+        return self._run_plain(self.plain, u, y, alpha)
 
     def plain(self, u, y, alpha):
         u = torch.tanh(self.scale * u)
@@ -302,66 +341,17 @@ def sup_offset(tau, delta, start):
     return start + 1.0 / (1.0 + math.exp(min(max(-delta / tau, -50.0), 50.0)))
 
 
-def _rank_ap(what, scores, target, params, want_grad, device_type):
-    """The arguments of rank_ap on either side, gated (engine/_args.py), and the call -> (ap float32 [B], grad or None)"""
-    dev = anchor(scores, what, "scores", device_type)
-    if scores.dtype in _HALF:
-        scores = scores.float()                      # exact
-    scores = gate(scores, what, "scores", torch.float32, dev, (None, None))
-    target = gate(target, what, "target", torch.float32, dev, tuple(scores.shape))
-    if not isinstance(params, _lib.RankApParams):
-        raise ValueError(f"{what}: params: expected a RankApParams (rank_ap_params()), got {type(params).__name__}")
-    B, M = scores.shape
-    ap = torch.empty(B, dtype=torch.float32, device=dev)
-    grad = torch.empty_like(scores) if want_grad else None
-    if device_type == "cpu":
-        rc = _lib.load().wv_rank_ap_cpu(_lib.ptr(scores), _lib.ptr(target), B, M, ctypes.byref(params), _lib.ptr(ap),
-                                        _lib.ptr(grad))
-        name = "wv_rank_ap_cpu"
-    else:
-        lib = _lib.require_gpu()
-        with torch.cuda.device(dev):
-            nbytes = lib.wv_rank_ap_workspace_bytes(B, M, params.form)
-            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            rc = lib.wv_rank_ap(_lib.ptr(scores), _lib.ptr(target), B, M, ctypes.byref(params), _lib.ptr(ap), _lib.ptr(grad),
-                                _lib.ptr(ws), ctypes.c_size_t(nbytes), _lib.stream_ptr())
-        name = "wv_rank_ap"
-    if rc == _lib.WV_ENOTSUP:
-        raise _lib.WvhashUnsupported(f"{name}: " + _lib.load().wv_last_error().decode(errors="replace"))
-    _lib.check(rc, name)
-    return ap, grad
-
-
 def rank_ap(scores, target, params, want_grad=True):
     """SmoothAP / SupAP of every query row with its gradient in one library call (wv_rank_ap, two or three launches on the
     current stream).  scores [B, M] on a CUDA device, fp32 (bf16 / fp16 are widened); target float32 [B, M] of 0 / 1; params:
     rank_ap_params() -> (ap float32 [B];  grad float32 [B, M] = d ap[q] / d scores[q, :], or None when not wanted: the kernel
     then skips that part).  A row without a positive: ap 0, grad 0.  WvhashUnsupported above RANK_AP_COLS_MAX rows or columns."""
-    return _rank_ap("rank_ap", scores, target, params, want_grad, "cuda")
+    return _fused_call(_RANK_AP, "rank_ap", scores, target, params, want_grad, "cuda")
 
 
 def rank_ap_host(scores, target, params, want_grad=True):
     """rank_ap on host tensors, over the host twin wv_rank_ap_cpu: the same rules and per-pair code."""
-    return _rank_ap("rank_ap_host", scores, target, params, want_grad, "cpu")
-
-
-class _FusedRankAP(torch.autograd.Function):
-    """ap = wv_rank_ap(scores); the gradient the same call returned is kept for backward (row q of it belongs to ap[q])."""
-
-    @staticmethod
-    def forward(ctx, scores, target, params, want):
-        # want: grad mode was on at the call and scores require grad; otherwise the gradient pointer is null
-        ap, grad = rank_ap(scores.detach(), target, params, want_grad=want)
-        if want:
-            ctx.save_for_backward(grad)
-        ctx.in_dtype = scores.dtype
-        return ap
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_output):
-        (grad,) = ctx.saved_tensors
-        return (grad_output.unsqueeze(1) * grad).to(ctx.in_dtype), None, None, None
+    return _fused_call(_RANK_AP, "rank_ap_host", scores, target, params, want_grad, "cpu")
 
 
 class _Heaviside(torch.autograd.Function):
@@ -406,7 +396,7 @@ def step_rank(tens, tau, rho, offset=None, delta=None, start=0.5, target=None, g
     return torch.where(tgt, heaviside(tens), torch.where(tens > 0, up, tau_sigmoid(tens, tau_n)))
 
 
-class SmoothRankAP(nn.Module):
+class SmoothRankAP(nn.Module, _FusedPaths):
     """AP of every query row under a smooth rank (main/losses/smooth_rank_ap.py:67-161): same names, kwargs, asserts, choice
     between the two forms and return types.  scores, target [B, M]; no `takes_embeddings`: train_step hands over the score
     matrix emb @ emb.t() and the label matrix.
@@ -422,8 +412,6 @@ class SmoothRankAP(nn.Module):
     (wv_rank_ap, csrc/rank_ap.hip) behind a torch.autograd.Function.  `fused = False` forces the plain path;
     `check_labels = False` promises 0 / 1 targets with a positive in every row (and a unit diagonal when square) and saves
     the check with its synchronise."""
-    fused = True
-    check_labels = True
     _kind = None            # the kernel's name for rank_approximation; None: plain path only
 
     def __init__(self, rank_approximation, return_type='1-mAP'):
@@ -465,7 +453,7 @@ class SmoothRankAP(nn.Module):
         return rank_ap_params("sup", form, kw["tau"], kw["rho"], offset, delta, start)
 
     def _takes_fused(self, scores, target, general):
-        if not (self.fused and self._kind is not None and scores.is_cuda and scores.dtype in (torch.float32,) + _HALF):
+        if not (self._fusable(scores) and self._kind is not None):
             return False
         if not (1 <= scores.shape[0] <= RANK_AP_COLS_MAX and 1 <= scores.shape[1] <= RANK_AP_COLS_MAX):
             return False
@@ -485,13 +473,11 @@ class SmoothRankAP(nn.Module):
 
         general = force_general or scores.size(0) != scores.size(1)
         if self._takes_fused(scores, target, general):
-            want = torch.is_grad_enabled() and scores.requires_grad    # the Function itself runs with grad mode off
-            ap = _FusedRankAP.apply(scores, target.to(device=scores.device, dtype=torch.float32), self._fused_params(general), want)
+            ap = self._fused(rank_ap, None, scores, target.to(device=scores.device, dtype=torch.float32), self._fused_params(general))
+        elif general:
+            ap = self._run_plain(partial(self.general_forward, verbose=verbose), scores, target)
         else:
-            with torch.autocast(scores.device.type, enabled=False):
-                wide = scores.float() if scores.dtype in _HALF else scores
-                t = target.to(device=wide.device, dtype=wide.dtype)
-                ap = self.general_forward(wide, t, verbose=verbose) if general else self.quick_forward(wide, t)
+            ap = self._run_plain(self.quick_forward, scores, target)
 
         if self.return_type == 'AP':
             return ap

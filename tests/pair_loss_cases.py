@@ -173,6 +173,15 @@ def grad_err(got, want):
     return diff / top
 
 
+def bf16_grad_slack(got, want):
+    """The worst element of a bf16 gradient over its allowance (met when <= 0); want: the plain path's fp32 gradient.
+    The fused gradient is rounded to bf16 at the end: against the plain gradient rounded the same way, every element
+    within one bf16 last place (2^-7 of its value) plus what TOL of the largest value can move an element before rounding"""
+    got, want = got.double(), want.to(got.dtype).double()
+    slack = (got - want).abs() - (2.0 ** -7 * want.abs() + TOL * float(want.abs().max()))
+    return float(slack.max())
+
+
 def check(out, grad, ref_out, ref_grad, what):
     """out [3] and grad against a float64 reference within TOL; prints the figures first"""
     errs = [scalar_err(out[i], ref_out[i]) for i in range(3)]

@@ -1,6 +1,6 @@
 """Shared by tests/test_rank_ap_host.py, tests/test_gpu_rank_ap.py and tests/golden/make_golden_rank_ap.py: seeded inputs
 of wv_rank_ap, a float64 restatement of SmoothAP / SupAP written from their definitions (include/wvhash.h) with explicit
-loops over the queries and their positives, and the error measure (TOL, scalar_err and grad_err are pair_loss_cases.py's).
+loops over the queries and their positives, and the error measure (TOL, scalar_err, grad_err and bf16_grad_slack are pair_loss_cases.py's).
 No test functions.  Everything is made on the host, once per case (functools caches), and never modified.
 
 Shapes, the smallest where the kernel can go wrong: a bit row is made of 64-column words and a wave's lanes stride the
@@ -24,7 +24,7 @@ import functools
 import numpy as np
 import torch
 
-from pair_loss_cases import TOL, grad_err, scalar_err  # noqa: F401
+from pair_loss_cases import TOL, bf16_grad_slack, grad_err, scalar_err  # noqa: F401
 
 COLS_MAX = 4096
 DELTA = 0.05

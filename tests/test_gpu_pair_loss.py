@@ -107,12 +107,9 @@ def test_fused_function_agrees_with_the_plain_path(kind, dtype, monkeypatch):
         print(f"{kind} {dtype}: loss {ev:.2e} grad {ge:.2e}")
         assert ev <= C.TOL and ge <= C.TOL
     else:
-        # the fused gradient is rounded to bf16 at the end: against the plain gradient rounded the same way, every element
-        # within one bf16 last place (2^-7 of its value) plus what TOL of the largest value can move an element before rounding
-        got, want = e.grad.double(), wide.grad.to(dtype).double()
-        slack = (got - want).abs() - (2.0 ** -7 * want.abs() + C.TOL * float(want.abs().max()))
-        print(f"{kind} {dtype}: loss {ev:.2e} grad, worst element over its allowance {float(slack.max()):.2e}")
-        assert ev <= C.TOL and float(slack.max()) <= 0.0
+        slack = C.bf16_grad_slack(e.grad, wide.grad)
+        print(f"{kind} {dtype}: loss {ev:.2e} grad, worst element over its allowance {slack:.2e}")
+        assert ev <= C.TOL and slack <= 0.0
     m.fused = True
     with torch.no_grad():
         quiet = m(e, lab)

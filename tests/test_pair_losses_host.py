@@ -232,6 +232,32 @@ def test_wrapper_gate():
     assert torch.equal(L.pair_loss_host(half, lp, p)[0], L.pair_loss_host(half.float(), lp, p)[0])
 
 
+@pytest.mark.parametrize("kind", ["sch_tanh", "hashnet_s3"])
+def test_fused_function_over_the_host_twin(kind):
+    """The autograd Function of the modules' fused path, run over pair_loss_host: value and gradient through a non-unit
+    grad_output (3 * loss) against the plain path on the same fp32 input; a bf16 input gets a bf16 gradient; with
+    want=False nothing is saved and the value has the same bits."""
+    case = next(c for c in C.CASES if c.B == 33 and c.D == 64 and c.kind == kind)
+    x = C.inputs(case)
+    params = C.params_of(x)
+    e = x.e.clone().requires_grad_(True)
+    val = L._FusedLoss.apply(L.pair_loss_host, 0, e, x.packed, params, True)
+    (3.0 * val).backward()
+    wide = x.e.clone().requires_grad_(True)
+    ref = _module(x.loss, case.D, x.alpha, x.beta, x.apply_tanh, x.pre_scale)(wide, x.labels)
+    (3.0 * ref).backward()
+    ev, eg = C.scalar_err(val, ref.detach().double()), C.grad_err(e.grad, wide.grad.double())
+    print(f"{kind}: loss {ev:.2e} grad {eg:.2e}")
+    assert val.shape == () and val.dtype == torch.float32 and e.grad.dtype == torch.float32
+    assert ev <= C.TOL and eg <= C.TOL
+    eb = x.e.bfloat16().requires_grad_(True)
+    L._FusedLoss.apply(L.pair_loss_host, 0, eb, x.packed, params, True).backward()
+    assert eb.grad.dtype == torch.bfloat16 and eb.grad.shape == eb.shape
+    quiet = L._FusedLoss.apply(L.pair_loss_host, 0, e, x.packed, params, False)
+    assert quiet.grad_fn.saved_tensors == ()
+    assert torch.equal(quiet.detach().view(torch.int32), val.detach().view(torch.int32))
+
+
 # ------------------------------------------------------------------------------------------------ train_step, gloo
 def _worker(rank, world, port, out_dir):
     sys.path.insert(0, ROOT)

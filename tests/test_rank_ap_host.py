@@ -199,6 +199,33 @@ def test_plain_path_takes_what_the_fused_path_does_not():
         L.SupAP(delta=None)(x.scores, x.target)                            # offset=None too: as in the reference
 
 
+@pytest.mark.parametrize("name, form", [("16x50", "general"), ("65x65", "quick")])
+def test_fused_function_over_the_host_twin(name, form):
+    """The autograd Function of the modules' fused path, run over rank_ap_host: AP and gradient through a grad_output that
+    differs row by row against the plain path on the same fp32 input; a bf16 input gets a bf16 gradient; with want=False
+    nothing is saved and the value has the same bits."""
+    case = next(c for c in C.CASES if c.name == name and c.kind == "sup" and c.form == form)
+    x = C.inputs(case)
+    params = C.params_of(x)
+    weights = torch.linspace(0.5, 2.0, case.B)
+    s = x.scores.clone().requires_grad_(True)
+    ap = L._FusedLoss.apply(L.rank_ap_host, None, s, x.target, params, True)
+    (weights * ap).sum().backward()
+    wide = x.scores.clone().requires_grad_(True)
+    ref = C.module_of(case, "AP")(wide, x.target, force_general=form == "general")
+    (weights * ref).sum().backward()
+    ea, eg = _errs(ap, s.grad, ref.detach().double(), wide.grad.double())
+    print(f"{name} {form}: ap {ea:.2e} grad {eg:.2e}")
+    assert ap.shape == (case.B,) and ap.dtype == torch.float32 and s.grad.dtype == torch.float32
+    assert ea <= C.TOL and eg <= C.TOL
+    sb = x.scores.bfloat16().requires_grad_(True)
+    L._FusedLoss.apply(L.rank_ap_host, None, sb, x.target, params, True).sum().backward()
+    assert sb.grad.dtype == torch.bfloat16 and sb.grad.shape == sb.shape
+    quiet = L._FusedLoss.apply(L.rank_ap_host, None, s, x.target, params, False)
+    assert quiet.grad_fn.saved_tensors == ()
+    assert torch.equal(quiet.detach().view(torch.int32), ap.detach().view(torch.int32))
+
+
 def test_train_step_reaches_the_score_matrix_branch():
     from wvhash.engine import train_step
     torch.manual_seed(0)

@@ -28,17 +28,9 @@ sys.path[:0] = [".", "image-retrieval-wavelet_amd"]
 from wvhash import _lib  # noqa: E402
 from wvhash.engine import batch_map, hamming as H  # noqa: E402
 from wvhash.engine.get_knn import knn_float  # noqa: E402
+from _timing import event_ms, spread  # noqa: E402
 
 BATCHES, D, CLASSES, P_TAG = (96, 256, 1024), 64, 38, 0.10
-
-
-def event_ms(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
 
 
 def host_ms(fn):
@@ -65,10 +57,6 @@ def reference_sequence(emb, lab):
         count = torch.arange(1, tsum + 1, device=emb.device).float()
         total += torch.mean(count / tindex).item()
     return total / emb.shape[0]
-
-
-def spread(v):
-    return {"ms": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
 
 
 def main():

@@ -13,28 +13,15 @@ a kernel's share of any peak.  Prints one JSON row.
 """
 import argparse
 import json
-import statistics
 import sys
 
 import torch
 
 sys.path[:0] = [".", "image-retrieval-wavelet_amd"]
 from wvhash import losses as L  # noqa: E402
+from _timing import fused_against_plain  # noqa: E402
 
 BATCHES, D, CLASSES, P_TAG = (64, 96, 128, 1024), 64, 38, 0.08
-
-
-def event_ms(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def spread(v):
-    return {"ms": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
 
 
 def modules():
@@ -64,23 +51,8 @@ def main():
                 val.backward()
                 return val.detach(), emb.grad
 
-            variants = {"fused": lambda: step(fused), "plain": lambda: step(plain)}
-            (fv, fg), (pv, pg) = variants["fused"](), variants["plain"]()
-            dv = abs(float(fv) - float(pv)) / abs(float(pv))
-            dg = float((fg - pg).abs().max() / pg.abs().max())
-            for _ in range(5):                                                   # warm-up: code objects, allocator, clocks
-                for fn in variants.values():
-                    fn()
-            torch.cuda.synchronize()
-            ms = {v: [] for v in variants}
-            for _ in range(args.rounds):                                         # alternating
-                for v, fn in variants.items():
-                    ms[v] += [event_ms(fn) for _ in range(args.calls)]
-            med = {v: statistics.median(t) for v, t in ms.items()}
-            rows.append({"loss": kind, "B": B, "D": D, "value_rel_diff": dv, "grad_normwise_diff": dg,
-                         "calls_per_variant": args.rounds * args.calls, "fused": spread(ms["fused"]), "plain": spread(ms["plain"]),
-                         "plain_over_fused": round(med["plain"] / med["fused"], 3),
-                         "fused_faster_than_plain": bool(med["fused"] < med["plain"])})
+            rows.append({"loss": kind, "B": B, "D": D,
+                         **fused_against_plain(lambda: step(fused), lambda: step(plain), 5, args.rounds, args.calls)})
     row = {"what": "loss + backward to the embeddings: wv_pair_loss behind the autograd Function (fused) against the plain "
                    "PyTorch path of the same module; SCHLoss(alpha=1, beta=1, apply_tanh=True), HashNetAdapter at scale 1",
            "device": torch.cuda.get_device_name(0), "classes": CLASSES, "p_tag": P_TAG,

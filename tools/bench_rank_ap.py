@@ -15,7 +15,6 @@ numbers are compared first (value relative, gradient norm-wise).  Prints one JSO
 """
 import argparse
 import json
-import statistics
 import sys
 
 import torch
@@ -23,31 +22,10 @@ import torch.nn.functional as F
 
 sys.path[:0] = [".", "image-retrieval-wavelet_amd"]
 from wvhash import losses as L  # noqa: E402
+from _timing import fused_against_plain  # noqa: E402
 
 SHAPES = ((96, 96), (256, 256), (512, 512), (96, 4096))
 D, CLASSES, P_TAG = 64, 38, 0.08
-
-
-def event_ms(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-def spread(v):
-    return {"ms": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
-
-
-def peak_bytes(fn):
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    fn()
-    torch.cuda.synchronize()
-    return torch.cuda.max_memory_allocated() - base
 
 
 def modules():
@@ -86,25 +64,8 @@ def main():
                 val.backward()
                 return val.detach(), scores.grad
 
-            variants = {"fused": lambda: step(fused), "plain": lambda: step(plain)}
-            (fv, fg), (pv, pg) = variants["fused"](), variants["plain"]()
-            dv = abs(float(fv) - float(pv)) / abs(float(pv))
-            dg = float((fg - pg).abs().max() / pg.abs().max())
-            for _ in range(3):                                                   # warm-up: code objects, allocator, clocks
-                for fn in variants.values():
-                    fn()
-            mem = {v: peak_bytes(fn) for v, fn in variants.items()}
-            ms = {v: [] for v in variants}
-            for _ in range(args.rounds):                                         # alternating
-                for v, fn in variants.items():
-                    ms[v] += [event_ms(fn) for _ in range(args.calls)]
-            med = {v: statistics.median(t) for v, t in ms.items()}
-            per_loss[kind] = {"value_rel_diff": dv, "grad_normwise_diff": dg, "calls_per_variant": args.rounds * args.calls,
-                              "fused": spread(ms["fused"]), "plain": spread(ms["plain"]),
-                              "fused_peak_bytes": mem["fused"], "plain_peak_bytes": mem["plain"],
-                              "plain_over_fused": round(med["plain"] / med["fused"], 3),
-                              "fused_faster_than_plain": bool(med["fused"] < med["plain"])}
-            del fused, plain, variants
+            per_loss[kind] = fused_against_plain(lambda: step(fused), lambda: step(plain), 3, args.rounds, args.calls, memory=True)
+            del fused, plain
             scores.grad = None
             torch.cuda.empty_cache()
         row = {"what": "loss (1 - mAP) + backward to the scores: wv_rank_ap behind the autograd Function (fused) against the "
