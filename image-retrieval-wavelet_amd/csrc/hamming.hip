@@ -99,13 +99,20 @@ __global__ __launch_bounds__(256) void k_hamming_dist(const uint64_t *__restrict
         constexpr int PER_THREAD = Cfg::THREAD_BYTES / 16;                 // chunks owned per thread
         const int64_t tile_bytes_valid = (min((int64_t)Cfg::TILE, N - n_tile)) * Cfg::CODE_BYTES;
         const uint8_t *gsrc = reinterpret_cast<const uint8_t *>(db) + n_tile * Cfg::CODE_BYTES;
+        const bool db16 = (reinterpret_cast<uintptr_t>(db) & 15) == 0;     // tiles start at multiples of 16 bytes: uniform
 #pragma unroll
         for (int i = 0; i < CHUNKS / 256; ++i) {
             const int ch = i * 256 + tid;
             const int64_t off = (int64_t)ch * 16;
             uint4 v = make_uint4(0, 0, 0, 0);
             if (off + 16 <= tile_bytes_valid) {
-                v = *reinterpret_cast<const uint4 *>(gsrc + off);
+                if (db16) {
+                    v = *reinterpret_cast<const uint4 *>(gsrc + off);
+                } else {                          // db at 8 mod 16 (a row slice of 64-bit codes): two natural 8-byte loads
+                    const uint64_t lo = *reinterpret_cast<const uint64_t *>(gsrc + off);
+                    const uint64_t hi = *reinterpret_cast<const uint64_t *>(gsrc + off + 8);
+                    v = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+                }
             } else if (off < tile_bytes_valid) {  // WORDS odd: last valid code straddles a chunk
                 const uint64_t lo = *reinterpret_cast<const uint64_t *>(gsrc + off);
                 v.x = (uint32_t)lo; v.y = (uint32_t)(lo >> 32);
@@ -180,6 +187,7 @@ __global__ __launch_bounds__(256) void k_db_permute(const uint64_t *__restrict__
     const int64_t total = tiles * PT * 256;
     const int64_t valid_bytes = N * Cfg::CODE_BYTES;
     const uint8_t *src = reinterpret_cast<const uint8_t *>(db);
+    const bool db16 = (reinterpret_cast<uintptr_t>(db) & 15) == 0;     // every `off` is a multiple of 16: uniform
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int t = (int)(i & 255);
         const int64_t tj = i >> 8;
@@ -188,7 +196,13 @@ __global__ __launch_bounds__(256) void k_db_permute(const uint64_t *__restrict__
         const int64_t off = tile * Cfg::TILE * Cfg::CODE_BYTES + (int64_t)t * Cfg::THREAD_BYTES + 16 * j;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (off + 16 <= valid_bytes) {
-            v = *reinterpret_cast<const uint4 *>(src + off);
+            if (db16) {
+                v = *reinterpret_cast<const uint4 *>(src + off);
+            } else {                              // db at 8 mod 16 (a row slice of 64-bit codes): two natural 8-byte loads
+                const uint64_t lo = *reinterpret_cast<const uint64_t *>(src + off);
+                const uint64_t hi = *reinterpret_cast<const uint64_t *>(src + off + 8);
+                v = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+            }
         } else if (off < valid_bytes) {
             const uint64_t lo = *reinterpret_cast<const uint64_t *>(src + off);
             v.x = (uint32_t)lo; v.y = (uint32_t)(lo >> 32);
@@ -407,6 +421,7 @@ extern "C" int wv_hamming_dist_prepared(const uint64_t *q, const void *prepared,
     WV_REQUIRE(Q >= 0 && N >= 0 && ld_dist >= N, "hamming_dist_prepared: bad shape Q=%d N=%lld ld=%lld", Q,
                (long long)N, (long long)ld_dist);
     WV_REQUIRE(words >= 1 && words <= 4, "hamming_dist_prepared: words=%d (nbits must be <= 255)", words);
+    WV_REQUIRE((reinterpret_cast<uintptr_t>(prepared) & 15) == 0, "hamming_dist_prepared: prepared must be 16-byte aligned");
     if (Q == 0 || N == 0) return WV_OK;
     hipStream_t st = (hipStream_t)stream;
     switch (words) {

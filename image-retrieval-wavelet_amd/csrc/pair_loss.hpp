@@ -59,6 +59,7 @@ inline int pair_loss_args(const char *what, const void *e, const void *labels, i
         if (ws_bytes < pair_loss_ws_bytes(B, D))
             WV_FAIL(WV_EINVAL, "%s: workspace of %zu bytes, %zu needed (wv_pair_loss_workspace_bytes)", what, ws_bytes,
                     pair_loss_ws_bytes(B, D));
+        if (reinterpret_cast<uintptr_t>(ws) & 15) WV_FAIL(WV_EINVAL, "%s: workspace must be 16-byte aligned", what);
     }
     return WV_OK;
 }

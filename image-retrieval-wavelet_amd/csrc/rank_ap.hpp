@@ -52,6 +52,7 @@ inline int rank_ap_args(const char *what, const void *scores, const void *target
         if (ws_bytes < rank_ap_ws_bytes(B, M, p->form))
             WV_FAIL(WV_EINVAL, "%s: workspace of %zu bytes, %zu needed (wv_rank_ap_workspace_bytes)", what, ws_bytes,
                     rank_ap_ws_bytes(B, M, p->form));
+        if (reinterpret_cast<uintptr_t>(ws) & 15) WV_FAIL(WV_EINVAL, "%s: workspace must be 16-byte aligned", what);
     }
     return WV_OK;
 }

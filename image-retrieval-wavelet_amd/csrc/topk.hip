@@ -722,11 +722,19 @@ static int validate_rank_ids(const char *what, bool buffers, int Q, int64_t N, i
     return WV_OK;
 }
 
+// Prepared blobs and workspaces hold the kernels' images, which are read and written 16 bytes at a time (uint4): a caller that
+// carves one out of a larger arena at another alignment is refused here, before anything is launched (NULL passes: absent).
+static int require_aligned16(const char *what, const char *name, const void *p)
+{
+    WV_REQUIRE((reinterpret_cast<uintptr_t>(p) & 15) == 0, "%s: %s must be 16-byte aligned", what, name);
+    return WV_OK;
+}
+
 static int require_workspace(const char *what, const void *workspace, size_t workspace_bytes, int Q, int64_t N, int nbits, int k)
 {
     const size_t need = wv_hamming_topk_workspace_bytes(Q, N, (nbits + 63) / 64, k);
     if (!workspace || workspace_bytes < need) WV_FAIL(WV_ENOMEM, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-    return WV_OK;
+    return require_aligned16(what, "workspace", workspace);
 }
 
 }  // namespace wv
@@ -762,6 +770,7 @@ extern "C" int wv_db_prepare(const uint64_t *db, int64_t N, int words, void *pre
 {
     WV_REQUIRE(db && prepared, "db_prepare: null buffer");
     WV_REQUIRE(N >= 1 && words >= 1 && words <= 4, "db_prepare: bad shape N=%lld words=%d", (long long)N, words);
+    if (int rc = require_aligned16("db_prepare", "prepared", prepared)) return rc;
     const BlobLayout L = blob_layout(N, words);
     if (prepared_bytes < L.total) WV_FAIL(WV_ENOMEM, "db_prepare: buffer %zu < %zu bytes", prepared_bytes, L.total);
     hipStream_t st = (hipStream_t)stream;
@@ -778,6 +787,7 @@ extern "C" int wv_hamming_topk_prepared(const uint64_t *q, const void *prepared,
                                         int64_t N, int nbits, int k, int64_t idx_offset, void *stream)
 {
     if (int rc = validate_rank_ids("hamming_topk_prepared", q && prepared && idx, Q, N, nbits, k, idx_offset)) return rc;
+    if (int rc = require_aligned16("hamming_topk_prepared", "prepared", prepared)) return rc;
     if (Q == 0) return WV_OK;
     return launch_topk(q, nullptr, prepared, idx, dist, Q, N, nbits, k, idx_offset, nullptr, (hipStream_t)stream);
 }
@@ -1040,6 +1050,7 @@ extern "C" int wv_hamming_topk_ex(const uint64_t *q, const uint64_t *db, const v
                                   void *workspace, size_t workspace_bytes, void *stream)
 {
     if (int rc = validate_rank_ids("hamming_topk_ex", q && idx && (db || prepared), Q, N, nbits, k, idx_offset)) return rc;
+    if (int rc = require_aligned16("hamming_topk_ex", "prepared", prepared)) return rc;
     if (Q == 0) return WV_OK;
     if (!prepared)
         if (int rc = require_workspace("hamming_topk_ex", workspace, workspace_bytes, Q, N, nbits, k)) return rc;
@@ -1062,6 +1073,7 @@ extern "C" int wv_rank_labels_prepare(const uint64_t *dblab, int64_t N, int lwor
         WV_FAIL(WV_ENOTSUP, "rank_labels_prepare: %lld rows x %d label words are outside the fused kernels (<= 32768 rows, <= 128 classes)",
                 (long long)N, lwords);
     if (prepared_bytes < need) WV_FAIL(WV_ENOMEM, "rank_labels_prepare: buffer %zu < %zu bytes", prepared_bytes, need);
+    if (int rc = require_aligned16("rank_labels_prepare", "prepared_labels", prepared_labels)) return rc;
     return rank2_labels_prepare(dblab, prepared_labels, N, lwords, (hipStream_t)stream);
 }
 
@@ -1069,6 +1081,8 @@ extern "C" int wv_rank_labels_prepare(const uint64_t *dblab, int64_t N, int lwor
 static int fused_call(const char *what, RankMode mode, const uint64_t *q, const void *prepared, const Rank2Ap &apx, uint32_t *cum, int Q,
                       int64_t N, int nbits, int k, void *stream)
 {
+    if (int rc = require_aligned16(what, "prepared", prepared)) return rc;
+    if (int rc = require_aligned16(what, "prepared_labels", apx.cls)) return rc;
     const RankPlan plan = rank_plan(Q, N, nbits, k, mode);
     if (plan.kernel == RankKernel::none) return rank_refuse(what, plan, N, k);
     return rank2_launch(plan, q, blob_image(prepared, N, (nbits + 63) / 64, plan.kernel), nullptr, nullptr, nullptr, cum, Q, N, nbits, k,
@@ -1094,6 +1108,8 @@ extern "C" int wv_hamming_radius_hist(const uint64_t *q, const void *prepared, c
     if (lwords > 2) WV_FAIL(WV_ENOTSUP, "hamming_radius_hist: %d label words (more than 128 classes)", lwords);
     if (int rc = validate_rank_shape("hamming_radius_hist", q && prepared && prepared_labels && qlab && cum && cumrel, Q, N, nbits)) return rc;
     if (Q == 0) return WV_OK;
+    if (int rc = require_aligned16("hamming_radius_hist", "prepared", prepared)) return rc;
+    if (int rc = require_aligned16("hamming_radius_hist", "prepared_labels", prepared_labels)) return rc;
     const RankPlan plan = rank_plan(Q, N, nbits, 0, RankMode::radius);
     if (plan.kernel == RankKernel::none) return rank_refuse("hamming_radius_hist", plan, N, 0);
     const Rank2Ap apx{(const uint32_t *)prepared_labels, qlab, lwords, nullptr, nullptr, nullptr, 0, 0};
@@ -1108,6 +1124,7 @@ static int shard_call(const char *what, RankMode mode, const uint64_t *q, const 
 {
     const RankPlan plan = rank_plan(Q, N, nbits, k, mode);
     if (plan.kernel == RankKernel::none) return rank_refuse(what, plan, N, k);
+    if (int rc = require_aligned16(what, "prepared", prepared)) return rc;
     if (!prepared)
         if (int rc = require_workspace(what, workspace, workspace_bytes, Q, N, nbits, k)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1193,6 +1210,8 @@ extern "C" int wv_hamming_map_at_ks(const uint64_t *q, const void *prepared, con
     ApCuts cuts;
     if (int rc = validate_cuts("hamming_map_at_ks", ks, nk, N, "N", cuts)) return rc;
     if (Q == 0) return WV_OK;
+    if (int rc = require_aligned16("hamming_map_at_ks", "prepared", prepared)) return rc;
+    if (int rc = require_aligned16("hamming_map_at_ks", "prepared_labels", prepared_labels)) return rc;
     const int kmax = cuts.k[nk - 1];
     const RankPlan plan = rank_plan(Q, N, nbits, kmax, RankMode::ap);    // list, window, LDS and bitmap: sized by the largest cut-off
     if (plan.kernel == RankKernel::none)

@@ -17,6 +17,14 @@
  *     work: no hidden synchronisation, no host<->device copies.
  *   - Thread-safe and re-entrant; no global mutable state except the per-thread error string.
  *   - One process per GPU; the current HIP device of the calling thread is used.
+ *   - Alignment.  For the ranking, metric and loss entry points (wv_hamming_dist ... wv_hit_prefix, wv_ip_map_at_k,
+ *     wv_group_layernorm, wv_pair_loss, wv_rank_ap) every typed pointer needs the natural alignment of its element and no
+ *     more: 1 byte for uint8 distance rows and matrices, 2 for uint16 rows and bf16, 4 for int32 / uint32 / float, 8 for
+ *     uint64 / double.  Kernels that move 16 bytes at a time test the address (and the row pitch) at run time and take an
+ *     element-wise path otherwise: the same bits at any alignment.  The exception is opaque memory: every `workspace`,
+ *     `prepared` and `prepared_labels` of these entry points holds images the kernels read and write as 16-byte words and
+ *     must be 16-BYTE ALIGNED; anything else is WV_EINVAL, answered on the host before any launch, no buffer touched.
+ *     (wv_knn_float states its own 16 bytes below.)  tests/test_gpu_buffer_contract.py holds the entry points to this.
  */
 #ifndef WVHASH_H
 #define WVHASH_H
@@ -234,6 +242,7 @@ int wv_bit_counts(const uint64_t *packed, int64_t rows, int nbits, uint32_t *cou
  * Hamming distances.  Replaces calc_hamming_dist (accuracy_calculator.py:183-186),
  * 0.5 * (B - q @ r.T), for +-1 codes, where it is an exact small integer.
  * dist[qi * ld_dist + n] = popcount(q[qi] ^ db[n]),  uint8 (nbits <= 255).
+ * q, db: 8-byte aligned (a row slice of a larger database is fine); dist: any address, any ld_dist >= N.
  * ------------------------------------------------------------------------------------------ */
 int wv_hamming_dist(const uint64_t *q, const uint64_t *db, uint8_t *dist, int64_t ld_dist, int Q,
                     int64_t N, int words, void *stream);
@@ -246,7 +255,9 @@ int wv_hamming_dist(const uint64_t *q, const uint64_t *db, uint8_t *dist, int64_
  *   (get_knn.py:63-66; IP score = nbits - 2 * dist), and faiss IndexFlatIP.search (:35-52).
  * idx : int32 [Q][k], values = local row + idx_offset (idx_offset = first global row of this
  *       shard when the database is row-sharded across GPUs).
- * dist: uint8 [Q][k].        Requires 1 <= k <= N, nbits <= 128.
+ * dist: uint8 [Q][k], or NULL when only the lists are wanted (the lists have the same bits).   Requires 1 <= k <= N, nbits <= 128.
+ * idx 4-byte aligned, dist at any address (any k: the rows of odd k start at every residue);  workspace: 16-byte aligned,
+ * wv_hamming_topk_workspace_bytes() bytes, written before it is read (old content is never looked at).
  * ------------------------------------------------------------------------------------------ */
 size_t wv_hamming_topk_workspace_bytes(int Q, int64_t N, int words, int k);
 int wv_hamming_topk(const uint64_t *q, const uint64_t *db, int32_t *idx, uint8_t *dist, int Q,
@@ -258,7 +269,8 @@ int wv_hamming_topk(const uint64_t *q, const uint64_t *db, int32_t *idx, uint8_t
  * here the per-database work is explicit: wv_db_prepare lays the packed codes out once in the two
  * images the kernels read with fully coalesced loads (distance tile image + ranking column image),
  * and the *_prepared entry points skip the per-call re-layout.  Results are identical to the
- * plain entry points.  `prepared` is caller-owned device memory of wv_db_prepared_bytes() bytes.
+ * plain entry points.  `prepared` is caller-owned device memory of wv_db_prepared_bytes() bytes, 16-byte aligned (WV_EINVAL
+ * otherwise, here and in every entry point that reads it); wv_db_prepare writes every byte a reader looks at.  db: 8-byte aligned.
  * ------------------------------------------------------------------------------------------ */
 size_t wv_db_prepared_bytes(int64_t N, int words);
 int wv_db_prepare(const uint64_t *db, int64_t N, int words, void *prepared, size_t prepared_bytes,
@@ -269,7 +281,7 @@ int wv_hamming_topk_prepared(const uint64_t *q, const void *prepared, int32_t *i
                              int64_t N, int nbits, int k, int64_t idx_offset, void *stream);
 
 /* Same ranking with every option: `prepared` (or NULL) instead of / beside `db`, and `cum` (or NULL):
- * uint32 [Q][nbits + 2], cum[q][b] = number of database rows of THIS call with distance < b (cum[q][nbits+1] = N).
+ * uint32 [Q][nbits + 2] (4-byte aligned), cum[q][b] = number of database rows of THIS call with distance < b (cum[q][nbits+1] = N).
  * A row-sharded search all-reduces `cum` to learn each query's global k-th distance, and then exchanges only
  * the list prefixes that can matter (wvhash/parallel.py) -- the role faiss' host-side shard merge plays at
  * get_knn.py:41-44. */
@@ -284,7 +296,7 @@ int wv_hamming_topk_ex(const uint64_t *q, const uint64_t *db, const void *prepar
  * what wv_map_at_k returns for wv_hamming_topk's list (same summation order; bit-identical at 256 threads per query).
  *   prepared         wv_db_prepare's blob of the database codes
  *   prepared_labels  wv_rank_labels_prepare's class-major bit matrix of the rows' label words
- *                    (wv_rank_labels_prepared_bytes(N) bytes; 0 = N is outside the windowed kernel)
+ *                    (wv_rank_labels_prepared_bytes(N) bytes; 0 = N is outside the windowed kernel); 16-byte aligned like `prepared`
  * Returns WV_ENOTSUP for shapes outside the fused kernel (more than 32,768 rows, k > 32,639 -- the list is built in LDS with
  * 16-bit cells --, lists that do not fit LDS beside the label bitmap, ...; mAP@ALL with k = N is inside for N <= 32,639): the caller then runs
  * wv_hamming_topk + wv_map_at_k. */
@@ -300,7 +312,8 @@ int wv_hamming_map_at_k(const uint64_t *q, const void *prepared, const void *pre
  *                          query, hence how long a list prefix each shard has to contribute (about k / shards + ties).
  *   wv_hamming_topk_rows16 the k nearest rows of the shard per query in (distance, row) order as 16-bit LOCAL row numbers,
  *                          uint16 [Q][k] -- the wire format wv_topk_merge_cum reads -- with k = that prefix length.
- * Returns WV_ENOTSUP for shards outside the windowed kernel's range (the caller then uses wv_hamming_topk_ex). */
+ * Returns WV_ENOTSUP for shards outside the windowed kernel's range (the caller then uses wv_hamming_topk_ex).
+ * rows: 2-byte aligned (odd k: the rows of odd queries start at 2 mod 4), cum: 4-byte aligned; workspace / prepared: 16 bytes. */
 int wv_hamming_hist(const uint64_t *q, const uint64_t *db, const void *prepared, uint32_t *cum, int Q, int64_t N, int nbits,
                     void *workspace, size_t workspace_bytes, void *stream);
 int wv_hamming_topk_rows16(const uint64_t *q, const uint64_t *db, const void *prepared, uint16_t *rows, int Q, int64_t N,
@@ -345,7 +358,8 @@ int wv_topk_merge_cum_need(const uint16_t *idx_local, const uint32_t *cum, int G
  *   wv_merge_relbits_map      relbits [G][Q][ceil(kin / 64)], cum [G][Q][nbits + 2] -> ap float32 [Q], nrel int32 [Q] (or NULL),
  *                             need_out as in wv_topk_merge_cum_need
  * relbits_ld / cum_ld: row pitches in uint64 / uint32 units (0 = tight): string and histogram of a (query, shard) may lie side
- * by side in ONE wire buffer, so that a single all_to_all moves both.
+ * by side in ONE wire buffer, so that a single all_to_all moves both; words of a row that belong to neither are not written.
+ * relbits 8-byte, cum 4-byte aligned.
  * WV_ENOTSUP outside the windowed kernel's range (shards of more than 32,768 rows, k > 32,639, wider labels); any k inside it:
  * a shard can send the relevance string of its whole ranking (mAP@ALL). */
 int wv_hamming_shard_relbits(const uint64_t *q, const void *prepared, const void *prepared_labels, const uint64_t *qlab,
@@ -373,7 +387,7 @@ int wv_hamming_radius_hist(const uint64_t *q, const void *prepared, const void *
 int wv_hamming_radius_hist_cpu(const uint64_t *q, const uint64_t *db, const uint64_t *qlab, const uint64_t *dblab, int lwords, int Q,
                                int64_t N, int nbits, uint32_t *cum, uint32_t *cumrel);
 
-/* Ranking from a stored distance matrix row (same order as wv_hamming_topk). */
+/* Ranking from a stored distance matrix row (same order as wv_hamming_topk).  dist_matrix: any address, any ld_dist >= N. */
 int wv_rank_from_dist(const uint8_t *dist_matrix, int64_t ld_dist, int Q, int64_t N, int nbits,
                       int32_t *idx, uint8_t *dist, int k, void *stream);
 
@@ -507,7 +521,8 @@ int wv_rank_scores_cpu(const float *S, int Q, int64_t N, int k, int flags, int32
  * (main/engine/batch_map.py, base_update.py:70-73,287-290).  The small problem -- no list wanted, one launch before a
  * .item(); large shapes are wv_knn_float + wv_map_at_k.
  *   q [Q][D], db [N][D] float32, dense; qlab [Q][lwords], dblab [N][lwords]: labels packed by wv_pack_bits(mode 1)
- *   ap float32 [Q], nrel int32 [Q] or NULL
+ *   ap float32 [Q], nrel int32 [Q] or NULL.  Every pointer at its natural alignment (D % 4 == 0 and db 16-byte aligned loads
+ *   db 16 bytes at a time; any other db four bytes at a time: the same bits)
  * The contract, the same for the kernel and the host twin, bit for bit:
  *   score      s(q, n) = the fp32 value wv_knn_float(metric = WV_METRIC_IP) writes for the pair: one fmaf chain from 0.0f over
  *              k in the order the matrix cores accumulate it (8c + e, 8c + 4 + e for e = 0..3 of every chunk c of eight).
@@ -755,7 +770,8 @@ int wv_colour_jitter_check(const wv_colour_ops *ops, int n);
  * Sequence n takes gamma / beta of group n / ceil(N / G): torch.chunk, including N % G != 0 and N < G (fewer groups in use).
  * Per row, in fp32: mean, biased variance of the centred values, 1 / sqrt(var + eps), ((x - mean) * rstd) * gamma + beta;
  * bf16 is widened on load and rounded to nearest even on store.  Any E >= 1; E % 4 == 0 moves 16 bytes (fp32) or 8 bytes
- * (bf16) per lane.  N * T == 0: WV_OK, nothing touched (pointers may be NULL).
+ * (bf16) per lane when x, out, gamma and beta are aligned to it, element by element otherwise: the same bits.  N * T == 0: WV_OK,
+ * nothing touched (pointers may be NULL).
  * wv_group_layernorm       DEVICE pointers; one launch on `stream`, no workspace, no hidden synchronisation.
  * wv_group_layernorm_cpu   host twin (HOST pointers): the kernel's order of sums replayed, equal to it bit for bit.
  * wv_group_layernorm_check the argument check both run first: WV_EINVAL for an unknown dtype, N < 0, T < 0, E < 1, G < 1;
@@ -788,7 +804,8 @@ int wv_group_layernorm_cpu(const void *x, int x_dtype, void *out, int out_dtype,
  *                         loss = sum_P t / S1 + sum_notP t / S0, an empty class contributing nothing.  nbits, beta unused.
  * fp32 arithmetic (G by fmaf), the two global sums in double.  No floating-point atomics: the same call gives the same bits.
  * Everything is enqueued on `stream`; no hidden synchronisation.
- * workspace: device memory of wv_pair_loss_workspace_bytes(B, D) bytes (two [B][D] fp32 sums + one record per 8 rows).
+ * workspace: device memory of wv_pair_loss_workspace_bytes(B, D) bytes (two [B][D] fp32 sums + one record per 8 rows), 16-byte
+ * aligned (WV_EINVAL otherwise), written before it is read.  e, out, grad: 4-byte aligned.
  * Arguments are checked on the host before any pointer is read: WV_EINVAL for a null pointer (grad excepted), B < 1, D < 1,
  * lwords outside {1, 2}, an unknown kind, pre_scale <= 0, a workspace shorter than the query says; WV_ENOTSUP for
  * B > WV_PAIR_LOSS_ROWS_MAX or D > 512; the message names the argument.
@@ -839,7 +856,8 @@ int wv_pair_loss_cpu(const float *e, const uint64_t *labels, int lwords, int B, 
  * Two launches for the general form (bit-packing of T; the rows), three for the quick form (the bit rows of LM between
  * them), all on `stream`; no hidden synchronisation.
  * workspace: device memory of wv_rank_ap_workspace_bytes(B, M, form) bytes: the bit rows of T, [B][ceil(M / 64)] 64-bit
- * words, and for the quick form as many for LM.
+ * words, and for the quick form as many for LM; 16-byte aligned (WV_EINVAL otherwise), written before it is read.  scores,
+ * target, ap, grad: 4-byte aligned.
  * Arguments are checked on the host before any pointer is read: WV_EINVAL for a null pointer (grad excepted), B < 1, M < 1, an
  * unknown kind or form, the quick form with B != M, tau not > 0, a workspace shorter than the query says; WV_ENOTSUP for
  * B or M above WV_RANK_AP_COLS_MAX (a row, its bit mask, its positives' list and their records live in one workgroup's LDS).

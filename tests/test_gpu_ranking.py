@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import ranking
+from ranking_cases import spread_codes as _spread_codes
 from wvhash import synth
 from wvhash.engine import CustomCalculator, get_knn, hamming as H
 
@@ -457,23 +458,6 @@ def test_l2_values_follow_the_selected_reference_backend(gold):
 
 
 # ---------------------------------------------------------------------------------- windowed kernel (rank2.hip)
-def _spread_codes(Q, N, nbits, seed):
-    """Distances of every query spread over (nearly) all bins: row j differs from a base code in j % (nbits + 1) bits,
-    queries differ from it in a few more -- the ranking needs several 32-bin windows."""
-    g = torch.Generator().manual_seed(seed)
-    base = torch.randint(0, 2, (nbits,), generator=g).float() * 2 - 1
-    r = base.repeat(N, 1)
-    flips = torch.randint(0, nbits + 1, (N,), generator=g)
-    for j in range(N):
-        pos = torch.randperm(nbits, generator=g)[:int(flips[j])]
-        r[j, pos] *= -1
-    q = base.repeat(Q, 1)
-    for i in range(Q):
-        pos = torch.randperm(nbits, generator=g)[:i % 7]
-        q[i, pos] *= -1
-    return q, r
-
-
 @pytest.mark.parametrize("variant", ["256", "64", "0"])
 @pytest.mark.parametrize("Q,N,nbits,k", [(9, 3000, 64, 2500), (5, 3000, 128, 3000), (33, 1000, 64, 37), (6, 257, 32, 257),
                                           (4100, 700, 64, 200)])
