@@ -18,7 +18,15 @@ coarsest level only.  Accumulation is in float32, tap order m = 0..L-1, no FMA, 
 single-precision C path PyWavelets takes for float32 input.
 
 PARITY STATUS: parity unpinned against PyWavelets itself (see oracle/swt_oracle.c header);
-pinned by the analytic known answers in tests/test_oracle_swt.py.
+pinned by the analytic known answers in tests/test_oracle_swt.py, and -- tests/test_swt_anchor.py,
+table in tests/swt_anchor_cases.py -- by numbers the REFERENCE's own lifting code produced
+(main/transforms/wavelets/{haar,daub_4,cdf_97}.py run level after level on LL: the decimated
+transform is the stationary one sampled on the 2^n lattice).  Pinned that way: the tap offset, the
+axis order, cH = 'da', the sign of dec_hi (opposite to the detail filter of all three liftings) and
+the tap tables of haar levels 1-3, db2 levels 1-3, bior4.4 levels 1-2; wavedec2_coarsest at level 1
+off its border.  Still unpinned: db4 and the computed dbN (the reference has no lifting for them),
+the periodic wrap at the border (the lifting pads with zeros there), DWT levels >= 2 (the symmetric
+extension moves the second decimation to the other phase), and PyWavelets' executed output.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """

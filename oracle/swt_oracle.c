@@ -25,6 +25,13 @@
  * constant-image gain 2^n, zero-sum detail bands, the 4x energy identity per level for
  * orthonormal filters, shift equivariance, impulse responses, and agreement with the
  * independent numpy restatement oracle/swt_np.py.
+ * Outside anchor (tests/test_swt_anchor.py, table in tests/swt_anchor_cases.py): numbers the
+ * reference's own lifting code produced (main/transforms/wavelets/{haar,daub_4,cdf_97}.py run
+ * level after level on LL) equal this transform sampled on the 2^n lattice, up to the lifting's
+ * scales.  That pins the tap offset, the axis order, cH = 'da', the sign of dec_hi and the taps
+ * of haar levels 1-3, db2 levels 1-3 and bior4.4 levels 1-2.  Still unpinned: db4 and the
+ * computed dbN (no lifting in the reference), the periodic wrap at the border (the lifting pads
+ * with zeros), and PyWavelets' executed output.
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may call this.
  */

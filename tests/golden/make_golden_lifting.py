@@ -23,17 +23,31 @@ REF = "/root/reference"
 sys.dont_write_bytecode = True
 
 
-def load_reference_wavelets():
+def load_reference_wavelets(daub4=False):
+    """-> (fast_haar_2d_op, fast_cdf97_2d_op); with `daub4` also the reference's daub_4 and utils modules.  daub_4.py
+    imports `wavelets.utils` and `vis_utils` absolutely: the first name is pointed at the utils module loaded here, the
+    second at an empty stub that carries the two names it asks for (plotting helpers, never called)."""
     pkg_dir = os.path.join(REF, "main", "transforms", "wavelets")
     pkg = types.ModuleType("refwavelets")
     pkg.__path__ = [pkg_dir]
     sys.modules["refwavelets"] = pkg
-    for name in ("utils", "haar", "cdf_97"):
+    names = ("utils", "haar", "cdf_97") + (("daub_4",) if daub4 else ())
+    for name in names:
+        if name == "daub_4":
+            stub_pkg = types.ModuleType("wavelets")
+            stub_pkg.__path__ = []
+            stub_pkg.utils = sys.modules["refwavelets.utils"]
+            vis = types.ModuleType("vis_utils")
+            vis.prepare_input_image = vis.show_lifting_results = None
+            sys.modules.update({"wavelets": stub_pkg, "wavelets.utils": stub_pkg.utils, "vis_utils": vis})
         spec = importlib.util.spec_from_file_location(f"refwavelets.{name}", os.path.join(pkg_dir, f"{name}.py"))
         mod = importlib.util.module_from_spec(spec)
         sys.modules[f"refwavelets.{name}"] = mod
         spec.loader.exec_module(mod)
-    return sys.modules["refwavelets.haar"].fast_haar_2d_op, sys.modules["refwavelets.cdf_97"].fast_cdf97_2d_op
+    ops = sys.modules["refwavelets.haar"].fast_haar_2d_op, sys.modules["refwavelets.cdf_97"].fast_cdf97_2d_op
+    if daub4:
+        return ops + (sys.modules["refwavelets.daub_4"], sys.modules["refwavelets.utils"])
+    return ops
 
 
 CASES = [  # name, basis, shape [N,C,H,W], levels, seed
