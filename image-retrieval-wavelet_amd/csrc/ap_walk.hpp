@@ -1,9 +1,11 @@
-// Average precision from relevance bits in list order -- the arithmetic and summation order of k_map_at_k (topk.hip):
-// position p = round * TPQ + t, the j-th hit adds the fp32 quotient j / (p + 1) to a double, threads summed per wave,
-// waves in index order.  Shared by the fused ranking + AP kernel (rank2.hip) and the merge of per-shard relevance
-// strings (topk.hip).
+// Average precision from relevance bits in list order -- the arithmetic and summation order of wv_map_at_k, stated
+// independently by its host twin (host_rank.cpp): position p = round * TPQ + t, the j-th hit adds the fp32 quotient
+// j / (p + 1) to a double, threads summed per wave, waves in index order.  Shared by the fused ranking + AP kernel
+// (rank2.hip), the batch mAP proxy (ip_map.hip), the merge of per-shard relevance strings (merge.hip) and the AP of
+// written lists (list_ap.hip).
 #pragma once
 #include "common.hpp"
+#include "ap_cuts.hpp"
 
 namespace wv {
 
@@ -17,8 +19,8 @@ __host__ __device__ constexpr int ap_scratch_dwords() { return kApRounds * (TPQ 
 //   ApState st;  for every chunk { lane 0 of every wave writes cnt[r_local * NW + wave] = hits of that wave in the round;
 //                                  group barrier;  ap_accum(relbits, cnt, rounds, first round, t, st);  group barrier; }
 //   ap_final(st, ...).
-// A thread's quotients are added to its double in increasing list position whatever the chunking: the result equals
-// k_map_at_k's bit for bit.
+// A thread's quotients are added to its double in increasing list position whatever the chunking: the result does not
+// depend on it, bit for bit.
 struct ApState {
     uint32_t running = 0;    // hits before the current round, all threads
     double acc = 0.0;        // this thread's sum of fp32 quotients j / rank
@@ -81,12 +83,7 @@ __device__ __forceinline__ void ap_final(const ApState &st, double *wsum, int t,
 // List position p = round * TPQ + t does not depend on k, a thread adds its quotients in increasing position, and the list
 // for the largest cut-off has the list for every smaller one as a prefix (the order distance, then row is total): AP@c is
 // a snapshot of the walk to k_max, taken in the round that holds position c - 1, with the bits of a walk to c.
-constexpr int kMaxCutoffs = 16;              // = WV_MAX_CUTOFFS (wvhash.h)
-
-struct ApCuts {                              // travels by value in the kernel arguments: no device copy, no sync
-    int n;                                   // 1 .. kMaxCutoffs
-    int k[kMaxCutoffs];                      // strictly ascending, k[0] >= 1; the walk is k[n - 1] positions long
-};
+// ApCuts and the rule for its contents: ap_cuts.hpp.
 
 // dwords of LDS scratch of the multi-cut walk: the single-cut walk's + the waves' hit counts below a cut
 template <int TPQ>
@@ -160,6 +157,43 @@ __device__ __forceinline__ void ap_accum_cuts(uint32_t relbits, const uint32_t *
                 st.running += tot;
             }
         }
+    }
+}
+
+// The whole walk of a 256-thread workgroup that owns one query, at the cut-offs `cuts`: what the multi-cut merge of relevance
+// strings (k_merge_relbits_ap_cuts, merge.hip) and the multi-cut AP over written lists (k_map_at_ks, list_ap.hip) share.  rel_at(p) = relevance of list
+// position p < k (free of side effects: the last position is asked again for the padding of the last round); scratch:
+// ap_cuts_scratch_dwords<256>() dwords of LDS, 8-byte aligned; ap / nrel: the query's rows of cuts.n entries.
+template <typename REL>
+__device__ __forceinline__ void walk_cuts_256(REL rel_at, int k, uint32_t *scratch, const ApCuts &cuts, float *__restrict__ ap,
+                                              int32_t *__restrict__ nrel)
+{
+    constexpr int CH = 8;
+    const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
+    const int R = (k + 255) / 256;
+    double *wsum = reinterpret_cast<double *>(scratch + kApRounds * 4 + (kApRounds * 4 & 1));
+    uint32_t *wcut = reinterpret_cast<uint32_t *>(wsum + 4);
+    ApState st;
+    int next = 0;
+    for (int c0 = 0; c0 < R; c0 += kApRounds) {                   // chunks of 32 rounds: any k (mAP@ALL: k = database size)
+        const int Rc = min(kApRounds, R - c0);
+        uint32_t mine = 0;
+        for (int r0 = 0; r0 < Rc; r0 += CH) {                     // a batch's reads are issued before the first is used
+            bool rv[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) rv[u] = rel_at(min((c0 + r0 + u) * 256 + tid, k - 1));
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                const int r = r0 + u;
+                const bool rel = r < Rc && (c0 + r) * 256 + tid < k && rv[u];
+                mine |= (rel ? 1u : 0u) << (r & 31);
+                const uint64_t m = __ballot(rel);
+                if (lane == 0 && r < Rc) scratch[r * 4 + wv] = (uint32_t)__popcll(m);
+            }
+        }
+        __syncthreads();
+        ap_accum_cuts<256>(mine, scratch, Rc, c0, tid, st, cuts, next, wsum, wcut, ap, nrel, [] { __syncthreads(); });
+        __syncthreads();
     }
 }
 

@@ -85,6 +85,19 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(v), 63);
 }
 
+// Exclusive scan over the bins of per-bin totals held 3 bins per lane of one wave (lane l: bins 3l .. 3l + 2; 192 >=
+// the 130 bins of the Hamming ranking): base[b] = sum of the bins below b.  Returns the sum of the bins below the lane's first.
+__device__ __forceinline__ uint32_t bin_scan3(const uint32_t (&t)[3], int nbins, uint32_t *base, int lane)
+{
+    const int b0 = 3 * lane;
+    const uint32_t incl = wave_incl_scan_u32(t[0] + t[1] + t[2]);
+    const uint32_t excl = incl - (t[0] + t[1] + t[2]);
+    if (b0 < nbins) base[b0] = excl;
+    if (b0 + 1 < nbins) base[b0 + 1] = excl + t[0];
+    if (b0 + 2 < nbins) base[b0 + 2] = excl + t[0] + t[1];
+    return excl;
+}
+
 __device__ __forceinline__ double wave_sum_f64(double v)
 {
 #pragma unroll

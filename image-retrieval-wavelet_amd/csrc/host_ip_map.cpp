@@ -4,7 +4,7 @@
 // The contract defines the result as wv_map_at_k applied to the list wv_knn_float(metric IP, k) returns, so the twin IS that
 // composition of the two existing twins, query block by query block: wv_knn_float_cpu forms every score as one fmaf chain in
 // accumulation_order(D) (host_knn.cpp) and ranks on (order-preserving key, row); wv_map_at_k_cpu walks the list with
-// k_map_at_k's arithmetic and summation order (host_rank.cpp).  What this file adds is the entry point's own argument rules
+// wv_map_at_k's arithmetic and summation order (host_rank.cpp).  What this file adds is the entry point's own argument rules
 // (ip_map.hpp, shared with the kernel) and the block loop that keeps the list at kBlock rows.  The kernel restates both
 // stages on the device (scalar fmaf chains, an in-LDS sort, the walk of ap_walk.hpp); the GPU tests hold it to these bits.
 // No HIP call, no thread, no global state.

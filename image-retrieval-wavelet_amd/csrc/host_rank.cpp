@@ -6,9 +6,10 @@
 //
 // Same results as the gfx950 kernels, bit for bit: integers by construction (packed words, counts, distances, the order
 // ascending distance then ascending database row = torch.argsort(stable=True)); the average precision because the fp32
-// quotients j / rank are summed in k_map_at_k's order (topk.hip: position p belongs to thread p % 256, a thread's
-// quotients accumulate in a double, the 64 lanes of a wave combine in the xor-butterfly of wave_sum_f64, the four waves
-// add up in index order).  No HIP call, no thread, no global state; plain C++ for the host, no fused multiply-add.
+// quotients j / rank are summed in the order of the kernels' walk (ap_walk.hpp: position p belongs to thread p % 256, a
+// thread's quotients accumulate in a double, the 64 lanes of a wave combine in the xor-butterfly of wave_sum_f64, the four
+// waves add up in index order).  wv_map_at_k_cpu states that arithmetic in a plain loop of its own: the list kernel
+// (list_ap.hip) is held against it bit for bit on the GPU.  No HIP call, no thread, no global state; plain C++ for the host, no fused multiply-add.
 // Product code: shares nothing with oracle/.
 #include <math.h>
 #include <stdint.h>
@@ -16,6 +17,7 @@
 
 #include <vector>
 
+#include "ap_cuts.hpp"
 #include "twin.hpp"
 
 namespace {
@@ -153,7 +155,7 @@ extern "C" int wv_hamming_topk_cpu(const uint64_t *q, const uint64_t *db, int32_
 }
 
 // Average precision over the first k entries of each ranked list (row pitch ld >= k), the arithmetic and the summation
-// order of k_map_at_k (see the file header); entries < 0 are skipped like there.
+// order of wv_map_at_k (see the file header); entries < 0 are skipped like there.
 extern "C" int wv_map_at_k_cpu(const int32_t *idx, int64_t ld, int Q, int k, const uint64_t *qlab, const uint64_t *dblab,
                                int lwords, float *ap, int32_t *nrel)
 {
@@ -187,12 +189,8 @@ extern "C" int wv_map_at_ks_cpu(const int32_t *idx, int64_t ld, int Q, const int
 {
     WV_REQUIRE(idx && qlab && dblab && ap, "map_at_ks_cpu: null buffer");
     WV_REQUIRE(Q >= 0 && ld >= 1 && lwords >= 1, "map_at_ks_cpu: bad shape Q=%d ld=%lld lwords=%d", Q, (long long)ld, lwords);
-    WV_REQUIRE(ks, "map_at_ks_cpu: null cut-off list");
-    WV_REQUIRE(nk >= 1 && nk <= WV_MAX_CUTOFFS, "map_at_ks_cpu: %d cut-offs (supported: 1..%d)", nk, WV_MAX_CUTOFFS);
-    WV_REQUIRE(ks[0] >= 1, "map_at_ks_cpu: cut-off %d must be >= 1", ks[0]);
-    for (int i = 1; i < nk; ++i)
-        WV_REQUIRE(ks[i] > ks[i - 1], "map_at_ks_cpu: cut-offs must be strictly ascending (ks[%d]=%d after %d)", i, ks[i], ks[i - 1]);
-    WV_REQUIRE(ks[nk - 1] <= ld, "map_at_ks_cpu: largest cut-off %d must be <= ld=%lld", ks[nk - 1], (long long)ld);
+    wv::ApCuts cuts;
+    if (int rc = wv::validate_cuts("map_at_ks_cpu", ks, nk, ld, "ld", cuts)) return rc;
     for (int qi = 0; qi < Q; ++qi) {
         const int32_t *list = idx + (int64_t)qi * ld;
         const uint64_t *ql = qlab + (int64_t)qi * lwords;

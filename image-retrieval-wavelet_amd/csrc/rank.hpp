@@ -1,12 +1,12 @@
 // Hamming ranking, host side: which kernel ranks a shape and what it needs (the planner), where each kernel's database
-// image lies in a prepared blob, and the interface between topk.hip (entry points, column kernel, merges) and rank2.hip
+// image lies in a prepared blob, and the interface between topk.hip (entry points, column kernel) and rank2.hip
 // (windowed kernel).  Every fit rule lives in rank_plan(): the entry points ask it and launch what it answers.
 #pragma once
 #include "common.hpp"
 
 namespace wv {
 
-struct ApCuts;                               // ap_walk.hpp
+struct ApCuts;                               // ap_cuts.hpp
 
 constexpr int kTopkThreads = 256;            // threads per workgroup of every ranking kernel
 constexpr int kMaxBins = 130;                // nbits <= 128 (+1 bin for the padding value of ragged shard lists)
@@ -35,6 +35,13 @@ enum class RankMode {
 // takes C <= 64 items per lane, 256 threads per query C <= 128 (distances cached in registers, 16-bit item numbers)
 constexpr int64_t kImg64MaxRows = 64 * 64;
 constexpr int64_t kImg256MaxRows = 256 * 128;
+
+// the code width every Hamming ranking and merge entry point takes (topk.hip, merge.hip)
+inline int require_nbits(const char *what, int nbits)
+{
+    WV_REQUIRE(nbits >= 1 && nbits <= 128, "%s: nbits=%d (supported: 1..128)", what, nbits);
+    return WV_OK;
+}
 
 // threads that share one query
 constexpr int rank_threads_per_query(RankKernel kern) { return kern == RankKernel::window64 ? 64 : 256; }

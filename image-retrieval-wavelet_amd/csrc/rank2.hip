@@ -26,7 +26,7 @@
 //     to be read back by the AP kernel, which then gathers 8-byte labels at random (the gather unit serves ~1 lane per
 //     clock: half of that kernel's time).  Here the labels come as a class-major bit matrix: the OR of the rows of the
 //     query's classes is its relevance bitmap (N bits, in LDS), and after placement the list in LDS is walked against
-//     the bitmap -- same thread <-> position mapping and summation order as k_map_at_k, bit-identical AP.
+//     the bitmap -- same thread <-> position mapping and summation order as wv_map_at_k, bit-identical AP.
 // Covers databases (shards) of at most 32,768 rows -- C <= 128 items per thread, their distances cached in registers as
 // bytes; 16-bit item numbers and counters -- and k small enough for the LDS list; everything else stays on topk.hip's
 // kernel (the rules: rank_plan(), rank.hpp).
@@ -257,7 +257,7 @@ __device__ __forceinline__ void rank2_relevance_bitmap(const uint32_t *__restric
     // the caller's next group barrier (there are several before the list is walked) makes the bitmap visible
 }
 
-// AP of the list in LDS (k_map_at_k's arithmetic and order: position p = round * TPQ + t, the j-th hit adds the fp32
+// AP of the list in LDS (wv_map_at_k's arithmetic and order: position p = round * TPQ + t, the j-th hit adds the fp32
 // quotient j / (p + 1) to a double, waves summed in index order).  scratch: free LDS, (32 * NW + 2 * NW + 2) dwords.
 // relbits_out (or NULL): the relevance string itself, bit p of the uint64 array = relevance of list position p -- what a
 // shard contributes to the sharded mAP (wv_hamming_shard_relbits); no AP is computed then.

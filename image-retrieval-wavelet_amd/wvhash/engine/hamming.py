@@ -714,7 +714,7 @@ def _merge_relbits(what, wire, kin, k, ks, nbits, need_out):
         with torch.cuda.device(wire.device):
             rc = getattr(lib, "wv_" + what)(*_wire_args(wire, nbits), G, Q, kin, *cargs, nbits, _lib.ptr(ap), _lib.ptr(nrel),
                                             _lib.ptr(need_out), _lib.stream_ptr())
-            if rc == _lib.WV_ENOTSUP and ks is not None:         # only the multi-k kernel keeps the merged string in LDS
+            if rc == _lib.WV_ENOTSUP:                            # the merged string does not fit the kernel's LDS
                 return None
             _lib.check(rc, "wv_" + what)
     return _columns(ap, nrel, cols)
@@ -722,16 +722,16 @@ def _merge_relbits(what, wire, kin, k, ks, nbits, need_out):
 
 def merge_relbits_map(wire, kin, k, nbits, need_out=None):
     """wire int64 [G, Q, relbits_wire_words(kin, nbits)] -- the rows hamming_shard_relbits made on G contiguous row shards in
-    rank order -> (ap float32 [Q], nrel int32 [Q]) of the merged top-k lists, equal to map_at_k of the merged lists.
-    need_out as in topk_merge_cum."""
+    rank order -> (ap float32 [Q], nrel int32 [Q]) of the merged top-k lists, equal to map_at_k of the merged lists, or
+    None when the k-bit merged string does not fit the kernel's LDS.  need_out as in topk_merge_cum."""
     return _merge_relbits("merge_relbits_map", wire, kin, k, None, nbits, need_out)
 
 
-MERGE_LDS_LIMIT = 60 * 1024  # WV_MERGE_RELBITS_LDS_LIMIT: dynamic LDS above which wv_merge_relbits_map_ks answers WV_ENOTSUP
+MERGE_LDS_LIMIT = 60 * 1024  # WV_MERGE_RELBITS_LDS_LIMIT: dynamic LDS above which wv_merge_relbits_map[_ks] answer WV_ENOTSUP
 
 
 def merge_relbits_lds_bytes(G, k, nbits):
-    """LDS wv_merge_relbits_map_ks needs for G shards and a largest cut-off k, as the library itself computes it
+    """LDS wv_merge_relbits_map[_ks] need for G shards and a (largest) cut-off k, as the library itself computes it
     (wv_merge_relbits_map_ks_lds_bytes; no GPU needed).  Callers that must decide a fallback before any rank exchanges
     anything (parallel.sharded_hamming_map_at_k) hold it against MERGE_LDS_LIMIT."""
     return int(_lib.load().wv_merge_relbits_map_ks_lds_bytes(int(G), int(k), int(nbits)))

@@ -282,7 +282,7 @@ def sharded_hamming_map_at_k(q_local, qlab_local, db_shard, labels_shard, nbits,
     lwords = qlab_local.shape[1]                         # 1 label word (<= 64 classes) or 2 (COCO's 80, NUS-WIDE's 81)
     if per > H.SHARD_ROWS_MAX or min(kmax, per) > H.RANK_K_MAX or lwords not in (1, 2) or nbits > 128:
         return None                                      # decided from values every rank shares: no rank goes another way
-    if multi and (len(set(k)) > H.MAX_CUTOFFS or H.merge_relbits_lds_bytes(world, kmax, nbits) > H.MERGE_LDS_LIMIT):
+    if (multi and len(set(k)) > H.MAX_CUTOFFS) or H.merge_relbits_lds_bytes(world, kmax, nbits) > H.MERGE_LDS_LIMIT:
         return None                                      # likewise: world, max(k) and nbits are the same on every rank
     dev = q_local.device
     both_all = _gather_rows(torch.cat([q_local, qlab_local], dim=1), world, group)   # codes | label words: one collective

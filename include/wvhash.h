@@ -360,8 +360,11 @@ int wv_topk_merge_cum_need(const uint16_t *idx_local, const uint32_t *cum, int G
  * relbits_ld / cum_ld: row pitches in uint64 / uint32 units (0 = tight): string and histogram of a (query, shard) may lie side
  * by side in ONE wire buffer, so that a single all_to_all moves both; words of a row that belong to neither are not written.
  * relbits 8-byte, cum 4-byte aligned.
- * WV_ENOTSUP outside the windowed kernel's range (shards of more than 32,768 rows, k > 32,639, wider labels); any k inside it:
- * a shard can send the relevance string of its whole ranking (mAP@ALL). */
+ * wv_hamming_shard_relbits: WV_ENOTSUP outside the windowed kernel's range (shards of more than 32,768 rows, k > 32,639, wider
+ * labels); any k inside it: a shard can send the relevance string of its whole ranking (mAP@ALL).
+ * wv_merge_relbits_map: WV_ENOTSUP when the k-bit merged string does not fit LDS beside the run boundaries of the G shards
+ * (wv_merge_relbits_map_ks_lds_bytes(G, k, nbits) > WV_MERGE_RELBITS_LDS_LIMIT, below); nothing is written, and the caller
+ * then merges the lists and runs wv_map_at_k. */
 int wv_hamming_shard_relbits(const uint64_t *q, const void *prepared, const void *prepared_labels, const uint64_t *qlab,
                              int lwords, uint64_t *relbits, int64_t relbits_ld, uint32_t *cum, int64_t cum_ld, int Q, int64_t N,
                              int nbits, int k, void *stream);
@@ -424,8 +427,9 @@ int wv_map_at_k_ld(const int32_t *idx, int64_t ld, int Q, int k, const uint64_t 
  * WV_ENOTSUP when the largest cut-off is outside the fused kernel (wv_hamming_map_at_ks: as wv_hamming_map_at_k) or its merged
  * string does not fit LDS (wv_merge_relbits_map_ks): the caller then runs wv_hamming_topk + wv_map_at_ks. */
 #define WV_MAX_CUTOFFS 16
-/* dynamic LDS wv_merge_relbits_map_ks needs for G shards and a largest cut-off kmax (0 for arguments it refuses); the call
- * answers WV_ENOTSUP above WV_MERGE_RELBITS_LDS_LIMIT.  For callers that must know before they exchange anything. */
+/* dynamic LDS wv_merge_relbits_map_ks and wv_merge_relbits_map (kmax = its k) need for G shards and a largest cut-off kmax
+ * (0 for arguments they refuse): their kernels share one LDS layout, sized here.  Either call answers WV_ENOTSUP above
+ * WV_MERGE_RELBITS_LDS_LIMIT.  For callers that must know before they exchange anything. */
 #define WV_MERGE_RELBITS_LDS_LIMIT (60 * 1024)
 size_t wv_merge_relbits_map_ks_lds_bytes(int G, int kmax, int nbits);
 int wv_hamming_map_at_ks(const uint64_t *q, const void *prepared, const void *prepared_labels, const uint64_t *qlab, int lwords,

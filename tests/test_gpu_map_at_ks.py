@@ -155,20 +155,34 @@ def test_merge_of_relevance_strings_at_several_cutoffs(short):
 @pytest.mark.parametrize("classes", [38, 80, 130])
 def test_list_kernel_reads_the_lists_once_for_all_cutoffs(classes):
     """wv_map_at_ks over lists of pitch ld > k_max against wv_map_at_k_ld per cut-off and against the host twin (one, two and
-    three label words: the last takes the kernel's generic label loop)."""
+    three label words: the last takes the kernels' generic label loop).  Both kernels live in list_ap.hip and share the
+    relevance test, so the single-cut one is anchored to the host twin's own plain loop (wv_map_at_k_cpu), bit for bit, at
+    every cut-off: 256 is the round boundary, 32 * 256 = 8192 the chunk boundary of the multi-cut walk."""
     c = _inputs(24, 9000, 64, classes, 31)
-    idx, _ = H.hamming_topk(c["qp"], c["rp"], 64, 3000, want_dist=False)
+    idx, _ = H.hamming_topk(c["qp"], c["rp"], 64, 8500, want_dist=False)
     idx[5, 77] = -1                                              # an absent entry is skipped
-    ks = (1, 255, 256, 257, 2048, 2049, 2500)
-    assert idx.stride(0) == 3000 > ks[-1]
+    ks = (1, 255, 256, 257, 2048, 2049, 2500, 8191, 8192, 8193)
+    assert idx.stride(0) == 8500 > ks[-1]
+    idx_h, qlp_h, rlp_h = idx.cpu(), c["qlp"].cpu(), c["rlp"].cpu()
     ap, nrel = H.map_at_ks(idx, c["qlp"], c["rlp"], ks)
     for i, k in enumerate(ks):
         ap1, nrel1 = H.map_at_k(idx, c["qlp"], c["rlp"], k=k)
         assert torch.equal(nrel[:, i], nrel1) and torch.equal(_bits(ap[:, i]), _bits(ap1)), k
-        if k >= 64:
-            assert (nrel1 > 0).float().mean().item() >= 0.9
-    ap_h, nrel_h = HH.map_at_ks(idx.cpu(), c["qlp"].cpu(), c["rlp"].cpu(), ks)
+        ap1_h, nrel1_h = HH.map_at_k(idx_h, qlp_h, rlp_h, k=k)
+        if k >= 64:                                              # a condition on the inputs, from the host twin alone
+            assert (nrel1_h > 0).float().mean().item() >= 0.9
+        assert torch.equal(nrel1.cpu(), nrel1_h), (k, nrel1.tolist(), nrel1_h.tolist())
+        assert torch.equal(_bits(ap1.cpu()), _bits(ap1_h)), (k, (ap1.cpu() - ap1_h).abs().max().item())
+    ap_h, nrel_h = HH.map_at_ks(idx_h, qlp_h, rlp_h, ks)
     assert torch.equal(nrel.cpu(), nrel_h) and torch.equal(_bits(ap.cpu()), _bits(ap_h))
+    # the C entry point itself, nrel = NULL: the same AP bits, nothing else asked for
+    k = 8193
+    ap_c = torch.full((24,), float("nan"), device="cuda")
+    with torch.cuda.device(idx.device):
+        rc = _lib.load().wv_map_at_k_ld(_lib.ptr(idx), idx.stride(0), 24, k, _lib.ptr(c["qlp"]), _lib.ptr(c["rlp"]), c["qlp"].shape[1],
+                                        _lib.ptr(ap_c), None, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0 and torch.equal(_bits(ap_c.cpu()), _bits(HH.map_at_k(idx_h, qlp_h, rlp_h, k=k)[0]))
 
 
 def test_against_the_oracles_canonical_order(c64, capsys):
@@ -273,3 +287,15 @@ def test_a_largest_cutoff_that_does_not_fit_is_refused_and_the_fallback_gives_th
     assert H.merge_relbits_lds_bytes(2, fits + 32, 64) > H.MERGE_LDS_LIMIT
     assert H.merge_relbits_map_ks(wire, 64, [10, fits], 64) is not None
     assert H.merge_relbits_map_ks(wire, 64, [10, fits + 32], 64) is None
+    # a single cut-off keeps the same string in the same LDS layout: the same refusal, the same sentence, the same flip
+    assert H.merge_relbits_map(wire, 64, 2000000, 64) is None
+    assert "does not fit" in _lib.load().wv_last_error().decode()
+    assert H.merge_relbits_map(wire, 64, fits, 64) is not None
+    assert H.merge_relbits_map(wire, 64, fits + 32, 64) is None
+    ap = torch.full((5,), -3.0, device="cuda")
+    nrel = torch.full((5,), -3, dtype=torch.int32, device="cuda")
+    with torch.cuda.device(wire.device):
+        rc = _lib.load().wv_merge_relbits_map(wire.data_ptr() + 8 * 33, wire.shape[2], wire.data_ptr(), 2 * wire.shape[2], 2, 5, 64,
+                                              2000000, 64, _lib.ptr(ap), _lib.ptr(nrel), None, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == _lib.WV_ENOTSUP and (ap == -3.0).all() and (nrel == -3).all()

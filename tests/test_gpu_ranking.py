@@ -629,7 +629,9 @@ def test_fused_map_at_k_refuses_what_it_cannot_do():
                                               (21, 20000, 128, 5000, 7, 64), (9, 40, 32, 7, 5, 3), (64, 25000, 64, 5000, 8, 38),
                                               (33, 117218, 128, 5000, 8, 80),
                                               # mAP@ALL (k = N): every shard sends the relevance string of its whole ranking
-                                              (5, 117218, 128, 117218, 8, 80), (7, 19581, 64, 19581, 2, 24), (4, 3000, 64, 3000, 8, 38)])
+                                              (5, 117218, 128, 117218, 8, 80), (7, 19581, 64, 19581, 2, 24), (4, 3000, 64, 3000, 8, 38),
+                                              # a single cut-off on and just past the walk's chunk boundary (32 rounds of 256)
+                                              (5, 9000, 64, 8192, 3, 38), (5, 9000, 64, 8193, 3, 38)])
 def test_sharded_map_from_relevance_strings_equals_unsharded(Q, N, nbits, k, G, Lc):
     """What the ranks of sharded_hamming_map_at_k run, for G shards on one GPU: wv_hamming_shard_relbits per shard (relevance
     string of the prefix + histograms) -> wv_merge_relbits_map.  AP and hit counts must equal map_at_k of the unsharded
@@ -695,7 +697,7 @@ def test_databases_beyond_32768_rows_take_virtual_shards(Q, N, nbits, k, Lc):
 def test_host_rank_twins_equal_the_kernels(Q, N, nbits, k, lc):
     """csrc/host_rank.cpp (CustomCalculator(device='cpu')) and the gfx950 kernels return the same bits: packed words, per-bit
     counts, distance matrix, ranked lists + distance rows, running hit counts -- and the average precision, whose fp32
-    quotients the twin sums in k_map_at_k's order (thread, wave butterfly, waves)."""
+    quotients the twin sums in the list kernel's order (thread, wave butterfly, waves)."""
     from wvhash.engine import hamming_host as HH
     ql, rl = synth.multi_hot_labels(Q, lc, 0.1, 21), synth.multi_hot_labels(N, lc, 0.1, 22)
     q, r = synth.structured_codes(ql, nbits, 3, 23), synth.structured_codes(rl, nbits, 3, 24)

@@ -242,6 +242,18 @@ def _map_worker(rank, world, port, cases, nbits, ql, out_dir, lc=12, p=0.2):
                 ap_i, nrel_i = (ap, nrel) if ki == k else parallel.sharded_hamming_map_at_k(
                     _pack(q_all[sl]), _label_words(ql_all[sl]), _pack(r[lo:hi]), _label_words(rl[lo:hi]), nbits, ki, n_db, hint)[:2]
                 assert torch.equal(ap_s[:, i], ap_i) and torch.equal(nrel_s[:, i], nrel_i), (n_db, ks, hint, i)
+    # a cut-off whose merged string does not fit the merge kernel's LDS, single or in a sequence: None (the caller's list
+    # fallback) from values every rank shares, before any collective
+    n_db = cases[0][0]
+    lo, hi, _ = parallel.shard_bounds(n_db, world, rank)
+    q, r = synth.random_codes(ql, n_db, nbits, seed=3)
+    qlab, rl = synth.multi_hot_labels(ql, lc, p, 5), synth.multi_hot_labels(n_db, lc, p, 6)
+    assert H.merge_relbits_lds_bytes(world, 2_000_000, nbits) > H.MERGE_LDS_LIMIT
+    for k in (2_000_000, [10, 2_000_000]):
+        parallel.TRACE = parallel.ExchangeTrace()
+        got = parallel.sharded_hamming_map_at_k(_pack(q), _label_words(qlab), _pack(r[lo:hi]), _label_words(rl[lo:hi]), nbits, k, n_db, 1)
+        calls, parallel.TRACE = parallel.TRACE.calls, None
+        assert got is None and calls == {"all_gather": 0, "all_to_all": 0, "all_reduce": 0}, (k, got, calls)
     torch.save(out, os.path.join(out_dir, f"m{rank}.pt"))
     dist.barrier()
     dist.destroy_process_group()
