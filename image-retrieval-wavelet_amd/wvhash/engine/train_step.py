@@ -136,6 +136,17 @@ def _micro_batches(total, sub_batch):
     return [(s, starts[i + 1] if i + 1 < len(starts) else total) for i, s in enumerate(starts)]
 
 
+def _label_matrix(labels):
+    """fp32 [B, B] target of the pairwise losses (main/utils/create_label_matrix.py:10-22): the labels squeezed first, so
+    class ids given as [B, 1] are ids, not one-column multi-hot rows; ids are compared, multi-hot rows overlap."""
+    labels = labels.squeeze()
+    if labels.ndim == 1:
+        return (labels.view(-1, 1) == labels.view(1, -1)).float()
+    if labels.ndim == 2:
+        return ((labels.float() @ labels.float().t()) > 0).float()
+    raise NotImplementedError(f"labels of {labels.ndim} dimensions have no label matrix")
+
+
 def _criterion_loss(criteria, emb, labels, logs):
     losses = []
     for crit, weight in criteria:
@@ -143,8 +154,7 @@ def _criterion_loss(criteria, emb, labels, logs):
             flat = labels.ndim == 1 or (labels.ndim == 2 and labels.size(1) == 1)
             loss = crit(emb, labels.view(-1) if flat else labels)
         else:   # pairwise losses see the score matrix and the label matrix (base_update.py:96-98)
-            same = labels.view(-1, 1) == labels.view(1, -1) if labels.ndim == 1 else (labels.float() @ labels.float().t()) > 0
-            loss = crit(emb @ emb.t(), same.float())
+            loss = crit(emb @ emb.t(), _label_matrix(labels))
         loss = loss.mean()
         losses.append(weight * loss)
         logs[type(crit).__name__] = float(loss.detach())
@@ -205,7 +215,10 @@ def backward_step(net, images, labels, criteria, autocast_dtype=torch.bfloat16, 
             states.append(_rng_snapshot(device))
             with _autocast(device.type, autocast_dtype):
                 cached.append(net(images[s:e]))
-    emb_full = torch.cat(cached, dim=0).float().detach().requires_grad_()
+    emb_full = torch.cat(cached, dim=0)
+    if emb_full.dtype != torch.float64:                 # a float64 model (the tests' high-precision yardstick) stays float64
+        emb_full = emb_full.float()
+    emb_full = emb_full.detach().requires_grad_()
     with _autocast(device.type, autocast_dtype):
         losses = _criterion_loss(criteria, emb_full, labels, logs)
         total_loss = sum(losses)
